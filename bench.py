@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): images/sec of the Mask R-CNN inference hot path at 1024x1024 with
 1000 proposals per image on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N=1 by default)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]          (N=1 by default)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +13,10 @@ fixed-shape detections. Workload at every N: BASELINE.json configs[2] per GPU (R
 synthetic 1024x1024) → weak scaling; N=8 is configs[3] (batch 64 sharded over 8 GPUs). Inputs are resident
 in HBM before the timed region. fp32 throughout (exact-fp32 MFMA).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+A plain run sets up, warms up, times EXACTLY K steps (one repetition), writes the last step's outputs with
+--dump-outputs DIR, and prints ONE JSON line on rank 0 with the driver's contract fields (`metric`, `value` images/s,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step). Everything else is measured only
+with --full, which adds three timed repetitions of K steps (`value` = the median one) and
   `roofline`      the dominant kernel (largest summed duration in a step: the direct implicit-GEMM kernel conv_igemm_f32 or
                   the F(4x4) Winograd kernel conv3x3_wino4_f32): the multiply-adds it EXECUTES (2*M*N*K, / 2.25 for Winograd
                   F(2x2,3x3), / 4 for F(4x4,3x3)) / its summed launch durations — HIP events on the launch stream around every conv
@@ -27,7 +30,8 @@ Prints ONE JSON line on rank 0 with the driver's contract fields plus
   `alt_configs`   never `value`: the headline step with SURVEY 8(d)'s 1000 VALID proposals per image injected behind the proposal
                   stage; MaskRCNNInference.detect() (uint8 images in, full-size masks out) beside predict() on the same batch;
                   BASELINE configs[4]'s geometry (R101-FPN, 832x1344, fp16 MFMA path) on this GPU;
-  `per_rank_ms_per_step`  slowest / fastest rank's own K steps per repetition (a straggler shows the first time N > 1 runs);
+  `per_rank_ms_per_step`  (every run) slowest / fastest rank's own K steps per repetition (a straggler shows the first time
+                  N > 1 runs);
   `cpu_baseline`  the CPU oracle's predict() on a bounded sample of the same workload, timed on this host's cores.
 """
 import argparse
@@ -39,6 +43,8 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+T_START = time.perf_counter()
 
 import torch  # noqa: E402
 
@@ -70,7 +76,9 @@ def kernel_source_sha16():
 def calibrate_heads_(sd, make_net, images, windows):
     """Random weights saturate the RPN/classifier softmaxes and blow up box deltas, which makes every
     proposal degenerate. Rescale the four head layers (weights only, deterministic) until scores are
-    spread and boxes sane, so the proposal/detection stages see realistic, diverse boxes."""
+    spread and boxes sane, so the proposal/detection stages see realistic, diverse boxes. Each factor is rounded to three
+    significant digits, so that builds whose arithmetic differs in the last bits still time (and --dump-outputs) the same
+    weights."""
     net = None
     for _ in range(8):
         net = make_net(sd)
@@ -84,7 +92,7 @@ def calibrate_heads_(sd, make_net, images, windows):
                                         ("classifier.linear_class.weight", cstd, 2.0, 3.0),
                                         ("classifier.linear_bbox.weight", bstd, 0.5, 1.0)):
             if cur > limit:
-                sd[key] = sd[key] * (target / cur)
+                sd[key] = sd[key] * float(f"{target / cur:.3g}")
                 done = False
         if done:
             break
@@ -475,7 +483,13 @@ def main():
                     help="with --gpus N > 1 outside torchrun: print the child command bench.py would start, and exit")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=3, help="timed repetitions of --steps steps; value = the median one")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (repetitions, roofline and traffic, other precisions and "
+                         "configurations, CPU baseline, batches in flight); without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of --steps steps; value = the median one (default: 1, or 3 with --full)")
     ap.add_argument("--batch", type=int, default=8, help="images per GPU per step (configs[2]: 8)")
     ap.add_argument("--arch", default="resnet50")
     ap.add_argument("--size", type=int, default=1024, help="square image side (BASELINE metric: 1024)")
@@ -505,13 +519,20 @@ def main():
     ap.add_argument("--alt-config5", type=int, default=1,
                     help="also time BASELINE configs[4]'s geometry (R101-FPN, 832x1344, fp16 MFMA path) on this GPU, N=1 only")
     args = ap.parse_args()
+    if args.dump_conv and not args.full:
+        ap.error("--dump-conv times the per-launch roofline pass, which only --full runs")
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
+    if not args.full:   # a plain run: the headline alone (the options below only select among the --full extras)
+        args.measure_traffic, args.roofline_steps, args.in_flight, args.alt_precision = 0, 0, 1, "none"
+        args.alt_injected, args.alt_detect, args.alt_config5, args.cpu_images = 0, 0, 0, 0
 
     # `python bench.py --gpus N`, N > 1, not under torchrun: become the launcher (before anything here touches the GPU)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(self_launch(args, sys.argv[1:]))
 
     # the counter passes are child processes: started before this process initialises the GPU
-    measured, measured_reason = None, "--measure-traffic 0"
+    measured, measured_reason = None, "--measure-traffic 0" if args.full else "not measured without --full"
     if args.measure_traffic and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and args.roofline_steps > 0:
         measured, measured_reason = measure_traffic_in_run(args, args.height or args.size, args.width or args.size)
         if measured is None:
@@ -568,10 +589,13 @@ def main():
             captured = step()
         runner = lambda: (graph.replay(), captured)[1]
 
+    t_setup = time.perf_counter()
     for _ in range(args.warmup):
         out = runner()
-    # Three timed repetitions of EXACTLY --steps steps, each bracketed by a barrier + synchronize on both sides and reduced
-    # with MAX over ranks; `value` is the MEDIAN repetition (run-to-run spread of one repetition on this pool: ~4 %), the
+    torch.cuda.synchronize()
+    t_warm = time.perf_counter()
+    # --reps timed repetitions (one in a plain run, three with --full) of EXACTLY --steps steps, each bracketed by a barrier +
+    # synchronize on both sides and reduced with MAX over ranks; `value` is the MEDIAN repetition (run-to-run spread of one repetition on this pool: ~4 %), the
     # fastest and slowest are reported beside it.
     reps, own_max, own_min = [], [], []
     for _ in range(max(1, args.reps)):
@@ -587,11 +611,15 @@ def main():
         own_max.append(mdist.max_over_ranks(own, dev))
         own_min.append(-mdist.max_over_ranks(-own, dev))   # a straggler shows as max >> min the first time SCALE runs
     elapsed = sorted(reps)[len(reps) // 2]
+    log(f"[bench] process start to end of set-up {t_setup - T_START:.1f} s, warm-up {t_warm - t_setup:.2f} s, "
+        f"timed {sum(reps):.2f} s")
     (gathered, gcounts), det = out
     n_images = world * args.batch * args.steps
     value = n_images / elapsed
 
-    mean_valid = round(float(net_last_counts(net, images, windows)), 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    mean_valid = round(float(net_last_counts(net, images, windows)), 1) if args.full else None
     # ---- context, never `value`: the same K steps with TWO batches in flight (consecutive steps on alternating HIP streams, as a
     # serving loop would double-buffer them). The tail of a step (top-k, NMS, the small pyramid levels) fills few CUs; a second
     # step's trunk runs beside it. Same timing discipline; single GPU only (the per-step all-gather stays on one stream).
@@ -924,6 +952,40 @@ def config5_entry(dev, args, ops, modules, InferenceConfig, MaskRCNNInference):
                                         "runs 1.3x faster: tools/f16_dvfs_probe.py, DESIGN.md 5.2a), so the nominal 2.5 PFLOP/s is not "
                                         "reachable on real activations",
             "mean_detections": round(float(det.counts.float().mean().item()), 1)}
+
+
+DUMP_MASK_SAMPLE = 1 << 21   # elements of the full mask tensor written by --dump-outputs (8 MB of float32)
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: what the last timed step returned, as float32 / float64 .npy files under `out_dir` (27 MB at the defaults).
+    `out` = ((gathered [N*B, D, 6], gathered counts [N*B]), Detections of this rank). The full mask tensor [B, D, 28, 28, classes]
+    (203 MB at the defaults) is written as a fixed sample of DUMP_MASK_SAMPLE elements (seed 0, sorted flat indices, listed in
+    masks_sample_index) and, whole, as the mask of each slot's own class (`detection_masks` [B, D, 28, 28]: what a caller
+    keeps). Integer outputs are exact in float32 (class ids < 2^24, counts <= D)."""
+    import numpy as np
+    (gathered, gcounts), det = out
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"class_ids": det.class_ids, "scores": det.scores, "boxes": det.boxes, "counts": det.counts,
+              "gathered_detections": gathered, "gathered_counts": gcounts}
+    if det.masks is not None:
+        m = det.masks
+        b, d, mh, mw, ncls = m.shape
+        cls = det.class_ids.long().clamp(0, ncls - 1).view(b, d, 1, 1, 1).expand(b, d, mh, mw, 1)
+        arrays["detection_masks"] = torch.gather(m, 4, cls).squeeze(4)
+        n = m.numel()
+        if n > DUMP_MASK_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(n, generator=g)[:DUMP_MASK_SAMPLE].sort()[0]
+            arrays["masks_sample"] = m.reshape(-1)[idx.to(m.device)]
+            arrays["masks_sample_index"] = idx.double()
+        else:
+            arrays["masks"] = m
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
 
 
 def net_last_counts(net, images, windows):

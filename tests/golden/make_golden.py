@@ -10,7 +10,7 @@ Sources of truth used here (nothing of theirs is copied into the repo — only i
     c++ext/maskrcnn/__init__.py:21-45 does (that file's legacy autograd.Function cannot run on
     torch >= 1.5).
 
-Usage:  python tests/golden/make_golden.py [nms crop roi_align roi_levels anchors graph refine schema image config1]
+Usage:  python tests/golden/make_golden.py [nms nms_sweep crop roi_align roi_levels anchors graph refine schema image config1]
         (no argument: rewrite every fixture; deterministic)
 """
 import contextlib
@@ -97,9 +97,32 @@ def load_reference():
 
 
 def save(name, **arrays):
+    """An .npz whose members are LZMA-compressed (np.load reads them as any other); a large array that repeats an earlier
+    one bit for bit is stored once and named in `__alias__` (tests/conftest.py:load_golden resolves it). Every fixture
+    stays under 1 MiB."""
+    import io
+    import zipfile
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print(f"{name}.npz  {os.path.getsize(path) / 1024:.1f} KiB")
+    seen, alias, stored = {}, [], {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        key = (v.dtype.str, v.shape, hashlib.sha256(v.tobytes()).hexdigest())
+        if v.nbytes >= 1024 and key in seen:
+            alias.append((k, seen[key]))
+            continue
+        seen.setdefault(key, k)
+        stored[k] = v
+    if alias:
+        stored["__alias__"] = np.array(alias)
+        stored["__order__"] = np.array(list(arrays))
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as zf:
+        for k, v in stored.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, v, allow_pickle=False)
+            zf.writestr(k + ".npy", buf.getvalue())
+    size = os.path.getsize(path)
+    print(f"{name}.npz  {size / 1024:.1f} KiB")
+    assert size < 1 << 20, f"{name}.npz is {size} bytes: over the 1 MiB limit of a committed file"
 
 
 def rand_dets(g, n, extent=1024.0, cluster=True, integral=False):
@@ -164,6 +187,22 @@ def gen_nms(refc):
     wide[:, 1:6] = d
     view = wide[:, 1:6]
     save("nms_strided", wide=wide.numpy(), keep=refc.nms(view, 0.6).numpy(), thr=np.float32(0.6))
+
+
+def gen_nms_sweep(refc):
+    """The sweep of tests/test_oracle.py::test_nms_vs_compiled_reference (seed 11; the test regenerates the inputs and
+    checks them against the stored ones): the reference's keep indices for fp32 and fp64 boxes at three thresholds."""
+    g = torch.Generator().manual_seed(11)
+    out = {}
+    for n in (7, 100, 777):
+        c = torch.rand(n, 2, generator=g) * 300
+        hw = torch.rand(n, 2, generator=g) * 120 + 1
+        d = torch.cat([c, c + hw, torch.randperm(n, generator=g)[:, None].float() / n], 1)
+        out[f"n{n}_dets"] = d.numpy()
+        for thr in (0.1, 0.5, 0.9):
+            out[f"n{n}_t{thr}_f32_keep"] = refc.nms(d, thr).numpy()
+            out[f"n{n}_t{thr}_f64_keep"] = refc.nms(d.double(), thr).numpy()
+    save("nms_sweep", **out)
 
 
 def rand_boxes(g, n, lo=0.02, hi=0.6, spill=0.0):
@@ -560,14 +599,19 @@ def gen_image(rconfig, rutils, rmodel, rdata):
 def gen_config1(rconfig, rutils, rmodel):
     """BASELINE configs[0]: `predict.py images/car58a54312d.jpg` — the geometry detect() sees for the reference's own
     sample image (predict.py:55-60 → model.detect, model.py:1095-1110): 1200 x 1920 RGB → scale 1024/1920 → 640 x 1024
-    → zero-padded to 1024 x 1024 with window (192, 0, 832, 1024). The image file is one of the reference's data files;
-    its decoded pixels are stored as the input vector. Outputs: the resized uint8 image (Pillow BILINEAR — what
-    scipy.misc.imresize did, utils.py:73), and from the reference's own resize_image / mold_image on it: window,
-    padding, and the molded fp32 [3,1024,1024] tensor as a sha256 plus a 16-pixel-stride sample (the full tensor is
-    12.6 MB)."""
+    → zero-padded to 1024 x 1024 with window (192, 0, 832, 1024). The image file is one of the reference's data files:
+    it is stored as tests/golden/car58a54312d.jpg (its decoded pixels, 6.9 MB, are pinned by their sha256). Outputs: the
+    resized uint8 image (Pillow BILINEAR — what scipy.misc.imresize did, utils.py:73) as a sha256 plus an 8-pixel-stride
+    sample, and from the reference's own resize_image / mold_image on it: window, padding, and the molded fp32
+    [3,1024,1024] tensor as a sha256 plus a 16-pixel-stride sample (the full tensor is 12.6 MB)."""
+    import shutil
+
     from PIL import Image
     cfg = rconfig.CocoInferenceConfig()
-    a = np.array(Image.open(os.path.join(REF, "images", "car58a54312d.jpg")).convert("RGB"))
+    jpg = os.path.join(HERE, "car58a54312d.jpg")
+    shutil.copyfile(os.path.join(REF, "images", "car58a54312d.jpg"), jpg)
+    with Image.open(jpg) as im:
+        a = np.array(im.convert("RGB"))
     h, w = a.shape[:2]
     scale = max(1, cfg.IMAGE_MIN_DIM / min(h, w))                            # utils.py:62-69, evaluated here
     if round(max(h, w) * scale) > cfg.IMAGE_MAX_DIM:
@@ -577,7 +621,10 @@ def gen_config1(rconfig, rutils, rmodel):
     assert s1 == 1
     molded = rmodel.mold_image(padded, cfg)                                   # model.py:1750-1754 (float64 mean)
     molded = torch.from_numpy(molded.transpose(2, 0, 1)).float().contiguous()  # model.py:1108
-    save("config1", image=a, resized=resized, window=np.array(window, dtype=np.int64),
+    sha = lambda x: np.array(hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest())
+    save("config1", image_shape=np.array(a.shape, dtype=np.int64), image_sha256=sha(a),
+         resized_shape=np.array(resized.shape, dtype=np.int64), resized_sha256=sha(resized),
+         resized_sample=resized[::8, ::8].copy(), window=np.array(window, dtype=np.int64),
          scale=np.array(scale, dtype=np.float64), padding=np.array(padding, dtype=np.int64),
          mean_pixel=np.asarray(cfg.MEAN_PIXEL, dtype=np.float64),
          min_dim=np.int64(cfg.IMAGE_MIN_DIM), max_dim=np.int64(cfg.IMAGE_MAX_DIM),
@@ -592,6 +639,8 @@ def main():
     refc, rconfig, rutils, rdata, rmodel = load_reference()
     if want("nms"):
         gen_nms(refc)
+    if want("nms_sweep"):
+        gen_nms_sweep(refc)
     if want("crop"):
         gen_crop(refc)
     if want("roi_align"):

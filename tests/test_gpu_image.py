@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from conftest import golden_jpeg, load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -302,9 +302,9 @@ def test_detect_batches_images_of_one_size(ops):
 
 
 def test_config1_car_image_mold_and_detect(ops, oracle):
-    """BASELINE configs[0] — `predict.py images/car58a54312d.jpg`: the reference's sample image (decoded pixels in the
-    fixture) through detect(): 1200 x 1920 → 640 x 1024 → 1024^2 canvas, window (192, 0, 832, 1024) (utils.py:42-90,
-    predict.py:55-60). The molded tensor is bit-identical to the golden one (sha256 of the reference's own mold_image
+    """BASELINE configs[0] — `predict.py images/car58a54312d.jpg`: the reference's sample image (the JPEG is a fixture,
+    its decoded pixels pinned by sha256) through detect(): 1200 x 1920 → 640 x 1024 → 1024^2 canvas, window (192, 0, 832,
+    1024) (utils.py:42-90, predict.py:55-60). The molded tensor is bit-identical to the golden one (sha256 of the reference's own mold_image
     output); detect() on it (synthetic weights: no checkpoint offline) returns boxes and masks in the ORIGINAL image's
     frame, equal to the oracle's full_masks / decode_masks / decode_boxes composed on the pipeline's detections."""
     import hashlib
@@ -314,7 +314,8 @@ def test_config1_car_image_mold_and_detect(ops, oracle):
     from maskrcnn_amd.config import InferenceConfig
     from maskrcnn_amd.pipeline import MaskRCNNInference
     z = load_golden("config1")
-    a = z["image"]
+    a = golden_jpeg("car58a54312d")
+    assert hashlib.sha256(a.tobytes()).hexdigest() == str(z["image_sha256"])
     cfg = InferenceConfig(image_height=1024, image_width=1024, backbone="resnet50", pre_nms_limit=500, proposal_count=500,
                           image_min_dim=int(z["min_dim"]), image_max_dim=int(z["max_dim"]),
                           mean_pixel=tuple(z["mean_pixel"].tolist()))
@@ -325,7 +326,9 @@ def test_config1_car_image_mold_and_detect(ops, oracle):
     assert hashlib.sha256(m.numpy().tobytes()).hexdigest() == str(z["molded_sha256"])
     assert np.array_equal(m.numpy()[:, ::16, ::16], z["molded_sample"])
     resized = imagelib.resize_image(a, cfg.image_min_dim, cfg.image_max_dim, padding=False, device=DEV)[0]
-    assert np.array_equal(resized.cpu().numpy(), z["resized"])
+    resized = resized.cpu().numpy()
+    assert resized.shape == tuple(z["resized_shape"].tolist()) and np.array_equal(resized[::8, ::8], z["resized_sample"])
+    assert hashlib.sha256(np.ascontiguousarray(resized).tobytes()).hexdigest() == str(z["resized_sha256"])
 
     sd = modules.synthetic_state_dict("resnet50", seed=0, bn_seed=1)
     g = torch.Generator().manual_seed(5)

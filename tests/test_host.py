@@ -293,6 +293,36 @@ def test_bench_self_launch_builds_the_torchrun_child_command():
     assert r.returncode != 0 and "WORLD_SIZE=1 but --gpus 8" in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_last_step_as_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array the step returns lands as DIR/<name>.npy in float32 / float64, integers exactly; the
+    mask tensor beyond the size cap as a fixed sample (same indices every run) plus each slot's own-class mask, whole."""
+    import types
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MASK_SAMPLE", 50)
+    g = torch.Generator().manual_seed(0)
+    b, d, ncls = 2, 3, 5
+    det = types.SimpleNamespace(class_ids=torch.randint(0, ncls, (b, d), generator=g), scores=torch.rand(b, d, generator=g),
+                                boxes=torch.rand(b, d, 4, generator=g) * 100, counts=torch.tensor([3, 1], dtype=torch.int32),
+                                masks=torch.rand(b, d, 4, 4, ncls, generator=g))
+    gathered = torch.rand(b, d, 6, generator=g)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), ((gathered, det.counts.clone()), det))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"class_ids", "scores", "boxes", "counts", "gathered_detections", "gathered_counts", "detection_masks",
+                        "masks_sample", "masks_sample_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["class_ids"], det.class_ids.numpy()) and np.array_equal(got["counts"], [3, 1])
+    assert np.array_equal(got["gathered_detections"], gathered.numpy())
+    idx = got["masks_sample_index"].astype(np.int64)
+    assert len(idx) == 50 and (np.diff(idx) > 0).all()
+    assert np.array_equal(got["masks_sample"], det.masks.reshape(-1).numpy()[idx])
+    want = np.take_along_axis(det.masks.numpy(), det.class_ids.numpy()[:, :, None, None, None], 4)[..., 0]
+    assert np.array_equal(got["detection_masks"], want)
+    for name, a in got.items():   # the same arrays, the same sample, run after run
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+
+
 def test_bench_roofline_reports_co_dominant_families_together():
     """When the two largest kernel families are within 5 % of each other's summed time (direct implicit GEMM vs F(4x4) in the
     headline step), roofline.frac is the fraction of BOTH together and each is listed — the line cannot quote the better half."""

@@ -54,15 +54,24 @@ def test_nms_class_aware_equals_per_class_loop(oracle):
     assert torch.equal(got, want)
 
 
-def test_nms_vs_compiled_reference(oracle, ref_ext):
+def test_nms_vs_compiled_reference(oracle):
+    """Against the keep indices the reference's compiled CPU extension returned for this sweep (tests/golden/nms_sweep.npz,
+    make_golden.py nms_sweep), and against oracle/_ref itself where it is built."""
+    from oracle import build_ref
+    live = build_ref.load()
+    z = load_golden("nms_sweep")
     g = torch.Generator().manual_seed(11)
     for n in (7, 100, 777):
         c = torch.rand(n, 2, generator=g) * 300
         hw = torch.rand(n, 2, generator=g) * 120 + 1
         d = torch.cat([c, c + hw, torch.randperm(n, generator=g)[:, None].float() / n], 1)
+        assert np.array_equal(d.numpy(), z[f"n{n}_dets"])
         for thr in (0.1, 0.5, 0.9):
-            assert torch.equal(oracle.nms(d, thr), ref_ext.nms(d, thr))
-            assert torch.equal(oracle.nms(d.double(), thr), ref_ext.nms(d.double(), thr))
+            for x, tag in ((d, "f32"), (d.double(), "f64")):
+                got = oracle.nms(x, thr)
+                assert np.array_equal(got.numpy(), z[f"n{n}_t{thr}_{tag}_keep"]), (n, thr, tag)
+                if live is not None:
+                    assert torch.equal(got, live.nms(x, thr))
 
 
 def test_crop_forward_golden(oracle):

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden
+from conftest import golden_jpeg, load_golden
 
 
 @pytest.fixture(scope="module")
@@ -98,12 +98,16 @@ def test_config1_car_image_geometry(oracle):
 
     from maskrcnn_amd import image as imagelib
     z = load_golden("config1")
-    a = z["image"]
-    assert a.shape == (1200, 1920, 3)
+    a = golden_jpeg("car58a54312d")
+    assert a.shape == (1200, 1920, 3) == tuple(z["image_shape"].tolist())
+    assert hashlib.sha256(a.tobytes()).hexdigest() == str(z["image_sha256"])
     img, window, scale, padding = oracle.resize_image(a, int(z["min_dim"]), int(z["max_dim"]), True)
     assert tuple(window) == tuple(z["window"].tolist()) == (192, 0, 832, 1024)
     assert float(scale) == float(z["scale"]) and np.array_equal(np.array(padding), z["padding"])
-    assert np.array_equal(img[192:832], z["resized"]) and not img[:192].any() and not img[832:].any()
+    resized = np.ascontiguousarray(img[192:832])
+    assert resized.shape == tuple(z["resized_shape"].tolist()) and np.array_equal(resized[::8, ::8], z["resized_sample"])
+    assert hashlib.sha256(resized.tobytes()).hexdigest() == str(z["resized_sha256"])
+    assert not img[:192].any() and not img[832:].any()
     molded = oracle.mold_image(img, z["mean_pixel"])[0].contiguous()
     assert hashlib.sha256(molded.numpy().tobytes()).hexdigest() == str(z["molded_sha256"])
     assert np.array_equal(molded.numpy()[:, ::16, ::16], z["molded_sample"])

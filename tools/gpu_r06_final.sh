@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ "$1" = a ]; then
   bash tools/gpu_round.sh r06z tests bench stats pmc || exit $?
   OUT=gpurun_out/r06z
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --cpu-images 0 --alt-precision none --alt-config5 0 --roofline-steps 0 > $OUT/bench_torchrun_n1.json 2> $OUT/bench_torchrun_n1.err
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --cpu-images 0 --alt-precision none --alt-config5 0 --roofline-steps 0 > $OUT/bench_torchrun_n1.json 2> $OUT/bench_torchrun_n1.err
   python3 -c "
 import json
 for f in ('bench_n1','bench_torchrun_n1'):

@@ -25,11 +25,11 @@ if [[ "$WHAT" == *" tests "* ]]; then
     tail -15 $OUT/tests.log
 fi
 if [[ "$WHAT" == *" bench "* ]]; then
-    step bench 400 python bench.py --dump-conv $OUT/conv_layers.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+    step bench 400 python bench.py --full --dump-conv $OUT/conv_layers.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err
     tail -c 600 $OUT/bench_n1.json
 fi
 if [[ "$WHAT" == *" stats "* ]]; then
-    step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --cpu-images 0 --alt-precision none --in-flight 1 > $OUT/kt.json 2> $OUT/kt.err
+    step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --cpu-images 0 --alt-precision none --in-flight 1 > $OUT/kt.json 2> $OUT/kt.err
     find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
     find $OUT/kt -name "*_kernel_trace.csv" -delete   # large; the stats summary is what is kept
 fi

@@ -9,8 +9,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 C5="--arch resnet101 --height 832 --width 1344 --precision f16 --cpu-images 0 --alt-precision none --alt-config5 0"
 step() { local name=$1 limit=$2; shift 2; echo "== $name" >&2; timeout -k 10 $limit "$@"; local rc=$?; echo "== $name rc=$rc" >&2
          if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "== $name was killed: stopping"; exit $rc; fi; return $rc; }
-step bench 300 python bench.py $C5 --dump-conv $OUT/config5_f16_conv_layers.json > $OUT/config5_f16.json 2> $OUT/config5_f16.err
-step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py $C5 --reps 1 > $OUT/kt.json 2> $OUT/kt.err
+step bench 300 python bench.py --full $C5 --dump-conv $OUT/config5_f16_conv_layers.json > $OUT/config5_f16.json 2> $OUT/config5_f16.err
+step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full $C5 --reps 1 > $OUT/kt.json 2> $OUT/kt.err
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/config5_f16_kernel_stats.csv \;
 find $OUT/kt -name "*_kernel_trace.csv" -delete
 mkdir -p $OUT/pmc_mfma
