@@ -364,7 +364,7 @@ int mrcnn_conv3x3_winograd_f32(const float* x, int32_t x_layout, int32_t batch, 
  *   mrcnn_winograd4_weights_f32   w_ohwi [Cout][3][3][Cin] -> u = G g G^T in the kernel's order [Cin/4][36][2][Cout][2]
  *                                 (36 * Cout * Cin floats; evaluated in double); Cin % 4 == 0
  *   mrcnn_conv3x3_winograd4_supported   1 when H % 4 == 0, W % 4 == 0, Cin % 8 == 0, Cout % 64 == 0 and the tensors stay
- *                                 inside the kernel's 32-bit byte offsets (B*H*W*Cin, B*H*W*Cout < 2^30 elements)
+ *                                 inside the kernel's 32-bit byte offsets (4*B*H*W*Cin, 4*B*H*W*Cout <= 0xFFFFFFF0 bytes)
  *   mrcnn_conv3x3_winograd4_f32   x k-blocked [Cin/8][B*H*W][8] -> relu?(conv * scale + shift) as NHWC and/or k-blocked
  *                                 [Cout/8][B*H*W][8] (either output pointer may be null, not both) */
 int mrcnn_winograd4_weights_f32(const float* w_ohwi, int32_t cout, int32_t cin, float* u, mrcnn_stream_t stream);

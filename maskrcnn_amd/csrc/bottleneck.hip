@@ -491,7 +491,7 @@ extern "C" int mrcnn_bottleneck_fused_f32(const float* x, int32_t batch, int32_t
                   batch, height, width, cin, planes);
     MRCNN_REQUIRE(x != y, "bottleneck_fused: in-place operation is not supported (halo reads)");
     const long long px = 1LL * batch * height * width;
-    MRCNN_REQUIRE(px * CO < (1LL << 30), "bottleneck_fused: tensor too large (32-bit buffer byte offsets)");
+    MRCNN_REQUIRE(4 * px * CO <= MAX_BUFFER_BYTES, "bottleneck_fused: tensor too large (32-bit buffer byte offsets)");
     BottleneckParams p;
     p.x = x; p.w1 = w1; p.s1 = scale1; p.t1 = shift1; p.u2 = u2; p.s2 = scale2; p.t2 = shift2;
     p.w3 = w3; p.s3 = scale3; p.t3 = shift3; p.y = y;

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -54,7 +55,7 @@ constexpr int L_TAB = L_T1 + T1_BYTES;
 constexpr int TAB_S1 = 0, TAB_T1 = 256, TAB_S2 = 512, TAB_T2 = 768, TAB_S3 = 1024, TAB_T3 = 2048, TAB_SD = 3072, TAB_TD = 4096;
 constexpr int LDS_BYTES = L_TAB + 5120;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-constexpr unsigned OOB = 0xFFFFFFF0u;
+using mrcnn_conv::OOB;
 constexpr int BAND = 4;   // tile rows per band of the tile order
 // timing-only ablations (MRCNN_BF16_ABL=<mask> python maskrcnn_amd/build.py; tools/c2_f16_ablate.sh): 1 no x loads after the first
 // tile, 2 no stores, 4 no conv2 MFMAs / fragment reads, 8 no conv3 (+ downsample) MFMAs, 16 no conv1 MFMAs. Results are wrong.
@@ -416,7 +417,9 @@ extern "C" int mrcnn_bottleneck_c2_f16_supported(int32_t batch, int32_t height, 
     if (batch < 1 || height < 1 || width < 1 || planes != 64) return 0;
     if (cin != (has_downsample ? 64 : 256)) return 0;
     const long long px = static_cast<long long>(batch) * height * width;
-    if (px * 256 * 2 >= (1LL << 31)) return 0;   // 32-bit byte offsets into y (and x)
+    // 32-bit byte offsets into y (and x); below mrcnn_conv::MAX_BUFFER_BYTES, and fp16 element offsets stay below 2^30
+    static_assert((1LL << 31) <= mrcnn_conv::MAX_BUFFER_BYTES, "buffer byte limit");
+    if (px * 256 * 2 >= (1LL << 31)) return 0;
     const long long tiles = static_cast<long long>(batch) * ((height + TH - 1) / TH) * ((width + TW - 1) / TW);
     return tiles < (1LL << 28) ? 1 : 0;
 }

@@ -729,7 +729,8 @@ extern "C" int mrcnn_rpn_level_fused_f32(const float* x, int32_t batch, int32_t 
                   "rpn_level: workspace too small");
     const long long M = 1LL * batch * height * width;
     const int tiles_n = cout / 128;
-    MRCNN_REQUIRE(M * cin < (1LL << 30) && 9LL * cin * cout < (1LL << 30) && M * head_n * tiles_n < (1LL << 30),
+    MRCNN_REQUIRE(4 * M * cin <= MAX_BUFFER_BYTES && 36LL * cin * cout <= MAX_BUFFER_BYTES &&
+                      4 * M * head_n * tiles_n <= MAX_BUFFER_BYTES,
                   "rpn_level: tensor too large for 32-bit buffer offsets");
     ConvParams p;
     p.x = x; p.w = w_shared; p.scale = nullptr; p.shift = b_shared; p.residual = nullptr;

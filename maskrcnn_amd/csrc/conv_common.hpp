@@ -9,6 +9,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr unsigned OOB = 0xFFFFFFF0u;  // byte offset beyond every buffer descriptor's num_records
+// The largest byte size of a tensor addressed through one buffer descriptor. A descriptor's num_records must not pass OOB, or a
+// store dropped by sending it to OOB lands inside the tensor (an fp32 tensor of 2^30 - 2 elements has num_records 0xFFFFFFF8, and
+// OOB is its element 2^30 - 4), and oob_add clamps a real offset at or past OOB onto OOB. Every 32-bit-offset size check is
+// stated against this constant; it also keeps fp32 element offsets below 2^30.
+constexpr long long MAX_BUFFER_BYTES = OOB;
 
 // row offset + column offset where either may be OOB: a saturating add (one v_add_u32 ... clamp) keeps the sum out of range
 // — the or / compare / add / select it replaces are VALU instructions of an epilogue that runs beside the other workgroup's
@@ -421,10 +426,10 @@ inline int fill_common(ConvCommon& p, const char* who, const float* x, int batch
         return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: res_div=2 needs even output size", who);
     const long long M = 1LL * batch * p.OH * p.OW;
     const long long K = 1LL * kh * kw * cin;
-    if (!(1LL * batch * height * width * cin < (1LL << 30) && M * cout < (1LL << 30) && K * cout < (1LL << 30) &&
-          M < (1LL << 31)))
+    if (!(4LL * batch * height * width * cin <= MAX_BUFFER_BYTES && 4LL * M * cout <= MAX_BUFFER_BYTES &&
+          4LL * K * cout <= MAX_BUFFER_BYTES && M < (1LL << 31)))
         return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT,
-                           "%s: tensor too large (each tensor < 2^30 elements: 32-bit buffer byte offsets)", who);
+                           "%s: tensor too large (each tensor <= 0xFFFFFFF0 bytes: 32-bit buffer byte offsets)", who);
     p.M = static_cast<int>(M);
     p.K = static_cast<int>(K);
     {

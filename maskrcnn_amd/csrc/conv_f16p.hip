@@ -31,6 +31,7 @@
 //   * Small tiles (TMW * NWT <= 8: 64 KB of LDS, <= 128 registers) run two workgroups per CU: the short-K expansion layers live
 //     in their prologue and epilogue, and a second workgroup is what covers them.
 #include "common.hpp"
+#include "conv_common.hpp"
 
 // every workgroup barrier of this file (schedule-fuzz builds sleep a pseudo-random time behind each: common.hpp)
 #define P8_BARRIER() do { __builtin_amdgcn_s_barrier(); MRCNN_SYNC_FUZZ_POINT(); } while (0)
@@ -45,7 +46,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
+using mrcnn_conv::OOB;
 constexpr int P8_MAX_TAPS = 25;
 
 struct P8Params {
@@ -505,7 +506,8 @@ extern "C" int mrcnn_conv_f16_pipelined_supported(int32_t batch, int32_t height,
     if (height + pad_top + pad_bottom < kh || width + pad_left + pad_right < kw) return 0;
     const long long oh = (height + pad_top + pad_bottom - kh) / stride + 1, ow = (width + pad_left + pad_right - kw) / stride + 1;
     const long long m = static_cast<long long>(batch) * oh * ow;
-    const long long lim = 1LL << 31;  // byte offsets are 32-bit, fp32 output included
+    const long long lim = 1LL << 31;  // byte offsets are 32-bit, fp32 output included (fp16 element offsets < 2^30)
+    static_assert((1LL << 31) <= mrcnn_conv::MAX_BUFFER_BYTES, "buffer byte limit");
     if (m * cout * 4 >= lim || static_cast<long long>(batch) * height * width * cin * 2 >= lim) return 0;
     if (static_cast<long long>(cout) * kh * kw * cin * 2 >= lim) return 0;
     return 1;

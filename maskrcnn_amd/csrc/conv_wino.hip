@@ -1090,7 +1090,7 @@ extern "C" int mrcnn_winograd_set_spatial(int32_t on) {
 
 extern "C" int mrcnn_winograd_weights_f32(const float* w, int32_t cout, int32_t cin, float* u, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(w && u, "winograd_weights: null pointer");
-    MRCNN_REQUIRE(cout >= 1 && cin >= 1 && 16LL * cout * cin < (1LL << 30), "winograd_weights: cout=%d cin=%d", cout, cin);
+    MRCNN_REQUIRE(cout >= 1 && cin >= 1 && 64LL * cout * cin <= MAX_BUFFER_BYTES, "winograd_weights: cout=%d cin=%d", cout, cin);
     const int64_t n = static_cast<int64_t>(cout) * cin;
     hipLaunchKernelGGL(wino_weights_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
                        mrcnn::as_stream(stream), w, cout, cin, u);
@@ -1118,7 +1118,8 @@ extern "C" int mrcnn_conv3x3_winograd_f32(const float* x, int32_t x_layout, int3
     MRCNN_REQUIRE(y_kblocked == nullptr || cout % 8 == 0, "conv3x3_winograd: a k-blocked output needs Cout %% 8 == 0");
     MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd: activation must be 0 or 1");
     const long long px = 1LL * batch * height * width;
-    MRCNN_REQUIRE(px * cin < (1LL << 30) && px * cout < (1LL << 30) && 16LL * cin * cout < (1LL << 30),
+    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES &&
+                      64LL * cin * cout <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd: tensor too large (32-bit buffer byte offsets)");
     hipStream_t st = mrcnn::as_stream(stream);
     const float* x8 = x;
@@ -1218,7 +1219,8 @@ extern "C" int mrcnn_conv3x3_winograd_heads_f32(const float* x_kblocked, int32_t
 #endif
     const long long px = 1LL * batch * height * width;
     const long long rows = mrcnn_conv3x3_winograd_heads_rows(batch, height, width, tile_mode);
-    MRCNN_REQUIRE(px * cin < (1LL << 30) && 16LL * cin * cout < (1LL << 30) && 2 * rows * 32 < (1LL << 30),
+    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 64LL * cin * cout <= MAX_BUFFER_BYTES &&
+                      8 * rows * 32 <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd_heads: tensor too large (32-bit buffer byte offsets)");
     WinoSParams p;
     p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;

@@ -867,7 +867,8 @@ extern "C" int mrcnn_winograd4_weights_f32(const float* w_ohwi, int32_t cout, in
     return mrcnn::check_launch("wino4_weights_kernel");
 }
 
-// shapes the kernel takes, the 32-bit byte-offset limits included (B*H*W*Cin, B*H*W*Cout < 2^30 elements): a caller that
+// shapes the kernel takes, the 32-bit byte-offset limits included (fp32 tensors B*H*W*Cin, B*H*W*Cout of at most
+// MAX_BUFFER_BYTES): a caller that
 // asks first can fall back to the F(2x2) or the direct kernel instead of being refused by the launch
 extern "C" int32_t mrcnn_conv3x3_winograd4_supported(int32_t batch, int32_t height, int32_t width, int32_t cin,
                                                      int32_t cout) {
@@ -875,7 +876,7 @@ extern "C" int32_t mrcnn_conv3x3_winograd4_supported(int32_t batch, int32_t heig
           cout >= W4_N && cout % W4_N == 0))
         return 0;
     const long long px = 1LL * batch * height * width;
-    return px * cin < (1LL << 30) && px * cout < (1LL << 30) && 36LL * cin * cout < (1LL << 30);
+    return 4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES && 144LL * cin * cout <= MAX_BUFFER_BYTES;
 }
 
 extern "C" int mrcnn_conv3x3_winograd4_f32(const float* x_kblocked, int32_t batch, int32_t height, int32_t width,
@@ -884,11 +885,12 @@ extern "C" int mrcnn_conv3x3_winograd4_f32(const float* x_kblocked, int32_t batc
                                            mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && (y_nhwc || y_kblocked), "conv3x3_winograd4: null pointer");
     MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, cout),
-                  "conv3x3_winograd4: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), B*H*W*C < 2^30 required",
+                  "conv3x3_winograd4: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required",
                   batch, height, width, cin, cout);
     MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd4: activation must be 0 or 1");
     const long long px = 1LL * batch * height * width;
-    MRCNN_REQUIRE(px * cin < (1LL << 30) && px * cout < (1LL << 30) && 36LL * cin * cout < (1LL << 30),
+    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES &&
+                      144LL * cin * cout <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd4: tensor too large (32-bit buffer byte offsets)");
     Wino4Params p;
     p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = y_nhwc; p.yk = y_kblocked;
@@ -950,12 +952,13 @@ extern "C" int mrcnn_conv3x3_winograd4_heads_f32(const float* x_kblocked, int32_
                                                  float* head_part, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && w_head32 && head_part, "conv3x3_winograd4_heads: null pointer");
     MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, cout),
-                  "conv3x3_winograd4_heads: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), B*H*W*C < 2^30 "
+                  "conv3x3_winograd4_heads: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes "
                   "required", batch, height, width, cin, cout);
     MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd4_heads: activation must be 0 or 1");
     const long long px = 1LL * batch * height * width;
     const long long rows = mrcnn_conv3x3_winograd4_heads_rows(batch, height, width);
-    MRCNN_REQUIRE(px * cin < (1LL << 30) && 36LL * cin * cout < (1LL << 30) && rows * 32 < (1LL << 30),
+    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 144LL * cin * cout <= MAX_BUFFER_BYTES &&
+                      4 * rows * 32 <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd4_heads: tensor too large (32-bit buffer byte offsets)");
     Wino4Params p;
     p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;
@@ -1010,12 +1013,12 @@ extern "C" int mrcnn_conv3x3_winograd4_conv3_f32(const float* x_kblocked, int32_
                                                  const float* residual, float* y, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && w3 && residual && y, "conv3x3_winograd4_conv3: null pointer");
     MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, W4_N),
-                  "conv3x3_winograd4_conv3: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0), B*H*W*C < 2^30 required", batch,
+                  "conv3x3_winograd4_conv3: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required", batch,
                   height, width, cin);
     MRCNN_REQUIRE(c3 >= 32 && c3 % 32 == 0 && c3 <= 256, "conv3x3_winograd4_conv3: c3=%d must be a multiple of 32, at most 256", c3);
     MRCNN_REQUIRE(residual != y, "conv3x3_winograd4_conv3: in-place operation is not supported");
     const long long px = 1LL * batch * height * width;
-    MRCNN_REQUIRE(px * c3 < (1LL << 30), "conv3x3_winograd4_conv3: tensor too large (32-bit buffer byte offsets)");
+    MRCNN_REQUIRE(4 * px * c3 <= MAX_BUFFER_BYTES, "conv3x3_winograd4_conv3: tensor too large (32-bit buffer byte offsets)");
     Wino4Params p;
     p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;
     p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = W4_N;

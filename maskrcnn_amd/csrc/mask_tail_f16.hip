@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -36,7 +37,7 @@ constexpr int L_W5 = L_WDE + WDE_BYTES, W5_BYTES = 48 * 1024;   // [kc 8][cb 6] 
 constexpr int L_BDE = L_W5 + W5_BYTES;        // deconv bias [4][256] fp32
 constexpr int L_B5 = L_BDE + 4096;            // conv5 bias [96] fp32 (zero beyond `classes`)
 constexpr int MT_LDS = L_B5 + 512;
-constexpr unsigned OOB = 0xFFFFFFF0u;
+using mrcnn_conv::OOB;
 
 struct MTParams {
     const _Float16* x;     // [M][256], M = rois * h * w
@@ -233,7 +234,7 @@ extern "C" int mrcnn_mask_tail_f16_supported(int32_t rois, int32_t height, int32
                                              int32_t classes) {
     if (rois < 1 || height < 1 || width < 1 || cin != 256 || cout_deconv != 256 || classes < 1 || classes > 96) return 0;
     const long long m = static_cast<long long>(rois) * height * width;
-    if (m * 512 >= (1LL << 31) || m * 4 * classes * 4 >= (1LL << 32) - 65536) return 0;   // 32-bit byte offsets
+    if (m * 512 >= (1LL << 31) || m * 4 * classes * 4 > mrcnn_conv::MAX_BUFFER_BYTES - 65536) return 0;   // 32-bit byte offsets
     return 1;
 }
 

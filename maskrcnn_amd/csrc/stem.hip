@@ -656,7 +656,7 @@ int run_stem(bool nchw, const float* x, int32_t batch, int32_t height, int32_t w
     MRCNN_REQUIRE(batch >= 1 && height >= 2 && width >= 2 && height % 2 == 0 && width % 2 == 0,
                   "stem: B=%d H=%d W=%d (even sizes required)", batch, height, width);
     MRCNN_REQUIRE(activation == 0 || activation == 1, "stem: activation must be 0 or 1");
-    MRCNN_REQUIRE(1LL * batch * height * width * 4 < (1LL << 30) && 1LL * batch * (height / 2) * (width / 2) * 64 < (1LL << 30),
+    MRCNN_REQUIRE(16LL * batch * height * width <= MAX_BUFFER_BYTES && 256LL * batch * (height / 2) * (width / 2) <= MAX_BUFFER_BYTES,
                   "stem: tensor too large (32-bit buffer byte offsets)");
     StemParams p;
     p.x = x; p.w = w; p.scale = scale; p.shift = shift; p.y = y;
@@ -704,7 +704,7 @@ extern "C" int mrcnn_stem_conv7x7_s2_pool_f16(const float* x_nchw, int32_t batch
     // (an odd conv size would give SamePad2d(3, 2) a top / left component — model.py:64-87 — and shift the pooling windows)
     MRCNN_REQUIRE(batch >= 1 && height >= 4 && width >= 4 && height % 4 == 0 && width % 4 == 0,
                   "stem_pool: B=%d H=%d W=%d (multiples of 4 required)", batch, height, width);
-    MRCNN_REQUIRE(1LL * batch * height * width * 3 < (1LL << 30), "stem_pool: tensor too large (32-bit buffer byte offsets)");
+    MRCNN_REQUIRE(12LL * batch * height * width <= MAX_BUFFER_BYTES, "stem_pool: tensor too large (32-bit buffer byte offsets)");
     StemPoolParams p;
     p.x = x_nchw; p.w = w; p.scale = scale; p.shift = shift; p.y = static_cast<_Float16*>(y_f16);
     p.B = batch; p.H = height; p.W = width; p.OH = height / 2; p.OW = width / 2;
@@ -729,7 +729,7 @@ extern "C" int mrcnn_stem_conv7x7_s2_pool_f32(const float* x_nchw, int32_t batch
     MRCNN_REQUIRE(batch >= 1 && height >= 4 && width >= 4 && height % 4 == 0 && width % 4 == 0,
                   "stem_pool_f32: B=%d H=%d W=%d (multiples of 4 required)", batch, height, width);
     // input 12 B and output 16 B per input pixel (64 fp32 channels per 4 x 4 pixels): the output is the larger tensor
-    MRCNN_REQUIRE(1LL * batch * height * width * 3 < (1LL << 30) && 16LL * batch * height * width < (1LL << 31),
+    MRCNN_REQUIRE(12LL * batch * height * width <= MAX_BUFFER_BYTES && 16LL * batch * height * width < (1LL << 31),
                   "stem_pool_f32: tensor too large (32-bit buffer byte offsets: B*H*W < 2^27 pixels)");
     StemPool32Params p;
     p.x = x_nchw; p.w = w; p.scale = scale; p.shift = shift; p.y = y;

@@ -1330,7 +1330,7 @@ def conv3x3_winograd(x: torch.Tensor, u: torch.Tensor, scale, shift, relu: bool 
 # Winograd F(4x4,3x3) 3x3 stride-1 SAME conv (csrc/conv_wino4.hip): maps with H % 4 == W % 4 == 0, Cout % 64 == 0
 # --------------------------------------------------------------------------------------------------
 def conv3x3_winograd4_supported(h: int, w: int, cin: int, cout: int, batch: int = 1) -> bool:
-    """Shapes the F(4x4) kernel takes — its 32-bit offset limits (batch * h * w * channels < 2^30) included."""
+    """Shapes the F(4x4) kernel takes — its 32-bit offset limits (4 * batch * h * w * channels <= 0xFFFFFFF0 bytes) included."""
     return bool(lib.mrcnn_conv3x3_winograd4_supported(int(batch), int(h), int(w), int(cin), int(cout)))
 
 

@@ -40,9 +40,14 @@ class Detections:
         return torch.cat([self.class_ids.float().unsqueeze(-1), self.scores.unsqueeze(-1), self.boxes], -1)
 
 
+# The kernels' largest tensor, in bytes (csrc/conv_common.hpp MAX_BUFFER_BYTES): a buffer descriptor's num_records never passes
+# the out-of-range offset 0xFFFFFFF0 that dropped stores and loads use.
+MAX_BUFFER_BYTES = 0xFFFFFFF0
+
+
 def max_batch_per_launch(cfg: InferenceConfig) -> int:
-    """Largest per-GPU batch one pass of the step takes: EVERY batch-scaled tensor stays under the kernels' 2^30-element limit
-    (32-bit byte offsets), so that no layer's kernel choice depends on the batch and no launch is refused. Per image: the RPN's
+    """Largest per-GPU batch one pass of the step takes: EVERY batch-scaled fp32 tensor stays within MAX_BUFFER_BYTES (32-bit
+    byte offsets), so that no layer's kernel choice depends on the batch and no launch is refused. Per image: the RPN's
     512-channel shared activation on P2, (H/4)(W/4) x 512 = 32 HW elements (the stem's output is 16 HW) — what bounds large
     images: 31 at 1024^2, 29 at 832 x 1344 —, and the RoI heads' tensors, which bound small images with many proposals: the
     pooled crops P x pool^2 x 256, the classifier's P x 1024 activations, the mask head's D x (2 mask_pool)^2 x 256 up-sampled
@@ -54,7 +59,7 @@ def max_batch_per_launch(cfg: InferenceConfig) -> int:
     per_image = max(32 * cfg.image_height * cfg.image_width,
                     p * cfg.pool_size * cfg.pool_size * 256, p * 1024, p * cfg.num_classes * 5,
                     d * up * 256, d * up * cfg.num_classes)
-    return max(1, ((1 << 30) - 1) // per_image)
+    return max(1, (MAX_BUFFER_BYTES // 4) // per_image)
 
 
 class MaskRCNNInference:
@@ -145,7 +150,7 @@ class MaskRCNNInference:
         assert tuple(images.shape[1:]) == (3, c.image_height, c.image_width)
         if b > self.max_batch:
             # Which kernel a layer takes (F(4x4) / F(2x2) / fused conv3) must never depend on the batch — image i of a batch
-            # equals image i alone bit for bit — but the kernels address tensors with 32-bit element offsets (< 2^30 elements),
+            # equals image i alone bit for bit — but the kernels address tensors with 32-bit byte offsets (MAX_BUFFER_BYTES),
             # so past max_batch a layer would fall to another kernel. Oversized batches therefore run as equal sub-batches.
             assert not return_intermediates, f"return_intermediates needs batch <= {self.max_batch} at this image size"
             assert host_counts is None, "host_counts: one launch group per call (batch <= max_batch)"

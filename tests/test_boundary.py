@@ -124,3 +124,76 @@ def test_native_cxx_module_loads_and_registers():
     assert "Tensor(a!) grads_image" in str(torch.ops.maskrcnn_native.crop_backward.default._schema)
     with pytest.raises(RuntimeError, match="Not compiled with CPU support"):
         m.nms(torch.zeros(3, 5), 0.5)
+
+
+OOB = 0xFFFFFFF0  # csrc/conv_common.hpp: the byte offset dropped loads and stores use; no descriptor's num_records may pass it
+
+
+def _largest_accepted(accepts, lo: int, hi: int) -> int:
+    """Largest v in [lo, hi) with accepts(v), for a predicate that holds on a prefix of the range (lo accepted, hi refused)."""
+    assert accepts(lo) and not accepts(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if accepts(mid) else (lo, mid)
+    return lo
+
+
+def test_size_predicates_keep_every_buffer_within_the_oob_sentinel():
+    """The *_supported predicates and max_batch_per_launch are host arithmetic (no HIP call). At the largest shape each one
+    accepts, every buffer it sizes stays at or below OOB (0xFFFFFFF0 bytes), so a store sent to OOB is dropped; the next shape
+    up is refused. Before the shared MAX_BUFFER_BYTES an fp32 tensor of 2^30 - 3 ... 2^30 - 1 elements was accepted."""
+    from maskrcnn_amd import _lib
+    from maskrcnn_amd.config import InferenceConfig
+    from maskrcnn_amd.pipeline import MAX_BUFFER_BYTES, max_batch_per_launch
+    lib = _lib.lib
+    assert MAX_BUFFER_BYTES == OOB
+    # F(4x4): x and y fp32 [B*H*W][C]; the width is the free size (multiples of 4)
+    for cin, cout in ((8, 64), (1024, 960), (24, 192)):
+        ok = lambda q: bool(lib.mrcnn_conv3x3_winograd4_supported(1, 4, 4 * q, cin, cout))
+        q = _largest_accepted(ok, 1, 1 << 28)
+        assert 4 * 16 * q * max(cin, cout) <= OOB < 4 * 16 * (q + 1) * max(cin, cout), (cin, cout, q)
+    # the C2 fp16 bottleneck: x and y fp16 [px][256]
+    for ds, cin in ((0, 256), (1, 64)):
+        ok = lambda px: bool(lib.mrcnn_bottleneck_c2_f16_supported(1, 1, px, cin, 64, ds))
+        px = _largest_accepted(ok, 1, 1 << 30)
+        assert 512 * px <= OOB and 512 * (px + 1) >= 1 << 31, (ds, px)
+    # the fp16 mask tail: x fp16 [m][256], fp32 output [m][4][classes]
+    for classes in (1, 81, 96):
+        ok = lambda r: bool(lib.mrcnn_mask_tail_f16_supported(r, 14, 14, 256, 256, classes))
+        r = _largest_accepted(ok, 1, 1 << 24)
+        for rr, accepted in ((r, True), (r + 1, False)):
+            m = rr * 196
+            assert (512 * m < 1 << 31 and 16 * m * classes <= OOB - 65536) == accepted, (classes, rr)
+            assert not accepted or max(512 * m, 16 * m * classes) <= OOB, (classes, rr)
+    # the pipelined fp16 conv: fp16 x, fp16 weights, fp32 y (the largest)
+    for k, pad, cout in ((1, (0, 0, 0, 0), 64), (3, (1, 1, 1, 1), 256), (3, (0, 0, 1, 1), 128)):
+        ok = lambda wd: bool(lib.mrcnn_conv_f16_pipelined_supported(1, 64, wd, 64, cout, k, k, 1, *pad))
+        wd = _largest_accepted(ok, 8, 1 << 24)
+        for ww, accepted in ((wd, True), (wd + 1, False)):
+            oh, ow = 64 + pad[0] + pad[2] - k + 1, ww + pad[1] + pad[3] - k + 1
+            ybytes, xbytes = 4 * oh * ow * cout, 2 * 64 * ww * 64
+            assert (max(ybytes, xbytes) < 1 << 31) == accepted and (not accepted or max(ybytes, xbytes) <= OOB), (k, cout, ww)
+    # max_batch_per_launch: every batch-scaled fp32 tensor of the step
+    for h, w, p, d in ((1024, 1024, 500, 50), (832, 1344, 1000, 50), (256, 256, 1000, 50), (128, 128, 4096, 4096),
+                       (64, 64, 1000, 100), (64, 64, 1, 1)):
+        cfg = InferenceConfig(image_height=h, image_width=w, pre_nms_limit=p, proposal_count=p, detection_max_instances=d)
+        m = max_batch_per_launch(cfg)
+        nc, up, pool2 = cfg.num_classes, (2 * cfg.mask_pool_size) ** 2, cfg.pool_size ** 2
+        nbytes = lambda b: 4 * max(b * (h // 4) * (w // 4) * 512, b * p * pool2 * 256, b * p * 1024, b * p * nc * 5,
+                                   b * d * up * 256, b * d * up * nc, b * d * (up // 4) * 256)
+        assert nbytes(m) <= OOB < nbytes(m + 1), (h, w, p, d, m)
+
+
+def test_direct_conv_refuses_the_oob_sentinel_window():
+    """Argument validation runs before any HIP call (the pointers are never touched). A 1x1 conv of 466 x 1103 pixels, Cin 32 ->
+    Cout 2089 has M * Cout = 2^30 - 2 elements, an fp32 output of 0xFFFFFFF8 bytes: the offset OOB of the dropped stores of
+    its ragged tiles would lie inside it (element 2^30 - 4 = y[M-1, 2087]). It is refused; the same call with Cout 1905 on
+    4 x 113 x 1247 pixels (exactly OOB bytes) is the largest of its kind accepted (tests/test_gpu_large_tensors.py runs it)."""
+    from maskrcnn_amd import _lib
+    lib = _lib.lib
+    dummy = ctypes.c_void_p(16)
+    for b, h, w, cin, cout in ((1, 466, 1103, 32, 2089), (1, 1, (2 ** 30 - 1) // 3, 4, 3), (4, 113, 1247, 32, 1906),
+                               (1, 2048, 2048, 256, 64)):
+        rc = lib.mrcnn_conv_bn_act_f32(dummy, b, h, w, cin, dummy, cout, 1, 1, 1, 0, 0, 0, 0, None, None, None, 1, 0, 0, dummy,
+                                       0, None)
+        assert rc != 0 and b"too large" in lib.mrcnn_last_error(), (b, h, w, cin, cout)
