@@ -45,21 +45,32 @@ class Detections:
 MAX_BUFFER_BYTES = 0xFFFFFFF0
 
 
-def max_batch_per_launch(cfg: InferenceConfig) -> int:
+def max_batch_per_launch(cfg: InferenceConfig, precision: str = "f32") -> int:
     """Largest per-GPU batch one pass of the step takes: EVERY batch-scaled fp32 tensor stays within MAX_BUFFER_BYTES (32-bit
     byte offsets), so that no layer's kernel choice depends on the batch and no launch is refused. Per image: the RPN's
     512-channel shared activation on P2, (H/4)(W/4) x 512 = 32 HW elements (the stem's output is 16 HW) — what bounds large
-    images: 31 at 1024^2, 29 at 832 x 1344 —, and the RoI heads' tensors, which bound small images with many proposals: the
+    images: 31 at 1024^2, 30 at 832 x 1344 —, and the RoI heads' tensors, which bound small images with many proposals: the
     pooled crops P x pool^2 x 256, the classifier's P x 1024 activations, the mask head's D x (2 mask_pool)^2 x 256 up-sampled
     map and its D x (2 mask_pool)^2 x classes output (256^2 with 1000 proposals: 85, not 511). predict() splits larger
-    batches into equal sub-batches."""
+    batches into equal sub-batches.
+    precision "f16": the fp16 family's size checks (csrc/conv_f16p.hip, bottleneck_f16.hip, mask_tail_f16.hip) keep every
+    tensor below 2^31 bytes, and the pipelined conv counts its fp32 result at 4 bytes per element even where only the fp16 copy
+    or the in-kernel RPN head sums are written: the RPN's shared 3x3 256 -> 512 on P2 (128 HW bytes per image) bounds large
+    images at 15 (1024^2 and 832 x 1344); the classifier's fp16 crops and fp32 fc activations, the mask head's convs (fp32 result
+    D x mask_pool^2 x 256) and the fused mask tail's output (D x (2 mask_pool)^2 x classes, <= MAX_BUFFER_BYTES - 64 KiB) bound the
+    rest."""
     p = min(cfg.proposal_count, cfg.pre_nms_limit)
     d = min(cfg.detection_max_instances, p)
     up = (2 * cfg.mask_pool_size) ** 2
     per_image = max(32 * cfg.image_height * cfg.image_width,
                     p * cfg.pool_size * cfg.pool_size * 256, p * 1024, p * cfg.num_classes * 5,
                     d * up * 256, d * up * cfg.num_classes)
-    return max(1, (MAX_BUFFER_BYTES // 4) // per_image)
+    n = max(1, (MAX_BUFFER_BYTES // 4) // per_image)
+    if precision == "f16":
+        bytes16 = max(4 * 32 * cfg.image_height * cfg.image_width, 2 * p * cfg.pool_size * cfg.pool_size * 256, 4 * p * 1024,
+                      4 * d * cfg.mask_pool_size ** 2 * 256)
+        n = min(n, ((1 << 31) - 1) // bytes16, (MAX_BUFFER_BYTES - 65536) // (4 * d * up * cfg.num_classes))
+    return max(1, n)
 
 
 class MaskRCNNInference:
@@ -86,7 +97,7 @@ class MaskRCNNInference:
         self.mask = modules.FusedMask(state_dict, self.device, precision=precision)
         self.anchors = pyramid_anchors(c).to(self.device)
         self.image_area = float(c.image_height * c.image_width)
-        self.max_batch = max_batch_per_launch(c)
+        self.max_batch = max_batch_per_launch(c, precision)
         env = os.environ.get("MRCNN_SUB_BATCHES")
         self.sub_batches = int(env) if env else (concurrent_sub_batches if concurrent_sub_batches is not None
                                                   else (2 if precision == "f16" else 1))

@@ -197,3 +197,117 @@ def test_direct_conv_refuses_the_oob_sentinel_window():
         rc = lib.mrcnn_conv_bn_act_f32(dummy, b, h, w, cin, dummy, cout, 1, 1, 1, 0, 0, 0, 0, None, None, None, 1, 0, 0, dummy,
                                        0, None)
         assert rc != 0 and b"too large" in lib.mrcnn_last_error(), (b, h, w, cin, cout)
+
+
+def _f16_checks(cfg, b):
+    """Every fp16 size check the "f16" step consults at batch b (modules.py: ConvWeight.takes_pipelined, FusedBottleneck, FusedMask),
+    by layer: the FPN laterals (1x1 C2..C5 -> 256) and smoothing convs (3x3 256 -> 256), the RPN's shared 3x3 256 -> 512 at every
+    pyramid level, the one-launch C2 blocks, the classifier's 7x7 and 1x1 GEMMs, the mask head's 3x3 convs and its fused tail."""
+    from maskrcnn_amd import ops
+    p = min(cfg.proposal_count, cfg.pre_nms_limit)
+    d = min(cfg.detection_max_instances, p)
+    same3 = (1, 1, 1, 1)
+    out = {}
+    for lvl, (h, w) in enumerate(cfg.backbone_shapes):
+        if lvl < 4:
+            out[f"lateral P{lvl + 2}"] = ops.conv_f16_pipelined_supported(b, h, w, 256 << lvl, 256, 1, 1)
+            out[f"smooth P{lvl + 2}"] = ops.conv_f16_pipelined_supported(b, h, w, 256, 256, 3, 3, same3)
+        out[f"rpn P{lvl + 2}"] = ops.conv_f16_pipelined_supported(b, h, w, 256, 512, 3, 3, same3)
+    h2, w2 = cfg.backbone_shapes[0]
+    out["c2 block"] = ops.bottleneck_c2_f16_supported(b, h2, w2, 256, 64, False)
+    out["c2 first block"] = ops.bottleneck_c2_f16_supported(b, h2, w2, 64, 64, True)
+    # the classifier runs its 7x7 'valid' conv as a 1x1 conv on the flattened crops (modules.FusedClassifier)
+    out["fc1"] = ops.conv_f16_pipelined_supported(b * p, 1, 1, cfg.pool_size * cfg.pool_size * 256, 1024, 1, 1)
+    out["fc2"] = ops.conv_f16_pipelined_supported(b * p, 1, 1, 1024, 1024, 1, 1)
+    mp = cfg.mask_pool_size
+    out["mask conv"] = ops.conv_f16_pipelined_supported(b * d, mp, mp, 256, 256, 3, 3, same3)
+    out["mask tail"] = ops.mask_tail_f16_supported(b * d, mp, mp, 256, 256, cfg.num_classes)
+    return out
+
+
+def test_max_batch_per_launch_f16_keeps_every_fp16_check_at_its_batch_1_answer():
+    """max_batch_per_launch(cfg, "f16"): up to that batch the fp16 size checks of the "f16" step's batch-scaled layers (_f16_checks:
+    the FPN, the RPN at every level, the C2 blocks, the classifier, the mask head and its tail) answer as they do for one image,
+    so none of those layers changes kernel with the batch (image i of a batch == image i alone). The fp16 family keeps each
+    tensor below 2^31 bytes and the pipelined conv counts its fp32 result even where it only writes fp16 or the RPN head sums:
+    the RPN's 512-channel shared conv on P2 allows 15 images at 1024^2 and at 832 x 1344, not the fp32 step's 31 and 30. Beyond
+    the bound some check changes its answer, or the fp32 bound (which the mode also obeys) is passed."""
+    from maskrcnn_amd.config import InferenceConfig
+    from maskrcnn_amd.pipeline import max_batch_per_launch
+    for h, w, p, d in ((1024, 1024, 500, 50), (832, 1344, 1000, 50), (256, 256, 1000, 50), (128, 128, 4096, 4096),
+                       (64, 64, 1000, 100), (64, 64, 1, 1)):
+        cfg = InferenceConfig(image_height=h, image_width=w, pre_nms_limit=p, proposal_count=p, detection_max_instances=d)
+        m = max_batch_per_launch(cfg, "f16")
+        assert 1 <= m <= max_batch_per_launch(cfg), (h, w, p, d, m)
+        one, at_m = _f16_checks(cfg, 1), _f16_checks(cfg, m)
+        assert at_m == one, (h, w, p, d, m, {k: (one[k], at_m[k]) for k in one if one[k] != at_m[k]})
+        assert _f16_checks(cfg, m + 1) != one or m == max_batch_per_launch(cfg), (h, w, p, d, m)
+    big = InferenceConfig(image_height=1024, image_width=1024)
+    r101 = InferenceConfig(image_height=832, image_width=1344, pre_nms_limit=1000, proposal_count=1000)
+    assert (max_batch_per_launch(big, "f16"), max_batch_per_launch(r101, "f16")) == (15, 15)
+    assert (max_batch_per_launch(big), max_batch_per_launch(r101)) == (31, 30)
+    for cfg in (big, r101):   # the binding check: P2's RPN conv (its heads form) goes off the pipelined kernel at 16 images
+        assert _f16_checks(cfg, 1)["rpn P2"] and not _f16_checks(cfg, 16)["rpn P2"]
+    # the other precisions run no fp16-family kernel: the fp32 bound
+    for precision in ("f32", "f16x3", "f32+f16x3"):
+        assert max_batch_per_launch(big, precision) == 31
+
+
+def test_entry_points_refuse_the_first_shape_past_their_limit():
+    """Argument validation runs before any HIP call (dummy pointers, never touched): for each kernel family with 32-bit buffer
+    byte offsets, the first shape past its size check is refused as "too large", and the shape just below it is inside the
+    check's arithmetic (tests/test_gpu_large_tensors.py runs several of them on the GPU). OOB = 0xFFFFFFF0."""
+    from maskrcnn_amd import _lib
+    lib = _lib.lib
+    dp = ctypes.c_void_p(16)
+    dq = ctypes.c_void_p(4096)   # a second pointer where the entry point refuses aliasing
+    big = ctypes.c_size_t(1 << 40)
+
+    def refused(rc, what):
+        assert rc != 0 and b"too large" in lib.mrcnn_last_error(), (what, lib.mrcnn_last_error())
+
+    # F(2x2): 4 B H W max(Cin, Cout) <= OOB. B4 x 512 x 510, 1024 -> 1000 is accepted: 4 * 4 * 512 * 510 * 1024 <= OOB
+    assert 4 * 4 * 512 * 510 * 1024 <= OOB < 4 * 4 * 512 * 512 * 1024
+    refused(lib.mrcnn_conv3x3_winograd_f32(dp, 1, 4, 512, 512, 1024, dp, 1000, None, None, 0, dp, None, None, 0, None), "wino k-blocked")
+    refused(lib.mrcnn_conv3x3_winograd_f32(dp, 0, 4, 512, 512, 1024, dp, 1000, None, None, 0, dp, dq, dp, big, None), "wino nhwc")
+    refused(lib.mrcnn_conv3x3_winograd_f32(dp, 1, 4, 512, 512, 8, dp, 1024, None, None, 0, dp, None, None, 0, None), "wino Cout")
+    refused(lib.mrcnn_conv3x3_winograd_nhwc_f32(dp, 4, 512, 512, 1024, dp, 1000, None, None, 0, dp, dq, big, None), "wino nhwc form")
+    # F(2x2) heads (the RPN's shared conv + heads): 4 B H W Cin <= OOB; B16 x 512 x 510 x 256 accepted
+    assert 4 * 16 * 512 * 510 * 256 <= OOB < 4 * 16 * 512 * 512 * 256
+    refused(lib.mrcnn_conv3x3_winograd_heads_f32(dp, 16, 512, 512, 256, dp, 512, None, None, 1, dp, 2, dq, None), "wino heads")
+    # the direct-kernel RPN level (exported by MRCNN_ABLATIONS builds only): 4 M Cin <= OOB; 2048 x 2040 x 256 accepted
+    if hasattr(lib, "mrcnn_rpn_level_fused_f32"):
+        assert 4 * 2048 * 2040 * 256 <= OOB < 4 * 2048 * 2048 * 256
+        refused(lib.mrcnn_rpn_level_fused_f32(dp, 1, 2048, 2048, 256, dp, 512, dp, dp, dp, 18, dq, big, dp, None), "rpn level")
+    # the fused fp32 bottleneck: 4 px 256 <= OOB; B4 x 1024 x 1008 accepted
+    assert 4 * 4 * 1024 * 1008 * 256 <= OOB < 4 * 4 * 1024 * 1024 * 256
+    refused(lib.mrcnn_bottleneck_fused_f32(dp, 4, 1024, 1024, 256, dp, None, None, dp, None, None, dp, None, None, 64, dq, None),
+            "bottleneck fused")
+    # the stem: y fp32 [B][H/2][W/2][64] <= OOB; B16 x 2048 x 2040 accepted (3.98 GiB)
+    assert 256 * 16 * 1024 * 1020 <= OOB < 256 * 16 * 1024 * 1024
+    for f in (lib.mrcnn_stem_conv7x7_s2_nhwc_f32, lib.mrcnn_stem_conv7x7_s2_nchw_f32, lib.mrcnn_stem_conv7x7_s2_nchw_f16out):
+        refused(f(dp, 16, 2048, 2048, dp, None, None, 1, dq, None), f.__name__)
+    # the stem + pool: fp32 y below 2^31 bytes (B32 x 2048 x 2040 accepted), fp32 x <= OOB for the fp16 form (B85 x 2048^2)
+    assert 16 * 32 * 2048 * 2040 < 1 << 31 <= 16 * 32 * 2048 * 2048
+    refused(lib.mrcnn_stem_conv7x7_s2_pool_f32(dp, 32, 2048, 2048, dp, None, None, dq, None), "stem pool f32")
+    assert 12 * 85 * 2048 * 2048 <= OOB < 12 * 86 * 2048 * 2048
+    refused(lib.mrcnn_stem_conv7x7_s2_pool_f16(dp, 86, 2048, 2048, dp, None, None, dq, None), "stem pool f16")
+    # the fp16 tile kernel (fill_common counts every tensor at 4 bytes per element): the 1x1 conv of
+    # test_direct_conv_refuses_the_oob_sentinel_window, M Cout = 2^30 - 2
+    for products in (1, 3):
+        refused(lib.mrcnn_conv_bn_act_nhwc_f16mfma(dp, 1, 466, 1103, 32, dp, dp, 2089, 1, 1, 1, 0, 0, 0, 0, None, None, None, 1, 0,
+                                                   products, dq, None), f"f16mfma products {products}")
+    for xf, yf in ((1, 1), (1, 0), (0, 1)):
+        refused(lib.mrcnn_conv_bn_act_nhwc_f16io(dp, xf, 1, 466, 1103, 32, dp, 2090, 1, 1, 1, 0, 0, 0, 0, None, None, None, 1, 0,
+                                                 dq, yf, None), f"f16io {xf}{yf}")
+    # the 2x2 deconvs: GEMM N = 4 Cout; 512 x 512 pixels x 4 x 1022 accepted, 4 x 1024 refused
+    assert 16 * 512 * 512 * 1022 <= OOB < 16 * 512 * 512 * 1024
+    refused(lib.mrcnn_deconv2x2_bias_act_nhwc_f16io(dp, 1, 512, 512, 32, dp, 1024, dp, 1, dq, None), "deconv f16io")
+    refused(lib.mrcnn_deconv2x2_bias_act_nhwc_f16mfma(dp, 1, 512, 512, 32, dp, dp, 1024, dp, 1, 3, dq, None), "deconv f16mfma")
+    # the fp16 family's own predicates, at the suggested top-of-range shapes and the first shape past them
+    assert lib.mrcnn_conv_f16_pipelined_supported(8, 512, 508, 256, 256, 3, 3, 1, 1, 1, 1, 1)
+    assert not lib.mrcnn_conv_f16_pipelined_supported(8, 512, 512, 256, 256, 3, 3, 1, 1, 1, 1, 1)
+    assert lib.mrcnn_bottleneck_c2_f16_supported(16, 512, 508, 256, 64, 0)
+    assert not lib.mrcnn_bottleneck_c2_f16_supported(16, 512, 512, 256, 64, 0)
+    assert lib.mrcnn_mask_tail_f16_supported(16907, 14, 14, 256, 256, 81)
+    assert not lib.mrcnn_mask_tail_f16_supported(16908, 14, 14, 256, 256, 81)
