@@ -18,11 +18,19 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
+import weakref
 
 import torch
 
 from ._lib import MaskrcnnHipError, c_f32, c_i32, c_vp, check, lib
+
+__all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnHipError",
+           "conv_bn_act", "conv_bn_act_f16mfma", "split_f16", "same_pad", "maxpool", "nchw_to_nhwc", "nhwc_to_nchw",
+           "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
+           "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
+           "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -35,10 +43,38 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+class HeadSums:
+    """Output of conv3x3_winograd_heads for one pyramid level: the two k halves of the 1x1-head sums (without bias) in
+    position-major pixel order, [2, rows, 32] fp32, for a [B, H, W] level. Consumed by rpn_scores_deltas."""
+
+    def __init__(self, part: torch.Tensor, batch: int, height: int, width: int, tile_mode: int = 1):
+        self.part, self.batch, self.height, self.width, self.tile_mode = part, batch, height, width, tile_mode
+
+    def to_nhwc(self, bias: torch.Tensor) -> torch.Tensor:
+        """[B,H,W,18] = (half 0 + half 1) + bias, in image order (tests / debugging; the pipeline never needs it)."""
+        b, h, w = self.batch, self.height, self.width
+        if self.tile_mode == 4:                                            # two planes in pixel order (conv_f16_pipelined_heads)
+            return ((self.part[0, :, :18] + self.part[1, :, :18]) + bias).view(b, h, w, 18).contiguous()
+        th, tw = h // 2, w // 2
+        if self.tile_mode == 1:
+            t = b * th * tw
+            v = (self.part[0, :t * 4, :18] + self.part[1, :t * 4, :18]) + bias
+            return v.view(b, th, tw, 2, 2, 18).permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, 18).contiguous()
+        if self.tile_mode == 3:                                            # F(4x4): rows (b, tyb, txb, py4, px8, i4, j4)
+            tyb, txb = -(-(h // 4) // 4), -(-(w // 4) // 8)
+            v = self.part[:, :18] + bias
+            v = v.view(b, tyb, txb, 4, 8, 4, 4, 18).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(b, tyb * 16, txb * 32, 18)
+            return v[:, :h, :w].contiguous()
+        tyb, txb = -(-th // 8), -(-tw // 8)
+        v = (self.part[0, :, :18] + self.part[1, :, :18]) + bias          # rows: (b, tyb, txb, py, px, a, c)
+        v = v.view(b, tyb, txb, 8, 8, 2, 2, 18).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(b, tyb * 16, txb * 16, 18)
+        return v[:, :h, :w].contiguous()
+
+
 def _tensors(obj):
     if isinstance(obj, torch.Tensor):
         yield obj
-    elif hasattr(obj, "part") and isinstance(getattr(obj, "part"), torch.Tensor):   # HeadSums
+    elif isinstance(obj, HeadSums):
         yield obj.part
     elif isinstance(obj, (list, tuple)):
         for o in obj:
@@ -186,14 +222,18 @@ def crop(image: torch.Tensor, boxes: torch.Tensor, box_index: torch.Tensor,
          extrapolation_value: float, crop_height: int, crop_width: int) -> torch.Tensor:
     """Functional form: returns a fresh [N, C, crop_height, crop_width] tensor."""
     _check_crop_inputs(image, boxes, box_index)
+    crops = torch.empty(boxes.size(0), image.size(1), crop_height, crop_width, dtype=torch.float32, device=image.device)
+    _crop_launch(image, boxes, box_index, extrapolation_value, crop_height, crop_width, crops)
+    return crops
+
+
+def _crop_launch(image, boxes, box_index, extrapolation_value, crop_height, crop_width, crops) -> None:
+    """The one launch behind crop and crop_forward: checked inputs (any strides), crops contiguous [N,C,crop_height,crop_width]."""
     image, boxes, box_index = image.contiguous(), boxes.contiguous(), box_index.contiguous()
     b, c, h, w = image.shape
-    n = boxes.size(0)
-    crops = torch.empty(n, c, crop_height, crop_width, dtype=torch.float32, device=image.device)
     check(lib.mrcnn_crop_forward_f32(image.data_ptr(), b, c, h, w, boxes.data_ptr(),
-                                     box_index.data_ptr(), n, float(extrapolation_value),
+                                     box_index.data_ptr(), boxes.size(0), float(extrapolation_value),
                                      int(crop_height), int(crop_width), crops.data_ptr(), _stream()))
-    return crops
 
 
 @_on_device
@@ -204,13 +244,8 @@ def _crop_forward(image, boxes, box_index, extrapolation_value, crop_height, cro
     _need_gpu(crops)
     if crops.dtype != torch.float32:
         raise RuntimeError("crop_forward: expected scalar type Float for crops")
-    image, boxes, box_index = image.contiguous(), boxes.contiguous(), box_index.contiguous()
-    b, c, h, w = image.shape
-    n = boxes.size(0)
-    crops.resize_(n, c, crop_height, crop_width)
-    check(lib.mrcnn_crop_forward_f32(image.data_ptr(), b, c, h, w, boxes.data_ptr(),
-                                     box_index.data_ptr(), n, float(extrapolation_value),
-                                     int(crop_height), int(crop_width), crops.data_ptr(), _stream()))
+    crops.resize_(boxes.size(0), image.size(1), crop_height, crop_width)
+    _crop_launch(image, boxes, box_index, extrapolation_value, crop_height, crop_width, crops)
 
 
 @_on_device
@@ -323,9 +358,6 @@ def roi_align_pyramid(feature_maps, rois: torch.Tensor, pool: int, image_area: f
     return (out, levels) if return_levels else out
 
 
-__all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnHipError"]
-
-
 # --------------------------------------------------------------------------------------------------
 # conv + BN + ReLU (+ residual), channels-last
 # --------------------------------------------------------------------------------------------------
@@ -333,6 +365,28 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
 # algorithmic_bytes = each operand/result tensor once, kernel tag) —
 # HIP events recorded on the launch stream; used by bench.py's roofline pass, never in the timed region.
 CONV_PROFILE: list | None = None
+
+
+def _launch(fn, args, book) -> None:
+    """check(fn(*args)) for an entry point whose launches the profiling pass times. While CONV_PROFILE is a list, HIP events
+    go on the stream right before and right after the launch and the row (start, end, *book()) is appended; book() ->
+    (algorithmic FLOPs, (M, N, K), algorithmic bytes, kernel tag[, executed FLOPs[, dict]]). book runs only then, and only after
+    the end event is on the stream: it may synchronise (row_counts.tolist()) or call back into the library."""
+    prof = CONV_PROFILE
+    if prof is None:
+        check(fn(*args))
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(*args))
+    e1.record()
+    prof.append((e0, e1, *book()))
+
+
+def _pad_out_hw(pad, h: int, w: int, kh: int, kw: int, stride: int = 1):
+    """pad = (top, left, bottom, right) as ints, and the output height and width of a kh x kw window at this stride."""
+    pt, pl, pb, pr = [int(v) for v in pad]
+    return (pt, pl, pb, pr), (h + pt + pb - kh) // stride + 1, (w + pl + pr - kw) // stride + 1
 
 
 @_on_device
@@ -360,9 +414,7 @@ def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | None,
     cout, kh, kw, wcin = w.shape
     if wcin != cin:
         raise RuntimeError(f"conv_bn_act: weight Cin {wcin} != input Cin {cin}")
-    pt, pl, pb, pr = [int(v) for v in pad]
-    oh = (h + pt + pb - kh) // stride + 1
-    ow = (wd + pl + pr - kw) // stride + 1
+    (pt, pl, pb, pr), oh, ow = _pad_out_hw(pad, h, wd, kh, kw, stride)
     if out_kblocked:
         assert out is None and cout % 8 == 0
         out = torch.empty(cout // 8, b, oh, ow, 8, dtype=torch.float32, device=x.device)
@@ -378,37 +430,34 @@ def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | None,
         want = (cout // 8, b, oh // res_div, ow // res_div, 8) if res_kblocked else (b, oh // res_div, ow // res_div, cout)
         assert tuple(residual.shape) == want, \
             f"residual {tuple(residual.shape)} vs output {(b, oh, ow, cout)} / {res_div}"
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     if row_counts is not None:
         assert residual is None and not out_kblocked and row_counts.dtype == torch.int32 and row_counts.is_contiguous()
         assert rows_per_group >= 1 and row_counts.numel() * rows_per_group == b * oh * ow
-        check(lib.mrcnn_conv_bn_act_rows_f32(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb,
-                                             pr, _ptr(scale), _ptr(shift), int(relu), out.data_ptr(), row_counts.data_ptr(),
-                                             int(rows_per_group), _stream()))
-    else:
-        check(lib.mrcnn_conv_bn_act_f32(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw,
-                                        int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift),
-                                        _ptr(residual), int(res_div), 1 if res_kblocked else 0, int(relu),
-                                        out.data_ptr(), 1 if out_kblocked else 0, _stream()))
-    if prof is not None:
-        e1.record()
-        m, k = b * oh * ow, kh * kw * (algo_cin or cin)  # algorithmic: 2*MACs of the un-padded conv
-        if row_counts is not None:
+
+        def book_rows():
             # Book what RAN: the kernel returns early for M tiles without a valid row (conv.hip), so the MFMA work is the
             # executed tiles' rows and the problem the reference poses is the valid rows only (model.py:1366-1374). The host
             # read of row_counts synchronises — profiling pass only, after the end event is on the stream.
+            m, k = b * oh * ow, kh * kw * (algo_cin or cin)
             bm = int(lib.mrcnn_conv_rows_tile_m(cout))
             rows_exec, rows_valid = rows_executed(row_counts.tolist(), int(rows_per_group), m, bm)
             kk = kh * kw * cin
             nbytes = 4 * (rows_exec * (kk + cout) + w.numel())
-            prof.append((e0, e1, 2.0 * rows_valid * k * cout, (rows_valid, cout, k), nbytes, "direct",
-                         2.0 * rows_exec * k * cout, {"rows_slots": m, "rows_executed": rows_exec, "rows_valid": rows_valid}))
-            return out
+            return (2.0 * rows_valid * k * cout, (rows_valid, cout, k), nbytes, "direct", 2.0 * rows_exec * k * cout,
+                    {"rows_slots": m, "rows_executed": rows_exec, "rows_valid": rows_valid})
+        _launch(lib.mrcnn_conv_bn_act_rows_f32,
+                (x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift),
+                 int(relu), out.data_ptr(), row_counts.data_ptr(), int(rows_per_group), _stream()), book_rows)
+        return out
+
+    def book():
+        m, k = b * oh * ow, kh * kw * (algo_cin or cin)  # algorithmic: 2*MACs of the un-padded conv
         nbytes = 4 * (x.numel() + w.numel() + out.numel() + (residual.numel() if residual is not None else 0))
-        prof.append((e0, e1, 2.0 * m * k * cout, (m, cout, k), nbytes, "direct"))
+        return 2.0 * m * k * cout, (m, cout, k), nbytes, "direct"
+    _launch(lib.mrcnn_conv_bn_act_f32,
+            (x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift),
+             _ptr(residual), int(res_div), 1 if res_kblocked else 0, int(relu), out.data_ptr(), 1 if out_kblocked else 0,
+             _stream()), book)
     return out
 
 
@@ -452,9 +501,7 @@ def conv_bn_act_f16mfma(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor 
     cout, kh, kw, wcin = w_hi.shape
     if wcin != cin:
         raise RuntimeError(f"conv_bn_act_f16mfma: weight Cin {wcin} != input Cin {cin}")
-    pt, pl, pb, pr = [int(v) for v in pad]
-    oh = (h + pt + pb - kh) // stride + 1
-    ow = (wd + pl + pr - kw) // stride + 1
+    (pt, pl, pb, pr), oh, ow = _pad_out_hw(pad, h, wd, kh, kw, stride)
     io16 = x_f16 or out_f16
     if io16 and products != 1:
         raise RuntimeError("conv_bn_act_f16mfma: fp16 activations belong to the plain-fp16 mode (products = 1)")
@@ -462,26 +509,23 @@ def conv_bn_act_f16mfma(x: torch.Tensor, w_hi: torch.Tensor, w_lo: torch.Tensor 
     if residual is not None:
         assert residual.is_contiguous() and tuple(residual.shape) == (b, oh // res_div, ow // res_div, cout)
         assert residual.dtype == out.dtype, "the residual has the output's storage type"
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if io16:
-        check(lib.mrcnn_conv_bn_act_nhwc_f16io(x.data_ptr(), 1 if x_f16 else 0, b, h, wd, cin, w_hi.data_ptr(), cout, kh,
-                                               kw, int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift), _ptr(residual),
-                                               int(res_div), int(relu), out.data_ptr(), 1 if out_f16 else 0, _stream()))
-    else:
-        check(lib.mrcnn_conv_bn_act_nhwc_f16mfma(x.data_ptr(), b, h, wd, cin, w_hi.data_ptr(), _ptr(w_lo), cout,
-                                                 kh, kw, int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift),
-                                                 _ptr(residual), int(res_div), int(relu), int(products),
-                                                 out.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * oh * ow, kh * kw * (algo_cin or cin)
         nbytes = x.numel() * x.element_size() + out.numel() * out.element_size() + \
             (residual.numel() * residual.element_size() if residual is not None else 0) + \
             2 * w_hi.numel() * (2 if products == 3 else 1)
-        prof.append((e0, e1, 2.0 * m * k * cout, (m, cout, k), nbytes, "f16"))
+        return 2.0 * m * k * cout, (m, cout, k), nbytes, "f16"
+    if io16:
+        _launch(lib.mrcnn_conv_bn_act_nhwc_f16io,
+                (x.data_ptr(), 1 if x_f16 else 0, b, h, wd, cin, w_hi.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb, pr,
+                 _ptr(scale), _ptr(shift), _ptr(residual), int(res_div), int(relu), out.data_ptr(), 1 if out_f16 else 0,
+                 _stream()), book)
+    else:
+        _launch(lib.mrcnn_conv_bn_act_nhwc_f16mfma,
+                (x.data_ptr(), b, h, wd, cin, w_hi.data_ptr(), _ptr(w_lo), cout, kh, kw, int(stride), pt, pl, pb, pr,
+                 _ptr(scale), _ptr(shift), _ptr(residual), int(res_div), int(relu), int(products), out.data_ptr(), _stream()),
+                book)
     return out
 
 
@@ -507,26 +551,21 @@ def conv_f16_pipelined(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | N
     cout, kh, kw, wcin = w.shape
     if wcin != cin:
         raise RuntimeError(f"conv_f16_pipelined: weight Cin {wcin} != input Cin {cin}")
-    pt, pl, pb, pr = [int(v) for v in pad]
-    oh, ow = (h + pt + pb - kh) // stride + 1, (wd + pl + pr - kw) // stride + 1
+    (pt, pl, pb, pr), oh, ow = _pad_out_hw(pad, h, wd, kh, kw, stride)
     y16 = torch.empty(b, oh, ow, cout, dtype=torch.float16, device=x.device) if out_f16 else None
     y32 = torch.empty(b, oh, ow, cout, dtype=torch.float32, device=x.device) if out_f32 else None
     if residual is not None:
         assert residual.dtype == torch.float16 and residual.is_contiguous()
         assert tuple(residual.shape) == (b, oh // res_div, ow // res_div, cout)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv_f16_pipelined(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb, pr,
-                                       _ptr(scale), _ptr(shift), _ptr(residual), int(res_div), int(relu), _ptr(y16),
-                                       _ptr(y32), int(tile_rows), int(tile_cols), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * oh * ow, kh * kw * (algo_cin or cin)
         nbytes = x.numel() * 2 + (y16.numel() * 2 if out_f16 else 0) + (y32.numel() * 4 if out_f32 else 0) + \
             (residual.numel() * 2 if residual is not None else 0) + 2 * w.numel()
-        prof.append((e0, e1, 2.0 * m * k * cout, (m, cout, k), nbytes, "f16p"))
+        return 2.0 * m * k * cout, (m, cout, k), nbytes, "f16p"
+    _launch(lib.mrcnn_conv_f16_pipelined,
+            (x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, int(stride), pt, pl, pb, pr, _ptr(scale), _ptr(shift),
+             _ptr(residual), int(res_div), int(relu), _ptr(y16), _ptr(y32), int(tile_rows), int(tile_cols), _stream()), book)
     if out_f16 and out_f32:
         return y16, y32
     return y16 if out_f16 else y32
@@ -563,15 +602,8 @@ def bottleneck_c2_f16(x: torch.Tensor, w1f, s1, t1, w2f, s2, t2, w3f, s3, t3, wd
         if v is not None and not (v.dtype == torch.float32 and v.numel() == n and v.is_contiguous()):
             raise RuntimeError("bottleneck_c2_f16: scale / shift vectors must be contiguous fp32 of the layer's Cout")
     y = torch.empty(b, h, w, 256, dtype=torch.float16, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_bottleneck_c2_f16(x.data_ptr(), b, h, w, cin, w1f.data_ptr(), _ptr(s1), _ptr(t1), w2f.data_ptr(), _ptr(s2),
-                                      _ptr(t2), w3f.data_ptr(), _ptr(s3), _ptr(t3), _ptr(wdf), _ptr(sd), _ptr(td),
-                                      y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m = b * h * w
         kk = cin * 64 + 576 * 64 + 64 * 256 + (cin * 256 if wdf is not None else 0)       # multiply-adds per pixel
         nbytes = x.numel() * 2 + y.numel() * 2 + 2 * kk
@@ -581,7 +613,10 @@ def bottleneck_c2_f16(x: torch.Tensor, w1f, s1, t1, w2f, s2, t2, w3f, s3, t3, wd
                   (2.0 * m * 64 * 256, 2 * (m * 64 + 2 * m * 256 + 64 * 256))]
         if wdf is not None:
             layers.append((2.0 * m * cin * 256, 2 * (m * cin + m * 256 + cin * 256)))
-        prof.append((e0, e1, 2.0 * m * kk, (m, 256, kk // 256), nbytes, "f16blk", 2.0 * m * kk, {"layers": layers}))
+        return 2.0 * m * kk, (m, 256, kk // 256), nbytes, "f16blk", 2.0 * m * kk, {"layers": layers}
+    _launch(lib.mrcnn_bottleneck_c2_f16,
+            (x.data_ptr(), b, h, w, cin, w1f.data_ptr(), _ptr(s1), _ptr(t1), w2f.data_ptr(), _ptr(s2), _ptr(t2), w3f.data_ptr(),
+             _ptr(s3), _ptr(t3), _ptr(wdf), _ptr(sd), _ptr(td), y.data_ptr(), _stream()), book)
     return y
 
 
@@ -603,26 +638,23 @@ def mask_tail_f16(x: torch.Tensor, wde_frags: torch.Tensor, bias_de4: torch.Tens
         raise RuntimeError("mask_tail_f16: weight fragments / biases do not belong to a 256 -> 256 deconv and a <= 96-class conv5")
     assert bias_de4.dtype == torch.float32 and bias5.dtype == torch.float32 and bias_de4.is_contiguous() and bias5.is_contiguous()
     y = torch.empty(r, 2 * h, 2 * w, classes, dtype=torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_mask_tail_f16(x.data_ptr(), r, h, w, cin, wde_frags.data_ptr(), bias_de4.data_ptr(), 256, w5_frags.data_ptr(),
-                                  bias5.data_ptr(), classes, y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m = r * h * w
         kk = cin * 1024 + 4 * 256 * classes                                   # multiply-adds per input pixel
         layers = [(2.0 * m * cin * 1024, 2 * (m * cin + m * 1024 + cin * 1024)),          # deconv as the per-layer path books it
                   (2.0 * m * 4 * 256 * classes, 2 * m * 1024 + 4 * m * 4 * classes + 2 * 256 * classes)]
-        prof.append((e0, e1, 2.0 * m * kk, (m, 4 * classes, kk // (4 * classes)), x.numel() * 2 + y.numel() * 4 + 2 * (1024 + 96) * cin,
-                     "f16tail", 2.0 * m * kk, {"layers": layers}))
+        return (2.0 * m * kk, (m, 4 * classes, kk // (4 * classes)), x.numel() * 2 + y.numel() * 4 + 2 * (1024 + 96) * cin,
+                "f16tail", 2.0 * m * kk, {"layers": layers})
+    _launch(lib.mrcnn_mask_tail_f16,
+            (x.data_ptr(), r, h, w, cin, wde_frags.data_ptr(), bias_de4.data_ptr(), 256, w5_frags.data_ptr(), bias5.data_ptr(),
+             classes, y.data_ptr(), _stream()), book)
     return y
 
 
 @_on_device
 def conv_f16_pipelined_heads(x: torch.Tensor, w: torch.Tensor, scale, shift, w_head32: torch.Tensor, pad=(1, 1, 1, 1),
-                             relu: bool = True, tile_rows: int = 0, algo_cin: int | None = None) -> "HeadSums":
+                             relu: bool = True, tile_rows: int = 0, algo_cin: int | None = None) -> HeadSums:
     """RPN conv_shared + both 1x1 heads in one launch on the pipelined fp16 kernel ("f16" mode; model.py:605-607,624-641):
     x fp16 NHWC, w fp16 OHWI with Cout = 512, w_head32 fp16 [32, 512] (rows 0-17: conv_class then conv_bbox). → HeadSums
     (form 4: two planes in pixel order, without the bias)."""
@@ -632,20 +664,15 @@ def conv_f16_pipelined_heads(x: torch.Tensor, w: torch.Tensor, scale, shift, w_h
     cout, kh, kw, wcin = w.shape
     assert wcin == cin and cout == 512, "the consumer (rpn_scores_deltas form 4) adds exactly two 256-channel planes"
     assert w_head32.dtype == torch.float16 and w_head32.is_contiguous() and tuple(w_head32.shape) == (32, cout)
-    pt, pl, pb, pr = [int(v) for v in pad]
-    oh, ow = h + pt + pb - kh + 1, wd + pl + pr - kw + 1
+    (pt, pl, pb, pr), oh, ow = _pad_out_hw(pad, h, wd, kh, kw)
     part = torch.empty(cout // 256, b * oh * ow, 32, dtype=torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv_f16_pipelined_heads(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, pt, pl, pb, pr,
-                                             _ptr(scale), _ptr(shift), 1 if relu else 0, w_head32.data_ptr(),
-                                             part.data_ptr(), int(tile_rows), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * oh * ow, kh * kw * (algo_cin or cin)
-        prof.append((e0, e1, 2.0 * m * cout * (k + 18), (m, cout, k), x.numel() * 2 + part.numel() * 4 + 2 * w.numel(), "f16p"))
+        return 2.0 * m * cout * (k + 18), (m, cout, k), x.numel() * 2 + part.numel() * 4 + 2 * w.numel(), "f16p"
+    _launch(lib.mrcnn_conv_f16_pipelined_heads,
+            (x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, pt, pl, pb, pr, _ptr(scale), _ptr(shift),
+             1 if relu else 0, w_head32.data_ptr(), part.data_ptr(), int(tile_rows), _stream()), book)
     return HeadSums(part, b, oh, ow, 4)
 
 
@@ -663,7 +690,6 @@ def same_pad(size_a: int, size_b: int, kernel: int, stride: int):
     """SamePad2d (model.py:64-87) as (top, left, bottom, right) for a [.., size_a, size_b] (H, W) input.
     The reference computes the LAST-dim pad from size(2) and vice versa (its width/height names are
     swapped); reproduced as written — it only matters when H and W need different pad amounts."""
-    import math
     out_a = math.ceil(float(size_a) / float(stride))
     out_b = math.ceil(float(size_b) / float(stride))
     pad_a = max((out_a - 1) * stride + kernel - size_a, 0)
@@ -680,9 +706,7 @@ def maxpool(x: torch.Tensor, kernel: int, stride: int, pad=(0, 0, 0, 0), out_kbl
     _need_gpu(x)
     assert x.is_contiguous() and x.dtype in (torch.float32, torch.float16) and x.dim() == 4
     b, h, w, c = x.shape
-    pt, pl, pb, pr = [int(v) for v in pad]
-    oh = (h + pt + pb - kernel) // stride + 1
-    ow = (w + pl + pr - kernel) // stride + 1
+    (pt, pl, pb, pr), oh, ow = _pad_out_hw(pad, h, w, kernel, kernel, stride)
     if x.dtype == torch.float16:
         assert not out_kblocked
         y = torch.empty(b, oh, ow, c, dtype=torch.float16, device=x.device)
@@ -740,22 +764,18 @@ def bottleneck_fused(x, w1, s1, t1, u2, s2, t2, w3, s3, t3) -> torch.Tensor:
     for t, n in ((s1, planes), (t1, planes), (s2, planes), (t2, planes), (s3, 4 * planes), (t3, 4 * planes)):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
     y = torch.empty(b, h, w, 4 * planes, dtype=torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_bottleneck_fused_f32(x.data_ptr(), b, h, w, cin, w1.data_ptr(), _ptr(s1), _ptr(t1), u2.data_ptr(),
-                                         _ptr(s2), _ptr(t2), w3.data_ptr(), _ptr(s3), _ptr(t3), planes, y.data_ptr(),
-                                         _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m = b * h * w
         algo = 2.0 * m * (cin * planes + 9 * planes * planes + planes * 4 * planes)
         # what the MFMA pipe executes: conv1 on 352 GEMM rows per 256 output pixels (halo + row-tile padding),
         # conv2 as Winograd (1/2.25), conv3 as is
         executed = 2.0 * m * (cin * planes * 352.0 / 256.0 + 9 * planes * planes / 2.25 + planes * 4 * planes)
-        prof.append((e0, e1, algo, (m, 4 * planes, cin + 9 * planes + planes),
-                     4.0 * (2 * x.numel() + y.numel() + w1.numel() + u2.numel() + w3.numel()), "bottleneck", executed))
+        return (algo, (m, 4 * planes, cin + 9 * planes + planes),
+                4.0 * (2 * x.numel() + y.numel() + w1.numel() + u2.numel() + w3.numel()), "bottleneck", executed)
+    _launch(lib.mrcnn_bottleneck_fused_f32,
+            (x.data_ptr(), b, h, w, cin, w1.data_ptr(), _ptr(s1), _ptr(t1), u2.data_ptr(), _ptr(s2), _ptr(t2), w3.data_ptr(),
+             _ptr(s3), _ptr(t3), planes, y.data_ptr(), _stream()), book)
     return y
 
 
@@ -765,35 +785,21 @@ def bottleneck_fused(x, w1, s1, t1, u2, s2, t2, w3, s3, t3) -> torch.Tensor:
 # step with its own flags.
 BOTTLENECK_OP_FUSED = (os.environ.get("MRCNN_TUNING") == "1" and os.environ.get("MRCNN_FUSED_BOTTLENECK", "0") == "1"
                        and os.environ.get("MRCNN_WINOGRAD", "1") != "0")
-_U2_CACHE: dict = {}   # data_ptr -> (weakref to the conv2 weight tensor, its version, its Winograd transform)
+_TRANSFORM_CACHE: dict = {}   # transform -> {data_ptr: (weakref to the conv2 weight tensor, its version, its Winograd transform)}
 
 
-def _cached_winograd_weights(w2: torch.Tensor) -> torch.Tensor:
-    """The transform of a conv2 weight is computed once per weight tensor, not per call. An entry is valid only for the SAME
-    tensor object at the same version: an address alone is reused by the allocator for other weights."""
-    import weakref
-    e = _U2_CACHE.get(w2.data_ptr())
+def _cached_transform(transform, w2: torch.Tensor) -> torch.Tensor:
+    """transform(w2) — winograd_weights (F(2x2)) or winograd4_weights (F(4x4)) of a conv2 weight — computed once per weight
+    tensor, not per call. An entry is valid only for the SAME tensor object at the same version: an address alone is reused by
+    the allocator for other weights."""
+    cache = _TRANSFORM_CACHE.setdefault(transform, {})
+    e = cache.get(w2.data_ptr())
     if e is not None and e[0]() is w2 and e[1] == w2._version:
         return e[2]
-    if len(_U2_CACHE) > 256:
-        _U2_CACHE.clear()
-    u = winograd_weights(w2)
-    _U2_CACHE[w2.data_ptr()] = (weakref.ref(w2), w2._version, u)
-    return u
-
-
-_U4_CACHE: dict = {}   # the same for the F(4x4) transform
-
-
-def _cached_winograd4_weights(w2: torch.Tensor) -> torch.Tensor:
-    import weakref
-    e = _U4_CACHE.get(w2.data_ptr())
-    if e is not None and e[0]() is w2 and e[1] == w2._version:
-        return e[2]
-    if len(_U4_CACHE) > 256:
-        _U4_CACHE.clear()
-    u = winograd4_weights(w2)
-    _U4_CACHE[w2.data_ptr()] = (weakref.ref(w2), w2._version, u)
+    if len(cache) > 256:
+        cache.clear()
+    u = transform(w2)
+    cache[w2.data_ptr()] = (weakref.ref(w2), w2._version, u)
     return u
 
 
@@ -864,10 +870,10 @@ def bottleneck_forward(x, w1, s1, t1, w2, s2, t2, w3, s3, t3, wd, sd, td, stride
     if (BOTTLENECK_OP_FUSED and wd is None and int(stride) == 1 and x.is_cuda and x.dim() == 4
             and tuple(w2.shape[1:3]) == (3, 3)
             and bottleneck_fused_supported(x.size(1), x.size(2), x.size(3), w1.size(0)) and w3.size(0) == x.size(3)):
-        return bottleneck_fused(x, w1, s1, t1, _cached_winograd_weights(w2), s2, t2, w3, s3, t3)
+        return bottleneck_fused(x, w1, s1, t1, _cached_transform(winograd_weights, w2), s2, t2, w3, s3, t3)
     wino = bool(_m.WINOGRAD) and x.is_cuda and tuple(w2.shape[1:3]) == (3, 3) and w2.size(3) % 8 == 0
-    u2 = _cached_winograd_weights(w2) if wino else None
-    u4 = _cached_winograd4_weights(w2) if (wino and _m.WINOGRAD4 and _m.WINOGRAD4_TRUNK and w2.size(0) % 64 == 0) else None
+    u2 = _cached_transform(winograd_weights, w2) if wino else None
+    u4 = _cached_transform(winograd4_weights, w2) if (wino and _m.WINOGRAD4 and _m.WINOGRAD4_TRUNK and w2.size(0) % 64 == 0) else None
     return bottleneck_native(x, w1, s1, t1, w2, u2, u4, s2, t2, w3, s3, t3, wd, sd, td, int(stride), _m.WINOGRAD4_MIN_TILES,
                              _m.FUSED_CONV3)
 
@@ -877,38 +883,6 @@ _LIB.define("bottleneck_forward(Tensor x, Tensor w1, Tensor s1, Tensor t1, Tenso
             "int stride) -> Tensor")
 _LIB.impl("bottleneck_forward", bottleneck_forward, "CUDA")
 _LIB.impl("bottleneck_forward", lambda x, *a: _need_gpu(x), "CPU")
-
-__all__ += ["conv_bn_act", "conv_bn_act_f16mfma", "split_f16", "same_pad", "maxpool", "nchw_to_nhwc", "nhwc_to_nchw", "bottleneck_forward",
-            "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan"]
-
-
-class HeadSums:
-    """Output of conv3x3_winograd_heads for one pyramid level: the two k halves of the 1x1-head sums (without bias) in
-    position-major pixel order, [2, rows, 32] fp32, for a [B, H, W] level. Consumed by rpn_scores_deltas."""
-
-    def __init__(self, part: torch.Tensor, batch: int, height: int, width: int, tile_mode: int = 1):
-        self.part, self.batch, self.height, self.width, self.tile_mode = part, batch, height, width, tile_mode
-
-    def to_nhwc(self, bias: torch.Tensor) -> torch.Tensor:
-        """[B,H,W,18] = (half 0 + half 1) + bias, in image order (tests / debugging; the pipeline never needs it)."""
-        b, h, w = self.batch, self.height, self.width
-        if self.tile_mode == 4:                                            # two planes in pixel order (conv_f16_pipelined_heads)
-            return ((self.part[0, :, :18] + self.part[1, :, :18]) + bias).view(b, h, w, 18).contiguous()
-        th, tw = h // 2, w // 2
-        if self.tile_mode == 1:
-            t = b * th * tw
-            v = (self.part[0, :t * 4, :18] + self.part[1, :t * 4, :18]) + bias
-            return v.view(b, th, tw, 2, 2, 18).permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, 18).contiguous()
-        if self.tile_mode == 3:                                            # F(4x4): rows (b, tyb, txb, py4, px8, i4, j4)
-            tyb, txb = -(-(h // 4) // 4), -(-(w // 4) // 8)
-            v = self.part[:, :18] + bias
-            v = v.view(b, tyb, txb, 4, 8, 4, 4, 18).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(b, tyb * 16, txb * 32, 18)
-            return v[:, :h, :w].contiguous()
-        tyb, txb = -(-th // 8), -(-tw // 8)
-        v = (self.part[0, :, :18] + self.part[1, :, :18]) + bias          # rows: (b, tyb, txb, py, px, a, c)
-        v = v.view(b, tyb, txb, 8, 8, 2, 2, 18).permute(0, 1, 3, 5, 2, 4, 6, 7).reshape(b, tyb * 16, txb * 16, 18)
-        return v[:, :h, :w].contiguous()
-
 
 @_on_device
 def conv3x3_winograd_heads(x_kblocked: torch.Tensor, u: torch.Tensor, scale, shift, w_head32: torch.Tensor,
@@ -927,20 +901,16 @@ def conv3x3_winograd_heads(x_kblocked: torch.Tensor, u: torch.Tensor, scale, shi
                            "kernel are required; the linear-tile heads variant is an MRCNN_ABLATIONS build")
     rows = int(lib.mrcnn_conv3x3_winograd_heads_rows(b, h, w, mode))
     part = torch.empty(2, rows, 32, dtype=torch.float32, device=x_kblocked.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv3x3_winograd_heads_f32(x_kblocked.data_ptr(), b, h, w, cin, u.data_ptr(), cout, _ptr(scale),
-                                               _ptr(shift), 1 if relu else 0, w_head32.data_ptr(), mode, part.data_ptr(),
-                                               _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * h * w, 9 * (algo_cin or cin)
         algo = 2.0 * m * cout * (k + 18)                      # the 3x3 conv + both 1x1 heads (18 channels)
         executed = 2.0 * m * cout * (k / 2.25 + 32)           # Winograd multiplies + the head MFMAs on 32 padded columns
-        prof.append((e0, e1, algo, (m, cout, k), 4.0 * (m * cin + 2 * part.numel() / 2 + cout * k),
-                     "winograd_spatial" if mode == 2 else "winograd", executed))
+        return (algo, (m, cout, k), 4.0 * (m * cin + 2 * part.numel() / 2 + cout * k),
+                "winograd_spatial" if mode == 2 else "winograd", executed)
+    _launch(lib.mrcnn_conv3x3_winograd_heads_f32,
+            (x_kblocked.data_ptr(), b, h, w, cin, u.data_ptr(), cout, _ptr(scale), _ptr(shift), 1 if relu else 0,
+             w_head32.data_ptr(), mode, part.data_ptr(), _stream()), book)
     return HeadSums(part, b, h, w, mode)
 
 
@@ -986,9 +956,6 @@ def proposal_decode(anchors, deltas, order, top_scores, std_dev, image_height, i
     return dets
 
 
-__all__ += ["rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums"]
-
-
 @_on_device
 def detection_decode(logits, bbox, rois, roi_counts, windows, std_dev, image_height, image_width,
                      min_confidence: float = 0.0):
@@ -1009,9 +976,6 @@ def detection_decode(logits, bbox, rois, roi_counts, windows, std_dev, image_hei
                                          float(image_width), float(min_confidence), dets.data_ptr(),
                                          nms_cls.data_ptr(), cls.data_ptr(), _stream()))
     return dets, nms_cls, cls
-
-
-__all__ += ["detection_decode"]
 
 
 @_on_device
@@ -1068,9 +1032,6 @@ def detection_select(dets, nms_class_ids, class_ids, keep, keep_counts, max_inst
     return ids, scores, boxes, rois, counts
 
 
-__all__ += ["topk_desc", "proposal_select", "detection_select"]
-
-
 @_on_device
 def deconv2x2(x: torch.Tensor, w, bias4: torch.Tensor, activation: int = 0, products: int = 0) -> torch.Tensor:
     """2x2 stride-2 transposed conv + bias + activation (Mask.forward's deconv, model.py:864,906-912) as one GEMM
@@ -1083,33 +1044,27 @@ def deconv2x2(x: torch.Tensor, w, bias4: torch.Tensor, activation: int = 0, prod
     cout = w0.size(0) // 4
     assert w0.size(3) == cin and bias4.numel() == 4 * cout
     y = torch.empty(b, 2 * h, 2 * wd, cout, dtype=x.dtype, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+
+    def book():
+        m = b * h * wd
+        return (2.0 * m * cin * 4 * cout, (m, 4 * cout, cin),
+                x.element_size() * (x.numel() + y.numel()) + (4 if products == 0 else 2 * (2 if products == 3 else 1)) * w0.numel(),
+                "direct" if products == 0 else "f16")
     if products == 0:
         assert w.dtype == torch.float32 and w.is_contiguous()
-        check(lib.mrcnn_deconv2x2_bias_act_nhwc_f32(x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout,
-                                                    bias4.data_ptr(), int(activation), y.data_ptr(), _stream()))
+        _launch(lib.mrcnn_deconv2x2_bias_act_nhwc_f32,
+                (x.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, bias4.data_ptr(), int(activation), y.data_ptr(), _stream()), book)
     elif x.dtype == torch.float16:   # fp16 activations: plain-fp16 mode only
         assert products == 1
-        check(lib.mrcnn_deconv2x2_bias_act_nhwc_f16io(x.data_ptr(), b, h, wd, cin, w[0].data_ptr(), cout, bias4.data_ptr(),
-                                                      int(activation), y.data_ptr(), _stream()))
+        _launch(lib.mrcnn_deconv2x2_bias_act_nhwc_f16io,
+                (x.data_ptr(), b, h, wd, cin, w[0].data_ptr(), cout, bias4.data_ptr(), int(activation), y.data_ptr(), _stream()),
+                book)
     else:
         w_hi, w_lo = w
-        check(lib.mrcnn_deconv2x2_bias_act_nhwc_f16mfma(x.data_ptr(), b, h, wd, cin, w_hi.data_ptr(), _ptr(w_lo),
-                                                        cout, bias4.data_ptr(), int(activation), int(products),
-                                                        y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
-        m = b * h * wd
-        prof.append((e0, e1, 2.0 * m * cin * 4 * cout, (m, 4 * cout, cin),
-                     x.element_size() * (x.numel() + y.numel()) + (4 if products == 0 else 2 * (2 if products == 3 else 1)) * w0.numel(),
-                     "direct" if products == 0 else "f16"))
+        _launch(lib.mrcnn_deconv2x2_bias_act_nhwc_f16mfma,
+                (x.data_ptr(), b, h, wd, cin, w_hi.data_ptr(), _ptr(w_lo), cout, bias4.data_ptr(), int(activation), int(products),
+                 y.data_ptr(), _stream()), book)
     return y
-
-
-__all__ += ["deconv2x2"]
 
 
 HAVE_ABLATIONS = hasattr(lib, "mrcnn_rpn_level_fused_f32")   # an MRCNN_ABLATIONS build of the library is loaded
@@ -1130,23 +1085,15 @@ def rpn_level_fused(x, w_shared, b_shared, w_head32, b_head, head_n: int = 18) -
     ws_bytes = int(lib.mrcnn_rpn_level_workspace_bytes(b, h, wd, cout, head_n))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     y = torch.empty(b, h, wd, head_n, dtype=torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_rpn_level_fused_f32(x.data_ptr(), b, h, wd, cin, w_shared.data_ptr(), cout, _ptr(b_shared),
-                                        w_head32.data_ptr(), _ptr(b_head), int(head_n), ws.data_ptr(), ws_bytes,
-                                        y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m = b * h * wd
         flops = 2.0 * m * (9 * cin * cout + cout * head_n)  # shared 3x3 conv + both 1x1 heads
-        prof.append((e0, e1, flops, (m, cout, 9 * cin),
-                     4 * (x.numel() + w_shared.numel() + cout * head_n + y.numel()), "rpn_fused"))
+        return flops, (m, cout, 9 * cin), 4 * (x.numel() + w_shared.numel() + cout * head_n + y.numel()), "rpn_fused"
+    _launch(lib.mrcnn_rpn_level_fused_f32,
+            (x.data_ptr(), b, h, wd, cin, w_shared.data_ptr(), cout, _ptr(b_shared), w_head32.data_ptr(), _ptr(b_head),
+             int(head_n), ws.data_ptr(), ws_bytes, y.data_ptr(), _stream()), book)
     return y
-
-
-__all__ += ["rpn_level_fused"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1309,20 +1256,16 @@ def conv3x3_winograd(x: torch.Tensor, u: torch.Tensor, scale, shift, relu: bool 
     if layout == 0:
         nbytes = int(lib.mrcnn_conv3x3_winograd_workspace_bytes(b, h, w, cin))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv3x3_winograd_f32(x.data_ptr(), layout, b, h, w, cin, u.data_ptr(), cout, _ptr(scale),
-                                         _ptr(shift), 1 if relu else 0, _ptr(y), _ptr(yk), _ptr(ws), nbytes, _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * h * w, 9 * (algo_cin or cin)
         # FLOPs are the algorithmic ones of the convolution (2*M*N*K), as for the direct kernel — not the reduced
         # multiply count Winograd actually executes
-        prof.append((e0, e1, 2.0 * m * cout * k, (m, cout, k),
-                     4.0 * (m * cin + m * cout * (2 if out == "both" else 1) + cout * k),
-                     "winograd_spatial" if int(lib.mrcnn_conv3x3_winograd_heads_tile_mode(h, w)) == 2 else "winograd"))
+        return (2.0 * m * cout * k, (m, cout, k), 4.0 * (m * cin + m * cout * (2 if out == "both" else 1) + cout * k),
+                "winograd_spatial" if int(lib.mrcnn_conv3x3_winograd_heads_tile_mode(h, w)) == 2 else "winograd")
+    _launch(lib.mrcnn_conv3x3_winograd_f32,
+            (x.data_ptr(), layout, b, h, w, cin, u.data_ptr(), cout, _ptr(scale), _ptr(shift), 1 if relu else 0, _ptr(y), _ptr(yk),
+             _ptr(ws), nbytes, _stream()), book)
     return y if out == "nhwc" else yk if out == "kblocked" else (y, yk)
 
 
@@ -1359,18 +1302,14 @@ def conv3x3_winograd4(x_kblocked: torch.Tensor, u4: torch.Tensor, scale, shift, 
     assert u4.size(0) * 4 == cin and conv3x3_winograd4_supported(h, w, cin, cout, b), (b, h, w, cin, cout)
     y = torch.empty(b, h, w, cout, dtype=torch.float32, device=x_kblocked.device) if out != "kblocked" else None
     yk = torch.empty(cout // 8, b, h, w, 8, dtype=torch.float32, device=x_kblocked.device) if out != "nhwc" else None
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv3x3_winograd4_f32(x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), cout, _ptr(scale),
-                                          _ptr(shift), 1 if relu else 0, _ptr(y), _ptr(yk), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * h * w, 9 * (algo_cin or cin)
-        prof.append((e0, e1, 2.0 * m * cout * k, (m, cout, k),
-                     4.0 * (m * cin + m * cout * (2 if out == "both" else 1) + 4 * cout * k), "winograd4",
-                     2.0 * m * cout * k / 4.0))
+        return (2.0 * m * cout * k, (m, cout, k), 4.0 * (m * cin + m * cout * (2 if out == "both" else 1) + 4 * cout * k),
+                "winograd4", 2.0 * m * cout * k / 4.0)
+    _launch(lib.mrcnn_conv3x3_winograd4_f32,
+            (x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), cout, _ptr(scale), _ptr(shift), 1 if relu else 0, _ptr(y),
+             _ptr(yk), _stream()), book)
     return y if out == "nhwc" else yk if out == "kblocked" else (y, yk)
 
 
@@ -1389,19 +1328,15 @@ def conv3x3_winograd4_conv3(x_kblocked: torch.Tensor, u4: torch.Tensor, scale, s
     assert w3.is_contiguous() and w3.numel() == c3 * 64 and c3 % 32 == 0
     assert residual.is_contiguous() and tuple(residual.shape) == (b, h, w, c3) and residual.dtype == torch.float32
     y = torch.empty(b, h, w, c3, dtype=torch.float32, device=x_kblocked.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv3x3_winograd4_conv3_f32(x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), _ptr(scale), _ptr(shift),
-                                                w3.data_ptr(), c3, _ptr(scale3), _ptr(shift3), residual.data_ptr(),
-                                                y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * h * w, 9 * (algo_cin or cin)
         algo = 2.0 * m * (64 * k + 64 * c3)
-        prof.append((e0, e1, algo, (m, c3, k + 64), 4.0 * (m * cin + 2 * m * c3 + 4 * 64 * k + 64 * c3), "winograd4",
-                     2.0 * m * (64 * k / 4.0 + 64 * c3)))
+        return (algo, (m, c3, k + 64), 4.0 * (m * cin + 2 * m * c3 + 4 * 64 * k + 64 * c3), "winograd4",
+                2.0 * m * (64 * k / 4.0 + 64 * c3))
+    _launch(lib.mrcnn_conv3x3_winograd4_conv3_f32,
+            (x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), _ptr(scale), _ptr(shift), w3.data_ptr(), c3, _ptr(scale3),
+             _ptr(shift3), residual.data_ptr(), y.data_ptr(), _stream()), book)
     return y
 
 
@@ -1418,18 +1353,14 @@ def conv3x3_winograd4_heads(x_kblocked: torch.Tensor, u4: torch.Tensor, scale, s
     assert w_head32.is_contiguous() and tuple(w_head32.shape) == (32, cout)
     rows = int(lib.mrcnn_conv3x3_winograd4_heads_rows(b, h, w))
     part = torch.empty(rows, 32, dtype=torch.float32, device=x_kblocked.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_conv3x3_winograd4_heads_f32(x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), cout, _ptr(scale),
-                                                _ptr(shift), 1 if relu else 0, w_head32.data_ptr(), part.data_ptr(),
-                                                _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * h * w, 9 * (algo_cin or cin)
-        prof.append((e0, e1, 2.0 * m * cout * (k + 18), (m, cout, k), 4.0 * (m * cin + part.numel() + 4 * cout * k),
-                     "winograd4", 2.0 * m * cout * (k / 4.0 + 32)))
+        return (2.0 * m * cout * (k + 18), (m, cout, k), 4.0 * (m * cin + part.numel() + 4 * cout * k), "winograd4",
+                2.0 * m * cout * (k / 4.0 + 32))
+    _launch(lib.mrcnn_conv3x3_winograd4_heads_f32,
+            (x_kblocked.data_ptr(), b, h, w, cin, u4.data_ptr(), cout, _ptr(scale), _ptr(shift), 1 if relu else 0,
+             w_head32.data_ptr(), part.data_ptr(), _stream()), book)
     return HeadSums(part, b, h, w, 3)
 
 
@@ -1447,40 +1378,39 @@ def stem_conv(x: torch.Tensor, w: torch.Tensor, scale, shift, relu: bool = True,
         b, h, wd, _ = x.shape
     assert nchw or not out_f16, "the fp16-output form reads the NCHW image"
     y = torch.empty(b, h // 2, wd // 2, 64, dtype=torch.float16 if out_f16 else torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     fn = lib.mrcnn_stem_conv7x7_s2_nchw_f16out if out_f16 else \
         lib.mrcnn_stem_conv7x7_s2_nchw_f32 if nchw else lib.mrcnn_stem_conv7x7_s2_nhwc_f32
-    check(fn(x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), 1 if relu else 0, y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = y.numel() // 64, 49 * (algo_cin or 4)
-        prof.append((e0, e1, 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + w.numel()) + y.numel() * y.element_size(), "stem"))
+        return 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + w.numel()) + y.numel() * y.element_size(), "stem"
+    _launch(fn, (x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), 1 if relu else 0, y.data_ptr(), _stream()), book)
     return y
+
+
+def _check_stem_pool(x, w, scale, shift):
+    """What both stem + max-pool forms take: x the molded NCHW image [B,3,H,W] fp32 with H and W multiples of 4, w OHWI
+    [64,7,7,4] fp32. → (B, H, W)."""
+    _need_gpu(x, w, scale, shift)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.size(1) == 3
+    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (64, 7, 7, 4)
+    b, _, h, wd = x.shape
+    assert h % 4 == 0 and wd % 4 == 0
+    return b, h, wd
 
 
 @_on_device
 def stem_pool_f16(x: torch.Tensor, w: torch.Tensor, scale, shift, algo_cin: int | None = None) -> torch.Tensor:
     """The "f16" mode's stem + max-pool in one launch on the fp16 MFMA (model.py:223-229): x the molded NCHW image [B,3,H,W]
     fp32, w OHWI [64,7,7,4] fp32 → fp16 NHWC [B, ceil(H/4), ceil(W/4), 64]."""
-    _need_gpu(x, w, scale, shift)
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.size(1) == 3
-    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (64, 7, 7, 4)
-    b, _, h, wd = x.shape
-    assert h % 4 == 0 and wd % 4 == 0
-    poh, pow_ = h // 4, wd // 4
-    y = torch.empty(b, poh, pow_, 64, dtype=torch.float16, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_stem_conv7x7_s2_pool_f16(x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+    b, h, wd = _check_stem_pool(x, w, scale, shift)
+    y = torch.empty(b, h // 4, wd // 4, 64, dtype=torch.float16, device=x.device)
+
+    def book():
         m, k = b * (h // 2) * (wd // 2), 49 * (algo_cin or 4)
-        prof.append((e0, e1, 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + w.numel()) + y.numel() * 2, "stem"))
+        return 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + w.numel()) + y.numel() * 2, "stem"
+    _launch(lib.mrcnn_stem_conv7x7_s2_pool_f16,
+            (x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), y.data_ptr(), _stream()), book)
     return y
 
 
@@ -1488,24 +1418,16 @@ def stem_pool_f16(x: torch.Tensor, w: torch.Tensor, scale, shift, algo_cin: int 
 def stem_pool_f32(x: torch.Tensor, w: torch.Tensor, scale, shift, algo_cin: int | None = None) -> torch.Tensor:
     """The exact-fp32 stem + max-pool in one launch (model.py:223-229; csrc/stem.hip: stem7x7_s2_pool_f32): x the molded NCHW
     image [B,3,H,W] fp32 (H, W multiples of 4), w OHWI [64,7,7,4] fp32 (channel 3 zero) → fp32 NHWC [B, H/4, W/4, 64]."""
-    _need_gpu(x, w, scale, shift)
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.size(1) == 3
-    assert w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (64, 7, 7, 4)
-    b, _, h, wd = x.shape
-    assert h % 4 == 0 and wd % 4 == 0
+    b, h, wd = _check_stem_pool(x, w, scale, shift)
     assert b * h * wd < (1 << 27), "stem_pool_f32: B*H*W < 2^27 pixels (32-bit byte offsets of the fp32 output)"
     y = torch.empty(b, h // 4, wd // 4, 64, dtype=torch.float32, device=x.device)
-    prof = CONV_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.mrcnn_stem_conv7x7_s2_pool_f32(x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), y.data_ptr(), _stream()))
-    if prof is not None:
-        e1.record()
+
+    def book():
         m, k = b * (h // 2) * (wd // 2), 49 * (algo_cin or 3)
         # executed: 77 MFMAs of K = 2 per 32 x 32 block (k = 22 per filter row) on 15 x 33 conv pixels per 7 x 16 pooled ones,
         # padded to 512 GEMM rows
         tiles = b * -(-(h // 4) // 7) * -(-(wd // 4) // 16)
-        prof.append((e0, e1, 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + 64 * 147 + y.numel()), "stem",
-                     2.0 * tiles * 512 * 64 * 154))
+        return 2.0 * m * 64 * k, (m, 64, k), 4.0 * (x.numel() + 64 * 147 + y.numel()), "stem", 2.0 * tiles * 512 * 64 * 154
+    _launch(lib.mrcnn_stem_conv7x7_s2_pool_f32,
+            (x.data_ptr(), b, h, wd, w.data_ptr(), _ptr(scale), _ptr(shift), y.data_ptr(), _stream()), book)
     return y

@@ -18,23 +18,65 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/maskrcnn_hip.h but not exported"
-    assert set(_lib._SIGS) == set(names), "ctypes table and header disagree"
+    # the bindings come from header_prototypes(): declared_symbols() is an independent regex, so equal name sets mean the
+    # parser dropped no prototype, and every one of them carries its ctypes signature on the loaded library
+    protos = _lib.header_prototypes()
+    assert set(protos) == set(names), "the prototype parser and the header's declared names disagree"
+    for n, (res, args) in protos.items():
+        fn = getattr(_lib.lib, n)
+        assert fn.restype == res and list(fn.argtypes) == args, f"{n} is not bound with the header's signature"
     assert _lib.lib.mrcnn_abi_version() == _lib.header_abi_version() >= 2
     assert _lib.lib.mrcnn_arch() == b"gfx950"
 
 
-def test_ctypes_table_matches_header_prototypes():
-    """_SIGS is a hand-kept copy of the header: argument counts and types are cross-checked against the prototypes
-    (a mismatch would pass wrong-width arguments to a kernel launch)."""
+def test_header_parser_yields_the_hand_written_signatures():
+    """The ctypes signatures are parsed from the header (a wrong one would pass wrong-width arguments to a kernel launch). These
+    are written out by hand, one entry point or more for every category the parser distinguishes: a const char* / size_t /
+    int64_t return, a (void) argument list, int64_t / float / size_t scalars, mrcnn_stream_t, plain pointers, host arrays of
+    pointers (const float* const fm[4]) and host arrays of int32_t, float and double."""
     from maskrcnn_amd import _lib
+    c_int, c_i32, c_i64, c_f32, c_vp, c_size = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
+                                                ctypes.c_size_t)
+    P = ctypes.POINTER
+    want = {
+        "mrcnn_last_error": (ctypes.c_char_p, []),
+        "mrcnn_nms_max_boxes": (c_i64, []),
+        "mrcnn_nms_workspace_bytes": (c_size, [c_i32, c_i64]),
+        "mrcnn_nms_batched_f32": (c_int, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                          c_f32, c_vp, c_vp, c_vp, c_size, c_vp]),
+        "mrcnn_roi_align_pyramid_counted_f32": (c_int, [P(c_vp), P(c_i32), P(c_i32),
+                                                        c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_vp,
+                                                        c_i32, c_vp, c_vp]),
+        "mrcnn_proposal_decode_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                              P(c_f32), c_f32, c_f32, c_vp, c_vp]),
+        "mrcnn_mold_images_u8": (c_int, [c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                         P(ctypes.c_double), c_vp, c_vp, c_size, c_vp]),
+        "mrcnn_bottleneck_forward_f32": (c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, P(c_vp), c_i32,
+                                                 c_i32, c_vp, c_size, c_vp, c_vp]),
+    }
     protos = _lib.header_prototypes()
-    assert set(protos) == set(_lib._SIGS)
-    for name, (res, args) in _lib._SIGS.items():
+    for name, (res, args) in want.items():
         hres, hargs = protos[name]
         assert res == hres, f"{name}: return type {res} vs header {hres}"
         assert len(args) == len(hargs), f"{name}: {len(args)} arguments vs {len(hargs)} in the header"
         for i, (a, h) in enumerate(zip(args, hargs)):
-            assert a == h, f"{name}: argument {i} is {a} in _SIGS, {h} in the header"
+            assert a == h, f"{name}: argument {i} is {a} by hand, {h} from the header"
+    ablations = _lib.header_prototypes(_lib.ABLATIONS_HEADER)
+    assert sorted(ablations) == ["mrcnn_rpn_level_fused_f32", "mrcnn_rpn_level_workspace_bytes"]
+    assert ablations["mrcnn_rpn_level_workspace_bytes"] == (c_size, [c_i32] * 5)
+
+
+def test_unknown_type_in_the_header_is_an_import_error(tmp_path, monkeypatch):
+    """A prototype whose type the parser has no ctypes type for must stop the import and name the prototype (it was a bare
+    KeyError): binding it with a guessed width is how a kernel launch gets wrong arguments."""
+    from maskrcnn_amd import _lib
+    fake = tmp_path / "maskrcnn_hip.h"
+    fake.write_text(open(_lib.HEADER).read() + "\nint mrcnn_made_up_entry(const float* x, uint8_t flag, mrcnn_stream_t stream);\n")
+    monkeypatch.setattr(_lib, "HEADER", str(fake))
+    with pytest.raises(ImportError, match=r"uint8_t.*mrcnn_made_up_entry\(const float\* x, uint8_t flag"):
+        _lib._load()
+    with pytest.raises(ImportError, match="mrcnn_made_up_entry"):
+        _lib.header_prototypes(str(fake))
 
 
 def test_stale_library_is_rejected(tmp_path, monkeypatch):
