@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 17
+#define MRCNN_ABI_VERSION 18
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -529,6 +529,27 @@ int mrcnn_paste_masks_u8(const float* masks, int64_t stride_n, int64_t stride_y,
                          int32_t n, int32_t mask_h, int32_t mask_w, int32_t num_classes, const int64_t* class_ids,
                          const float* boxes, int32_t height, int32_t width, int32_t on_value, uint8_t* out,
                          mrcnn_stream_t stream);
+/* COCO run-length encoding of n single-channel 8-bit masks — replaces maskUtils.encode(np.asfortranarray(mask)) per
+ * detection in build_coco_results (coco.py:40-60): rleEncode, rleToString, rleArea and rleToBbox of
+ * cocoapi/common/maskApi.c applied to the mask binarised as byte > threshold (0: the 0/1 and 0/255 masks of
+ * mrcnn_paste_masks_u8; 127: the grey levels decode_masks returns, the full_masks threshold of data.py:308).
+ *   masks   mask i at masks + i*image_stride, rows row_stride bytes apart (>= width), pixels contiguous: a cropped view
+ *           needs no copy. Pixels are visited in column-major order j = x*height + y; counts = diff([0, transitions.., H*W]).
+ *   num_runs      int32 [n]               the true number of runs, also beyond capacity
+ *   counts        uint32 [n][capacity]    run lengths (off run first: a mask whose first pixel is on starts with 0); may be NULL
+ *   strings       uint8 [n][6*capacity]   rleToString's characters, no terminator; may be NULL
+ *   string_bytes  int32 [n]               length of the string
+ *   areas         int32 [n]               on pixels;   bboxes int32 [n][4]  tight (x, y, w, h), zeros for an empty mask
+ * A mask with more runs than capacity: num_runs, areas and bboxes are exact, string_bytes is 0, and its counts and strings
+ * rows are not written at all; the other masks of the call are unaffected. Nothing is written past a row's capacity.
+ * Fixed capacity per mask: no mask depends on another, no atomics decide a position (same bits from run to run), no host sync.
+ * 1 <= height, width <= 16384; n <= 65535 (0: nothing is launched); threshold in [0,254]; capacity >= 1.
+ * workspace: mrcnn_rle_workspace_bytes(n, height, width) bytes of device memory, 16-byte aligned. */
+size_t mrcnn_rle_workspace_bytes(int32_t n, int32_t height, int32_t width);
+int mrcnn_rle_encode_u8(const uint8_t* masks, int64_t image_stride, int64_t row_stride, int32_t n, int32_t height,
+                        int32_t width, int32_t threshold, int32_t capacity, int32_t* num_runs, uint32_t* counts,
+                        uint8_t* strings, int32_t* string_bytes, int32_t* areas, int32_t* bboxes, void* workspace,
+                        size_t workspace_bytes, mrcnn_stream_t stream);
 
 /* RPN conv_shared + both 1x1 heads in one launch on the Winograd kernel (RPN.forward, model.py:605-607,624-641):
  * relu(conv3x3_same(x) * scale + shift) is never stored — each 64-channel output tile is transposed through LDS and

@@ -45,6 +45,7 @@ SOURCES = {
     "misc.hip": ["-ffp-contract=off"],
     "select.hip": ["-ffp-contract=off"],
     "image.hip": ["-ffp-contract=off"],   # Pillow's coefficient arithmetic, operation by operation in fp64
+    "rle.hip": [],                        # COCO RLE of the detection masks: integer work only
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-fast-math",
           "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -123,3 +123,91 @@ def decode_masks(masks_l8: torch.Tensor, scale, window) -> torch.Tensor:
     left = int(round((ww - cw) / 2.0))
     nh, nw = round(ch * 1.0 / scale), round(cw * 1.0 / scale)
     return ops.resize_bilinear_u8(masks_l8[:, top:top + ch, left:left + cw], nh, nw)
+
+
+# ---------------------------------------------------------------------------------------------- COCO RLE masks
+class RleMasks:
+    """N masks of one size as COCO run-length encodings on the device: what ops.rle_encode returns (row views of it for one
+    image of a detect() batch). size = (h, w); num_runs int32 [N], counts int32 [N,capacity], strings uint8 [N,6*capacity],
+    string_bytes int32 [N], areas int32 [N] (on pixels), bboxes int32 [N,4] (x, y, w, h)."""
+
+    def __init__(self, size, num_runs, counts, strings, string_bytes, areas, bboxes):
+        self.size = (int(size[0]), int(size[1]))
+        self.num_runs, self.counts, self.strings, self.string_bytes = num_runs, counts, strings, string_bytes
+        self.areas, self.bboxes = areas, bboxes
+
+    def __len__(self):
+        return int(self.num_runs.size(0))
+
+    @property
+    def capacity(self) -> int:
+        return int(self.counts.size(1))
+
+    def to_coco(self):
+        """→ [{"size": [h, w], "counts": bytes}] per mask: the dict maskUtils.encode returns (pycocotools' compressed RLE).
+        The string characters are gathered on the device and come to the host in ONE small copy together with the lengths
+        (a few KB per mask instead of h*w bytes). A mask that did not fit the encode's capacity has no string: RuntimeError."""
+        n = len(self)
+        if n == 0:
+            return []
+        live = torch.arange(self.strings.size(1), device=self.strings.device)[None, :] < self.string_bytes[:, None]
+        head = torch.stack([self.num_runs, self.string_bytes]).contiguous().view(torch.uint8).reshape(-1)
+        packed = torch.cat([head, self.strings[live]]).cpu().numpy()
+        runs, nbytes = packed[:8 * n].view(np.int32).reshape(2, n)
+        if (runs > self.capacity).any():
+            raise RuntimeError(f"RleMasks.to_coco: masks {np.nonzero(runs > self.capacity)[0].tolist()} have more runs than the "
+                               f"capacity {self.capacity} they were encoded with; encode again with capacity >= {int(runs.max())}")
+        ends = 8 * n + np.cumsum(nbytes, dtype=np.int64)
+        h, w = self.size
+        return [{"size": [h, w], "counts": packed[e - b:e].tobytes()} for b, e in zip(nbytes.tolist(), ends.tolist())]
+
+
+def rle_masks(masks: torch.Tensor, threshold: int = 0) -> RleMasks:
+    """ops.rle_encode of uint8 / bool masks [N,H,W] as an RleMasks in which every mask fits: when one has more runs than the
+    default capacity the batch is encoded once more with room for the longest (one host read of the run counts)."""
+    enc = ops.rle_encode(masks, threshold)
+    if masks.size(0):
+        longest = int(enc[0].max())
+        if longest > enc[1].size(1):
+            enc = ops.rle_encode(masks, threshold, capacity=longest)
+    return RleMasks(masks.shape[-2:], *enc)
+
+
+def rle_counts(obj) -> np.ndarray:
+    """The run lengths (uint32, off run first) of a COCO RLE given as a dict {"size", "counts"}, a compressed string
+    (bytes or str: rleFrString of cocoapi/common/maskApi.c) or a count list (returned as is). Pure numpy."""
+    if isinstance(obj, dict):
+        obj = obj["counts"]
+    if isinstance(obj, str):
+        obj = obj.encode("ascii")
+    if not isinstance(obj, (bytes, bytearray)):
+        return np.asarray(obj, dtype=np.uint32).reshape(-1)
+    cnts, x, k = [], 0, 0
+    for ch in obj:
+        c = ch - 48
+        x |= (c & 0x1f) << (5 * k)
+        k += 1
+        if c & 0x20:
+            continue
+        if c & 0x10:
+            x |= -1 << (5 * k)          # sign-extend: the string holds differences to the run two back
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x)
+        x, k = 0, 0
+    return np.asarray(cnts, dtype=np.uint32)
+
+
+def rle_decode(obj, size=None) -> np.ndarray:
+    """bool [h, w] mask of a COCO RLE: a dict {"size": [h, w], "counts": compressed bytes / str or a count list}, or raw
+    counts / a raw string with size=(h, w). Runs alternate off / on over the pixels in column-major order. Pure numpy."""
+    if isinstance(obj, dict):
+        size = obj["size"]
+    if size is None:
+        raise ValueError("rle_decode: size=(h, w) is needed with raw counts")
+    h, w = int(size[0]), int(size[1])
+    cnts = rle_counts(obj).astype(np.int64)
+    if int(cnts.sum()) != h * w:
+        raise ValueError(f"rle_decode: the runs cover {int(cnts.sum())} pixels, the mask has {h} x {w}")
+    flat = np.repeat(np.arange(cnts.size) & 1, cnts).astype(bool)
+    return flat.reshape(w, h).T

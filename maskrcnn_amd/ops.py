@@ -30,7 +30,8 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "conv_bn_act", "conv_bn_act_f16mfma", "split_f16", "same_pad", "maxpool", "nchw_to_nhwc", "nhwc_to_nchw",
            "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
-           "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused"]
+           "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
+           "rle_encode"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1198,6 +1199,56 @@ def paste_masks(masks: torch.Tensor, class_ids: torch.Tensor, boxes: torch.Tenso
     check(lib.mrcnn_paste_masks_u8(masks.data_ptr(), sn, sy, sx, sc, n, mh, mw, c, class_ids.data_ptr(),
                                    boxes.data_ptr(), height, width, 255 if as_l8 else 1, out.data_ptr(), _stream()))
     return out if as_l8 else out.view(torch.bool)
+
+
+# --------------------------------------------------------------------------------------------------
+# COCO run-length encoding of masks (csrc/rle.hip)
+# --------------------------------------------------------------------------------------------------
+def rle_default_capacity(height: int, width: int) -> int:
+    """Runs per mask rle_encode reserves when the caller names no capacity: four transitions per column (two blobs crossing
+    every column) and never less than 1024, never more than a mask can have (H*W + 1)."""
+    return min(height * width + 1, max(1024, 4 * width + 2))
+
+
+@_on_device
+def rle_encode(masks: torch.Tensor, threshold: int = 0, capacity: int | None = None):
+    """COCO RLE (maskUtils.encode: rleEncode + rleToString + rleArea + rleToBbox of cocoapi/common/maskApi.c) of uint8 or bool
+    masks [N,H,W] or [H,W] (N = 1) on the GPU; the last stride must be 1, image and row strides are free (a cropped view needs
+    no copy). A pixel is on iff its byte > threshold. → (num_runs int32 [N], counts int32 [N,capacity], strings uint8
+    [N,6*capacity], string_bytes int32 [N], areas int32 [N], bboxes int32 [N,4] (x, y, w, h)), all on the device, no host
+    synchronisation. A mask with more than `capacity` runs (default rle_default_capacity(H, W)) reports its true num_runs, area
+    and bbox, string_bytes 0, and its counts / strings rows are not written (they are uninitialised memory here)."""
+    _need_gpu(masks)
+    if masks.dtype not in (torch.uint8, torch.bool) or masks.dim() not in (2, 3):
+        raise RuntimeError(f"rle_encode: expected a uint8 or bool [N,H,W] or [H,W] tensor, got {masks.dtype} {tuple(masks.shape)}")
+    a = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    if a.dim() == 2:
+        a = a.unsqueeze(0)
+    n, h, w = a.shape
+    if w > 1 and a.stride(2) != 1:
+        raise RuntimeError(f"rle_encode: the last stride must be 1, got strides {tuple(masks.stride())}")
+    if capacity is None:
+        capacity = rle_default_capacity(h, w)
+    capacity = int(capacity)
+    image_stride = a.stride(0) if n > 1 else 0
+    row_stride = a.stride(1) if h > 1 else w
+    dev = a.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    num_runs, string_bytes, areas, bboxes = i32(n), i32(n), i32(n), i32(n, 4)
+    counts = i32(n, max(capacity, 0))
+    strings = torch.empty(n, 6 * max(capacity, 0), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.mrcnn_rle_workspace_bytes(n, h, w))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _launch(lib.mrcnn_rle_encode_u8,
+            (a.data_ptr(), image_stride, row_stride, n, h, w, int(threshold), capacity, num_runs.data_ptr(), counts.data_ptr(),
+             strings.data_ptr(), string_bytes.data_ptr(), areas.data_ptr(), bboxes.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (n, h, w), n * h * w, "rle_encode"))
+    return num_runs, counts, strings, string_bytes, areas, bboxes
+
+
+_LIB.define("rle_encode(Tensor masks, int threshold=0, int? capacity=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.impl("rle_encode", rle_encode, "CUDA")
+_LIB.impl("rle_encode", lambda masks, *a: _need_gpu(masks), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------

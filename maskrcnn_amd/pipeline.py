@@ -272,7 +272,7 @@ class MaskRCNNInference:
 
     # ---------------------------------------------------------------- images in, full-size masks out
     @torch.no_grad()
-    def detect(self, images, timings: dict | None = None):
+    def detect(self, images, timings: dict | None = None, mask_format: str = "dense"):
         """MaskRCNN.detect (model.py:1095-1138) for a list of RGB uint8 [h,w,3] images of any sizes: resize + pad +
         mean-subtract on the GPU (utils.resize_image, mold_image), predict, paste the masks at full size
         (datalib.full_masks, which the reference calls inside predict, model.py:1190) and map boxes and masks back
@@ -282,7 +282,16 @@ class MaskRCNNInference:
         scores [n], boxes [n,4], masks [n,h',w']) device tensors (views of the batch's tensors), or (None, None, None, None)
         when nothing was detected (model.py:1119-1120). The reference returns Python lists (:1132-1135); masks are bool when
         scale == 1 and uint8 grey levels otherwise, as in the reference.
+        mask_format="rle": the fourth element of each result is an imagelib.RleMasks over the image's detections instead —
+        COCO run-length encodings made on the device (ops.rle_encode, one call per group, after the paste and decode above),
+        what build_coco_results (coco.py:40-60) gets from maskUtils.encode; RleMasks.to_coco() brings them to the host. A pixel
+        is on iff it is nonzero when scale == 1 and iff its grey level is > 127 otherwise: the reference's own rleEncode breaks
+        a run at every VALUE change, so its RLE of a grey-level mask is not a binary mask at all, and 127 is the threshold
+        full_masks binarises with (data.py:308). Masks with more runs than ops.rle_default_capacity are encoded a second time
+        with room for the longest (one more small device-to-host copy, of the run counts). Anything else: ValueError.
         timings: filled with HIP-event milliseconds of the three stages (mold / predict / paste + decode) when given."""
+        if mask_format not in ("dense", "rle"):
+            raise ValueError(f"detect: mask_format must be 'dense' or 'rle', got {mask_format!r}")
         c = self.cfg
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
         if ev:
@@ -311,7 +320,7 @@ class MaskRCNNInference:
         m = det.masks.view(b * d, det.masks.size(2), det.masks.size(3), det.masks.size(4))
         ids_flat = det.class_ids.reshape(-1)
         m_cls = torch.gather(m, 3, ids_flat.clamp(min=0).view(-1, 1, 1, 1).expand(-1, m.size(1), m.size(2), 1)).squeeze(3)
-        groups = {}
+        groups, encoded = {}, []
         for i, n in enumerate(counts):
             if n > 0:
                 groups.setdefault((metas[i][0], tuple(windows_l[i])), []).append(i)
@@ -327,11 +336,25 @@ class MaskRCNNInference:
                 l8 = ops.paste_masks(g_masks, zeros, g_boxes, c.image_height, c.image_width, channels_last=True, as_l8=True)
                 pasted = imagelib.decode_masks(l8, scale, window)
                 out_boxes = imagelib.decode_boxes(g_boxes, scale, window)
+            if mask_format == "rle":
+                encoded.append((idx, out_boxes, pasted, 0 if scale == 1 else 127, ops.rle_encode(pasted, 0 if scale == 1 else 127)))
+                continue
             off = 0
             for i in idx:
                 n = counts[i]
                 results[i] = (det.class_ids[i, :n], det.scores[i, :n], out_boxes[off:off + n], pasted[off:off + n])
                 off += n
+        if encoded:
+            longest = torch.stack([e[4][0].max() for e in encoded]).tolist()        # one copy: the most runs of each group
+            for (idx, out_boxes, pasted, threshold, enc), runs in zip(encoded, longest):
+                if runs > enc[1].size(1):                                           # did not fit: once more, with room for all
+                    enc = ops.rle_encode(pasted, threshold, capacity=runs)
+                off = 0
+                for i in idx:
+                    n = counts[i]
+                    results[i] = (det.class_ids[i, :n], det.scores[i, :n], out_boxes[off:off + n],
+                                  imagelib.RleMasks(pasted.shape[1:], *[t[off:off + n] for t in enc]))
+                    off += n
         if ev:
             ev[3].record()
             torch.cuda.synchronize()

@@ -46,6 +46,8 @@ def main(argv=None):
     ap.add_argument("--backbone", default="resnet101", choices=["resnet50", "resnet101"], help="the reference hard-codes resnet101")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f32+f16x3", "f16"])
     ap.add_argument("--save", default=None, help="write class_ids / scores / boxes / masks to this .npz")
+    ap.add_argument("--coco-json", default=None, help="write COCO result records (image_id, category_id, bbox, score, "
+                                                     "segmentation as RLE: build_coco_results, coco.py:53-60) to this file")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("image", type=str, help="image file")
     args = ap.parse_args(argv)
@@ -85,6 +87,21 @@ def main(argv=None):
         else:
             np.savez_compressed(args.save, class_ids=class_ids.cpu().numpy(), scores=scores.cpu().numpy(),
                                 boxes=boxes.cpu().numpy(), masks=masks.cpu().numpy())
+    if args.coco_json:
+        import json
+        from maskrcnn_amd import image as imagelib
+        records = []
+        if class_ids is not None:
+            # the masks the lines above came with, encoded on the device (grey levels when the image was resized: > 127)
+            rle = imagelib.rle_masks(masks, 0 if masks.dtype == torch.bool else 127)
+            image_id = os.path.splitext(os.path.basename(args.image))[0]
+            for (j, _, b, s), seg in zip(out, rle.to_coco()):
+                y1, x1, y2, x2 = b
+                records.append({"image_id": image_id, "category_id": j,
+                                "bbox": [round(x1, 1), round(y1, 1), round(x2 - x1, 1), round(y2 - y1, 1)], "score": s,
+                                "segmentation": {"size": seg["size"], "counts": seg["counts"].decode("ascii")}})
+        with open(args.coco_json, "w") as fh:
+            json.dump(records, fh)
     return out
 
 
