@@ -306,7 +306,9 @@ int mrcnn_mask_tail_f16(const void* x_f16, int32_t rois, int32_t height, int32_t
  * mrcnn_proposal_decode_f32 — replaces the gather + boxes_refine + boxes_clamp_ of rpn_refine
  *   (model.py:1341-1358, data.py:124-148,86-92): for the top-k anchor indices `order` [batch][k] (int64) and
  *   their scores, dets [batch][k][5] = (clip(refine(anchor, delta*std_dev), [0,H]x[0,W]), score), in the
- *   reference's fp32 op order. */
+ *   reference's fp32 op order. The clip is fminf(fmaxf(v, lo), hi): a NaN coordinate (expf overflow: -inf + inf)
+ *   becomes the lower bound, where torch.clamp would keep the NaN — every output coordinate is finite and inside
+ *   the image, whatever the deltas, so NMS never sees a non-finite box. The score is copied as it is. */
 int mrcnn_rpn_scores_deltas_f32(const float* const heads[5], const int32_t level_hw[5], int32_t batch,
                                 float* scores, float* deltas, mrcnn_stream_t stream);
 /* The same with a per-level input form (level_mode[l]): 0 = NHWC [batch][H_l][W_l][18] head outputs as above;
@@ -331,7 +333,15 @@ int mrcnn_proposal_decode_f32(const float* anchors, const float* deltas, const i
  *   bbox_stride), rois [batch*P][4] normalised, windows [batch][4] pixels.
  *   dets [batch*P][5] = (y1,x1,y2,x2,score), class_ids int64 [batch*P] = arg-max class,
  *   nms_class_ids int32 [batch*P] = class for valid slots, a unique negative value otherwise (so that excluded
- *   slots neither suppress nor are suppressed in the class-aware NMS that follows). */
+ *   slots neither suppress nor are suppressed in the class-aware NMS that follows).
+ * A slot at or past roi_counts[image] gets the empty record: its dets row all zero, class_ids = 0, nms_class_ids =
+ * -(slot+1); nothing of its logits / bbox rows is read. A live row whose softmax is NaN gets the same record, and
+ * nothing of its bbox row is read: a row with a NaN logit or a +inf logit (the sum of exponentials is NaN), and a row
+ * without an ordered maximum (all NaN, or all -inf). F.softmax gives NaN probabilities there and torch.max of an all-NaN
+ * row index 0 (model.py:791,1407-1415): the reference drops the RoI as background. class_ids is therefore always in
+ * [0, num_classes). -inf logits beside a finite maximum are ordinary (probability 0).
+ * The window clip is fminf(fmaxf(v, lo), hi) as in mrcnn_proposal_decode_f32: a NaN coordinate becomes the window's
+ * lower bound (torch.clamp would keep it), so every box of a valid slot is finite and inside its window. */
 int mrcnn_detection_decode_f32(const float* logits, int64_t logit_stride, const float* bbox, int64_t bbox_stride,
                                const float* rois, const int32_t* roi_counts, const float* windows, int32_t batch,
                                int32_t rois_per_image, int32_t num_classes, const float std_dev[4],
@@ -456,7 +466,8 @@ int mrcnn_stem_conv7x7_s2_pool_f16(const float* x_nchw, int32_t batch, int32_t h
 
 /* ---- selection steps of the two refine stages (no library sort / top-k / gather in the step) --------------------
  * Total, deterministic order everywhere: descending score, ties by ascending index (ATen's sort, which the
- * reference calls at model.py:1346,1478, leaves ties unspecified).
+ * reference calls at model.py:1346,1478, leaves ties unspecified). Any NaN, of either sign, ranks first (above +inf), as
+ * in ATen's descending sort and in mrcnn_nms_*; NaNs tie with each other (ascending index). -0.0 ranks below +0.0.
  * mrcnn_topk_desc_f32 — replaces `scores.sort(descending=True)` + `[:pre_nms_limit]` of rpn_refine
  *   (model.py:1345-1350): scores [batch][n] -> top_scores [batch][k], order int64 [batch][k]. k <= 4096, k <= n;
  *   workspace >= mrcnn_topk_workspace_bytes(batch) bytes of device memory (contents irrelevant).

@@ -420,15 +420,17 @@ __global__ __launch_bounds__(256) void detection_decode(
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);  // RoI index in [0, B*P)
     if (r >= B * P) return;
     const int b = r / P, slot = r - b * P;
+    // the fixed, excluded record of a slot that yields no detection
+    auto write_empty = [&]() {
+        float* o = dets + static_cast<int64_t>(r) * 5;
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f;
+        class_ids[r] = 0;
+        nms_cls[r] = -(slot + 1);
+    };
     if (slot >= roi_counts[b]) {
         // no RoI in this slot (the reference's tensors simply end before it, model.py:1366-1374). Its logits / bbox rows may
-        // never have been written (the head skips row tiles of empty slots): nothing of them is read; a fixed, excluded record
-        if (lane == 0) {
-            float* o = dets + static_cast<int64_t>(r) * 5;
-            o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f;
-            class_ids[r] = 0;
-            nms_cls[r] = -(slot + 1);
-        }
+        // never have been written (the head skips row tiles of empty slots): nothing of them is read
+        if (lane == 0) write_empty();
         return;
     }
     const float* lg = logits + static_cast<int64_t>(r) * logit_stride;
@@ -450,6 +452,14 @@ __global__ __launch_bounds__(256) void detection_decode(
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
     if (lane != 0) return;
+    // A live row whose softmax is NaN (a NaN or +inf logit makes the sum NaN; all NaN or all -inf leaves no ordered
+    // maximum and besti at its sentinel): F.softmax gives an all-NaN row, torch.max of it index 0 = background
+    // (model.py:791,1407-1415), so the reference drops the RoI. Decoded like an empty slot; bbox is not read, and
+    // besti leaves this point inside [0, C).
+    if (static_cast<unsigned>(besti) >= static_cast<unsigned>(C) || sum != sum) {
+        write_empty();
+        return;
+    }
     const float score = 1.0f / sum;  // exp(0) / sum: the probability of the arg-max class
     const float* dl = bbox + static_cast<int64_t>(r) * bbox_stride + besti * 4;
     const float dy = dl[0] * s0, dx = dl[1] * s1, dh = dl[2] * s2, dw = dl[3] * s3;

@@ -15,10 +15,15 @@ constexpr int TOPK_THREADS = 1024;
 constexpr int TOPK_WAVES = TOPK_THREADS / 64;
 constexpr int SORT_CAP = 4096;  // elements the in-LDS bitonic sort handles (== mrcnn_nms_max_boxes())
 
-// float -> uint32 whose unsigned order is the float order (NaN with the sign bit clear sorts above +inf, as in ATen)
+// float -> uint32 whose unsigned order is the float order; NaN first, as in ATen's descending sort and in nms.hip's
+// make_key. -0 stays below +0 (unlike there): ties between them are the only place the two orders differ.
+// No float maps to key 0 any more (only the sign-set NaN 0xFFFFFFFF did), and a composite (key << 32 | ~index) of a
+// real element is non-zero anyway because index < 2^32 - 1: emit_topk's "0 = padding, sorts last" and
+// detection_select's "e != 0 = a candidate" hold.
 __device__ __forceinline__ uint32_t order_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    uint32_t u = __float_as_uint(f);
+    if (f != f) u = 0x7FC00000u;  // any NaN → +qNaN (largest)
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone float → uint
 }
 
 // Descending bitonic sort of n (a power of two) keys in LDS by all threads of the workgroup.

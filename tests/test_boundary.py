@@ -353,3 +353,73 @@ def test_entry_points_refuse_the_first_shape_past_their_limit():
     assert not lib.mrcnn_bottleneck_c2_f16_supported(16, 512, 512, 256, 64, 0)
     assert lib.mrcnn_mask_tail_f16_supported(16907, 14, 14, 256, 256, 81)
     assert not lib.mrcnn_mask_tail_f16_supported(16908, 14, 14, 256, 256, 81)
+
+
+def test_refine_stage_entry_points_refuse_bad_arguments():
+    """Argument validation of the selection / glue / RoIAlign entry points runs before any HIP call (dummy pointers, never
+    touched): each refusal with its message."""
+    from maskrcnn_amd import _lib
+    lib = _lib.lib
+    dp = ctypes.c_void_p(4096)
+    i5 = lambda *v: (ctypes.c_int32 * 5)(*v)
+    i4 = lambda *v: (ctypes.c_int32 * 4)(*v)
+
+    def refused(rc, text):
+        assert rc != 0 and text in lib.mrcnn_last_error(), (text, lib.mrcnn_last_error())
+
+    # top-k: k <= 4096, k <= n, n < 2^32 - 1 (indices are stored complemented in 32 bits, 0 is the padding key), workspace
+    need = lib.mrcnn_topk_workspace_bytes(2)
+    assert need > 0 and lib.mrcnn_topk_workspace_bytes(0) == 0
+    refused(lib.mrcnn_topk_desc_f32(dp, 2, 100000, 4097, dp, dp, dp, need, None), b"topk: k=4097 must be in [1, min(n, 4096)]")
+    refused(lib.mrcnn_topk_desc_f32(dp, 2, 10, 11, dp, dp, dp, need, None), b"topk: k=11 must be in [1, min(n, 4096)]")
+    refused(lib.mrcnn_topk_desc_f32(dp, 1, 2 ** 32 - 1, 1000, dp, dp, dp, need, None), b"topk: batch=1 n=4294967295")
+    refused(lib.mrcnn_topk_desc_f32(dp, 2, 100000, 1000, dp, dp, dp, need - 1, None),
+            b"topk: workspace too small (%d < %d)" % (need - 1, need))
+    refused(lib.mrcnn_topk_desc_f32(dp, 2, 100000, 1000, dp, dp, dp, lib.mrcnn_topk_workspace_bytes(1), None),
+            b"topk: workspace too small")
+    # proposal_select: keep[:proposal_count] of k boxes
+    refused(lib.mrcnn_proposal_select_f32(dp, dp, dp, 2, 1000, 1001, 1024.0, 1024.0, dp, dp, None),
+            b"proposal_select: batch=2 k=1000 proposal_count=1001 (1 <= proposal_count <= k)")
+    # rpn_scores_deltas: the head-sum forms need whole tiles and the bias they have not added yet
+    heads = (ctypes.c_void_p * 5)(*[4096] * 5)
+    bias = ctypes.c_void_p(8192)
+    for lvl, h, w, mode, b in ((0, 7, 8, 1, bias), (1, 8, 7, 2, bias), (2, 7, 8, 2, bias), (3, 6, 8, 3, bias), (4, 8, 6, 3, bias),
+                               (0, 8, 8, 1, None), (1, 8, 8, 2, None), (2, 8, 8, 3, None), (3, 8, 8, 4, None), (4, 8, 8, 5, bias)):
+        hs, ws, modes = [8] * 5, [8] * 5, [0] * 5
+        hs[lvl], ws[lvl], modes[lvl] = h, w, mode
+        refused(lib.mrcnn_rpn_scores_deltas_v2_f32(heads, i5(*hs), i5(*ws), i5(*modes), b, 1, dp, dp, None),
+                b"rpn_scores_deltas: level %d: mode must be 0 (NHWC heads), 1 or 2" % lvl)
+    # the pyramid RoIAlign: roi_counts excludes roi_batch; four channels per lane; pool
+    fm = (ctypes.c_void_p * 4)(*[4096] * 4)
+    call = lambda depth, roi_batch, counts, pool: lib.mrcnn_roi_align_pyramid_counted_f32(
+        fm, i4(32, 16, 8, 4), i4(32, 16, 8, 4), 2, depth, dp, roi_batch, 16, 8, counts, pool, 16384.0, dp, 0, None, None)
+    refused(call(256, dp, dp, 7), b"roi_align_pyramid: roi_counts needs rois_per_image (no roi_batch)")
+    refused(call(258, None, None, 7), b"roi_align_pyramid: depth=258 must be a multiple of 4")
+    refused(call(2, None, None, 7), b"roi_align_pyramid: depth=2 must be a multiple of 4")
+    refused(call(256, None, None, 0), b"roi_align_pyramid: pool=0")
+    refused(call(256, None, None, 1025), b"roi_align_pyramid: pool=1025")
+
+
+def test_detection_decode_argmax_sentinel_restated():
+    """The arg-max loop of detection_decode restated on the host (`v > best` from -inf with the index sentinel 0x7fffffff): a
+    row without an ordered maximum — all NaN, all -inf — leaves the sentinel in place, which the kernel used to multiply by 4
+    as a bbox offset and write out as a class id; a NaN or +inf logit beside ordinary ones leaves a valid index but a NaN
+    sum of exponentials. The rule the kernel now applies (index outside [0, C) or NaN sum: the empty-slot record) catches
+    exactly the rows whose softmax is NaN in torch (tests/test_gpu_refine_edges.py runs the kernel)."""
+    import numpy as np
+    nan, inf = float("nan"), float("inf")
+    rows = {"benign": [0.5, 2.0, -1.0], "some -inf": [-inf, 1.0, -inf], "one NaN": [0.5, nan, 1.0], "one +inf": [0.5, inf, 1.0],
+            "all NaN": [nan] * 3, "all -inf": [-inf] * 3}
+    for name, row in rows.items():
+        best, besti = np.float32(-inf), 0x7FFFFFFF
+        for c, v in enumerate(np.float32(row)):
+            if v > best:
+                best, besti = v, c
+        with np.errstate(invalid="ignore"):
+            total = np.float32(sum(np.exp(v - best) for v in np.float32(row)))
+        assert (besti == 0x7FFFFFFF) == (name in ("all NaN", "all -inf")), name
+        dropped = not 0 <= besti < len(row) or bool(np.isnan(total))
+        softmax_is_nan = bool(torch.isnan(torch.softmax(torch.tensor(row), 0)).all())
+        assert dropped == softmax_is_nan == (name not in ("benign", "some -inf")), name
+        if softmax_is_nan:
+            assert int(torch.max(torch.softmax(torch.tensor(row), 0), 0)[1]) == 0      # the reference: background
