@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 18
+#define MRCNN_ABI_VERSION 19
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -561,6 +561,53 @@ int mrcnn_rle_encode_u8(const uint8_t* masks, int64_t image_stride, int64_t row_
                         int32_t width, int32_t threshold, int32_t capacity, int32_t* num_runs, uint32_t* counts,
                         uint8_t* strings, int32_t* string_bytes, int32_t* areas, int32_t* bboxes, void* workspace,
                         size_t workspace_bytes, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * COCO evaluation — replaces the per-pair and per-group work of COCOeval.evaluate()
+ * (cocoapi/PythonAPI/pycocotools/cocoeval.py:122-162): maskUtils.iou (rleIou / bbIou of cocoapi/common/maskApi.c:77-120)
+ * and the matching loop of evaluateImg (cocoeval.py:251-300). csrc/cocoeval.hip.
+ *
+ * All three entry points are GROUPED: one call serves `groups` = K groups, a group being one (image, category).
+ *   dt_off   int32 [K+1]   group k owns detections   [dt_off[k], dt_off[k+1]) of the detection table (n_dt rows)
+ *   gt_off   int32 [K+1]   and ground truths          [gt_off[k], gt_off[k+1]) of the ground-truth table (n_gt rows)
+ *   out_off  int64 [K+1]   its IoU matrix starts at element out_off[k] (non-decreasing; out_off[k+1] - out_off[k] >= m*n)
+ * all in device memory. The matrix of a group of m detections and n ground truths is maskApi's o[g*m + d] (detection
+ * fastest: what _mask.pyx:239 reshapes to [m, n] in Fortran order). A group with m == 0 or n == 0 writes nothing, and so do
+ * elements of `out` (out_len doubles) that belong to no group's matrix. Offsets that point outside the tables read nothing.
+ *
+ * mrcnn_rle_iou_f64: rleIou on two run-list tables in the layout mrcnn_rle_encode_u8 writes — counts uint32 [n][capacity]
+ *   (off run first), num_runs int32 [n]. iscrowd uint8 [n_gt] or NULL. Every value has the bits of rleIou:
+ *   (double)i / (double)u with i the intersection pixels and u the union pixels (the detection's area where the ground truth
+ *   is a crowd; 1 when i == 0). A pair in which either mask has num_runs > capacity (the encoder wrote no counts for it)
+ *   gets -1, the reference's "cannot compare" value; nothing is read past a row's capacity. Contract: both masks of a pair
+ *   cover the same pixel count (< 2^32) and have no zero-length runs other than a leading one.
+ *   workspace: mrcnn_rle_iou_workspace_bytes(n_dt, dt_capacity, n_gt, gt_capacity) bytes of device memory, 16-byte aligned.
+ * mrcnn_bbox_iou_f64: bbIou on float64 (x, y, w, h) boxes [n][4], operation by operation (no FMA contraction).
+ * mrcnn_coco_match: evaluateImg's matching for every group x area range x IoU threshold in one launch.
+ *   ious, ious_len        the matrices above (out / out_len of an IoU call with the same offsets)
+ *   dt_area  double [n_dt]; gt_area double [n_gt]; gt_iscrowd uint8 [n_gt] (the ground truth's `ignore`, cocoeval.py:109-110)
+ *   area_ranges double [A][2], thresholds double [T]: device memory, used as those very doubles
+ *   the detections of a group are already sorted by descending score (stable) and cut at maxDet
+ *   dt_match int32 [A][T][n_dt], gt_match int32 [A][T][n_gt]: the matched partner's 1-based position within the group in
+ *   INPUT order (0 = none); dt_ignore uint8 [A][T][n_dt]; gt_ignore uint8 [A][n_gt]. Every element that belongs to a group
+ *   is written. The ground truths are visited regular first, then ignored, each in input order (the stable argsort of
+ *   cocoeval.py:258); the host applies that permutation when it builds evalImgs.
+ * No atomics (same bits from run to run), no allocation, no host synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mrcnn_rle_iou_workspace_bytes(int32_t n_dt, int32_t dt_capacity, int32_t n_gt, int32_t gt_capacity);
+int mrcnn_rle_iou_f64(const int32_t* dt_num_runs, const uint32_t* dt_counts, int32_t n_dt, int32_t dt_capacity,
+                      const int32_t* gt_num_runs, const uint32_t* gt_counts, int32_t n_gt, int32_t gt_capacity,
+                      const uint8_t* iscrowd, const int32_t* dt_off, const int32_t* gt_off, const int64_t* out_off,
+                      int32_t groups, double* out, int64_t out_len, void* workspace, size_t workspace_bytes,
+                      mrcnn_stream_t stream);
+int mrcnn_bbox_iou_f64(const double* dt_boxes, int32_t n_dt, const double* gt_boxes, int32_t n_gt, const uint8_t* iscrowd,
+                       const int32_t* dt_off, const int32_t* gt_off, const int64_t* out_off, int32_t groups, double* out,
+                       int64_t out_len, mrcnn_stream_t stream);
+int mrcnn_coco_match(const double* ious, int64_t ious_len, const int32_t* dt_off, const int32_t* gt_off,
+                     const int64_t* out_off, int32_t groups, const double* dt_area, int32_t n_dt, const double* gt_area,
+                     const uint8_t* gt_iscrowd, int32_t n_gt, const double* area_ranges, int32_t num_ranges,
+                     const double* thresholds, int32_t num_thresholds, int32_t* dt_match, int32_t* gt_match,
+                     uint8_t* dt_ignore, uint8_t* gt_ignore, mrcnn_stream_t stream);
 
 /* RPN conv_shared + both 1x1 heads in one launch on the Winograd kernel (RPN.forward, model.py:605-607,624-641):
  * relu(conv3x3_same(x) * scale + shift) is never stored — each 64-channel output tile is transposed through LDS and

@@ -9,7 +9,12 @@ import ctypes
 import os
 import re
 
-PKG = os.path.dirname(os.path.abspath(__file__))
+# torch FIRST: its wheel carries its own libamdhip64, and the tensors this library works on are allocated by that runtime. Loaded
+# before torch (`python -m maskrcnn_amd.cocoeval`, `python -c "import maskrcnn_amd"`), libmaskrcnn_hip.so would bind the system's
+# copy instead — a second HIP runtime in the process, whose launches fail with "no ROCm-capable device is detected".
+import torch  # noqa: F401
+
+PKG =os.path.dirname(os.path.abspath(__file__))
 # MRCNN_LIB: load another build of the same library (an experiment / ablation build made by `build.py --variant NAME`,
 # which never overwrites the product file). Same ABI check, same no-fallback rule.
 LIB_PATH = os.environ.get("MRCNN_LIB") or os.path.join(PKG, "libmaskrcnn_hip.so")

@@ -46,6 +46,7 @@ SOURCES = {
     "select.hip": ["-ffp-contract=off"],
     "image.hip": ["-ffp-contract=off"],   # Pillow's coefficient arithmetic, operation by operation in fp64
     "rle.hip": [],                        # COCO RLE of the detection masks: integer work only
+    "cocoeval.hip": ["-ffp-contract=off"],   # bbIou's da+ga-i, i=w*h: separately rounded fp64, as the reference's plain C
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-fast-math",
           "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -1,0 +1,360 @@
+"""COCO detection evaluation (bbox / segm AP and AR) — the second half of `python coco.py evaluate` (coco.py:78-135):
+COCOeval(coco, coco_results, iou_type).evaluate() / accumulate() / summarize() of cocoapi/PythonAPI/pycocotools/cocoeval.py,
+without pycocotools.
+
+    ev = evaluate("instances_val.json", "out.json", iou_type="segm")     # out.json: predict.py --coco-json
+    print("\\n".join(ev.summary()))
+    python -m maskrcnn_amd.cocoeval GT.json RESULTS.json [--type segm|bbox]
+
+Where the work is done:
+    GPU   the IoU of every detection x ground truth of every (image, category) — ONE grouped ops.rle_iou / ops.bbox_iou call —
+          and the matching of evaluateImg for every group x area range x threshold — ONE grouped ops.coco_match call
+    host  loadRes / _prepare (grouping, the -score mergesort, the maxDets[-1] cut), and accumulate / summarize restated
+          operation by operation in numpy on the small arrays the two calls return.
+Every number equals the reference's bit for bit (tests/golden/cocoeval.npz). Out of scope: polygon segmentations (rleFrPoly),
+keypoints, useCats = 0.
+"""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import torch
+
+__all__ = ["Params", "CocoEval", "evaluate", "accumulate", "summarize", "load_results"]
+
+
+class Params:
+    """Params.setDetParams (cocoeval.py:503-512)."""
+
+    def __init__(self, iou_type: str = "segm"):
+        if iou_type not in ("segm", "bbox"):
+            raise ValueError(f"iou_type {iou_type!r}: 'segm' or 'bbox' (keypoints are out of scope)")
+        self.iouType = iou_type
+        self.imgIds, self.catIds = [], []
+        self.iouThrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        self.recThrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+        self.maxDets = [1, 10, 100]
+        self.areaRng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+        self.areaRngLbl = ["all", "small", "medium", "large"]
+        self.useCats = 1
+
+
+# ------------------------------------------------------------------------------------------------ accumulate / summarize
+def accumulate(eval_imgs, params: Params):
+    """COCOeval.accumulate (cocoeval.py:316-421) on eval_imgs — the list evaluate() builds, [K x A x I] entries (category
+    slowest), None or a dict with dtScores, dtMatches [T,D], dtIgnore [T,D], gtIgnore [G] — for the params it was built with.
+    → precision [T,R,K,A,M], recall [T,K,A,M], scores [T,R,K,A,M]."""
+    p = params
+    T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
+    I0 = len(p.imgIds)
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    scores = -np.ones((T, R, K, A, M))
+    for k in range(K):
+        Nk = k * A * I0
+        for a in range(A):
+            Na = a * I0
+            for m, maxDet in enumerate(p.maxDets):
+                E = [e for e in eval_imgs[Nk + Na:Nk + Na + I0] if e is not None]
+                if len(E) == 0:
+                    continue
+                dtScores = np.concatenate([e["dtScores"][0:maxDet] for e in E])
+                inds = np.argsort(-dtScores, kind="mergesort")
+                dtScoresSorted = dtScores[inds]
+                dtm = np.concatenate([e["dtMatches"][:, 0:maxDet] for e in E], axis=1)[:, inds]
+                dtIg = np.concatenate([e["dtIgnore"][:, 0:maxDet] for e in E], axis=1)[:, inds]
+                gtIg = np.concatenate([e["gtIgnore"] for e in E])
+                npig = np.count_nonzero(gtIg == 0)
+                if npig == 0:
+                    continue
+                tps = np.logical_and(dtm, np.logical_not(dtIg))
+                fps = np.logical_and(np.logical_not(dtm), np.logical_not(dtIg))
+                tp_sum = np.cumsum(tps, axis=1).astype(dtype=float)
+                fp_sum = np.cumsum(fps, axis=1).astype(dtype=float)
+                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                    nd = len(tp)
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    q = np.zeros((R,))
+                    ss = np.zeros((R,))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    # the reference's backward loop (pr[i-1] = pr[i] where larger) is a running maximum from the right
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    inds_r = np.searchsorted(rc, p.recThrs, side="left")
+                    ok = inds_r < nd      # its try / except stops at the first index past the end; they are non-decreasing
+                    q[ok] = pr[inds_r[ok]]
+                    ss[ok] = dtScoresSorted[inds_r[ok]]
+                    precision[t, :, k, a, m] = q
+                    scores[t, :, k, a, m] = ss
+    return precision, recall, scores
+
+
+def summarize(precision, recall, params: Params):
+    """COCOeval.summarize (_summarizeDets, cocoeval.py:423-473) → (stats float64 [12], the twelve lines it prints)."""
+    p = params
+    lines = []
+
+    def _summarize(ap=1, iouThr=None, areaRng="all", maxDets=100):
+        iStr = " {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}"
+        titleStr = "Average Precision" if ap == 1 else "Average Recall"
+        typeStr = "(AP)" if ap == 1 else "(AR)"
+        iouStr = "{:0.2f}:{:0.2f}".format(p.iouThrs[0], p.iouThrs[-1]) if iouThr is None else "{:0.2f}".format(iouThr)
+        aind = [i for i, aRng in enumerate(p.areaRngLbl) if aRng == areaRng]
+        mind = [i for i, mDet in enumerate(p.maxDets) if mDet == maxDets]
+        if ap == 1:
+            s = precision
+            if iouThr is not None:
+                s = s[np.where(iouThr == p.iouThrs)[0]]
+            s = s[:, :, :, aind, mind]
+        else:
+            s = recall
+            if iouThr is not None:
+                s = s[np.where(iouThr == p.iouThrs)[0]]
+            s = s[:, :, aind, mind]
+        mean_s = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+        lines.append(iStr.format(titleStr, typeStr, iouStr, areaRng, maxDets, mean_s))
+        return mean_s
+
+    stats = np.zeros((12,))
+    stats[0] = _summarize(1)
+    stats[1] = _summarize(1, iouThr=.5, maxDets=p.maxDets[2])
+    stats[2] = _summarize(1, iouThr=.75, maxDets=p.maxDets[2])
+    stats[3] = _summarize(1, areaRng="small", maxDets=p.maxDets[2])
+    stats[4] = _summarize(1, areaRng="medium", maxDets=p.maxDets[2])
+    stats[5] = _summarize(1, areaRng="large", maxDets=p.maxDets[2])
+    stats[6] = _summarize(0, maxDets=p.maxDets[0])
+    stats[7] = _summarize(0, maxDets=p.maxDets[1])
+    stats[8] = _summarize(0, maxDets=p.maxDets[2])
+    stats[9] = _summarize(0, areaRng="small", maxDets=p.maxDets[2])
+    stats[10] = _summarize(0, areaRng="medium", maxDets=p.maxDets[2])
+    stats[11] = _summarize(0, areaRng="large", maxDets=p.maxDets[2])
+    return stats, lines
+
+
+class CocoEval:
+    """What evaluate() returns: params, ious {(image_id, category_id): float64 [D,G] or []}, eval_imgs (COCOeval.evalImgs),
+    precision [T,R,K,A,M], recall [T,K,A,M], scores [T,R,K,A,M], stats [12]; summary() → the lines summarize() prints."""
+
+    def __init__(self, params, ious, eval_imgs):
+        self.params, self.ious, self.eval_imgs = params, ious, eval_imgs
+        self.precision, self.recall, self.scores = accumulate(eval_imgs, params)
+        self.stats, self._lines = summarize(self.precision, self.recall, params)
+
+    def summary(self):
+        return list(self._lines)
+
+
+# ------------------------------------------------------------------------------------------------ loadRes / _prepare
+def _rle_area_bbox(cnts: np.ndarray, h: int, w: int):
+    """rleArea and rleToBbox (maskApi.c:72-75, :133-147) of one run list → (area, [x, y, w, h] as floats)."""
+    area = int(cnts[1::2].astype(np.int64).sum())
+    m = (cnts.size // 2) * 2
+    if m == 0:
+        return area, [0.0, 0.0, 0.0, 0.0]
+    cc = np.cumsum(cnts[:m].astype(np.int64))
+    t = cc - (np.arange(m) % 2)
+    y = t % h
+    x = (t - y) // h
+    xs, xe, ys, ye = int(min(w, x.min())), int(x.max()), int(min(h, y.min())), int(y.max())
+    if (x[0::2] < x[1::2]).any():      # a run that crosses into another column spans every row
+        ys, ye = 0, h - 1
+    return area, [float(xs), float(ys), float(xe - xs + 1), float(ye - ys + 1)]
+
+
+def _is_polygon(seg) -> bool:
+    return isinstance(seg, (list, tuple))
+
+
+def _seg_size(seg):
+    if isinstance(seg, dict):
+        return int(seg["size"][0]), int(seg["size"][1])
+    return int(seg.shape[-2]), int(seg.shape[-1])      # a dense [h, w] mask
+
+
+def _seg_counts(seg, i: int, device) -> np.ndarray:
+    """Run lengths of one segmentation: an RLE dict (compressed string or count list), or a dense mask array, which is
+    encoded on the GPU (ops.rle_encode)."""
+    from . import image
+    if isinstance(seg, dict):
+        h, w = _seg_size(seg)
+        return image._checked_counts(seg, h, w, i)
+    if isinstance(seg, (np.ndarray, torch.Tensor)):
+        t = torch.as_tensor(np.ascontiguousarray(seg) if isinstance(seg, np.ndarray) else seg)
+        if t.dtype not in (torch.uint8, torch.bool):
+            t = t != 0
+        enc = image.rle_masks(t.to(device)[None])
+        return enc.counts[0, :int(enc.num_runs[0])].cpu().numpy().view(np.uint32)
+    raise TypeError(f"segmentation {i}: expected an RLE dict or a dense mask array, got {type(seg).__name__}")
+
+
+def load_results(results, iou_type: str):
+    """COCO.loadRes (pycocotools/coco.py:297-352) on a list of result records: id = i + 1, iscrowd = 0, and — decided by the
+    FIRST record, as there — area = w*h of the box where records carry a bbox, else the RLE's area and bbox = toBbox."""
+    if isinstance(results, str):
+        with open(results) as fh:
+            results = json.load(fh)
+    if not isinstance(results, list):
+        raise TypeError("results in not an array of objects")
+    anns = [dict(r) for r in results]
+    if not anns:
+        return anns
+    if "bbox" in anns[0] and not anns[0]["bbox"] == []:
+        for i, ann in enumerate(anns):
+            bb = ann["bbox"]
+            ann["area"] = bb[2] * bb[3]
+            ann["id"] = i + 1
+            ann["iscrowd"] = 0
+    elif "segmentation" in anns[0]:
+        for i, ann in enumerate(anns):
+            seg = ann["segmentation"]
+            if _is_polygon(seg):
+                raise NotImplementedError("polygon segmentations are out of scope (rleFrPoly is not implemented): give RLE")
+            h, w = _seg_size(seg)
+            from . import image
+            area, bbox = _rle_area_bbox(image.rle_counts(seg), h, w)
+            ann["area"] = np.uint32(area)
+            if "bbox" not in ann:
+                ann["bbox"] = np.array(bbox)
+            ann["id"] = i + 1
+            ann["iscrowd"] = 0
+    else:
+        raise ValueError("result records carry neither 'bbox' nor 'segmentation'")
+    return anns
+
+
+def evaluate(gt, results, iou_type: str = "segm", device="cuda:0") -> CocoEval:
+    """COCOeval(COCO(gt), COCO(gt).loadRes(results), iou_type) → evaluate(), accumulate(), summarize().
+    gt: a COCO dataset dict (images, annotations, categories) or its path; results: the list predict.py --coco-json writes, or
+    its path. Ground-truth segmentations (iou_type="segm"): compressed-string RLE, count-list RLE or a dense mask array;
+    polygons raise NotImplementedError. iou_type="bbox" never looks at segmentations."""
+    from . import image, ops
+    p = Params(iou_type)
+    if isinstance(gt, str):
+        with open(gt) as fh:
+            gt = json.load(fh)
+    img_ids = [img["id"] for img in gt["images"]]
+    p.imgIds = list(np.unique(img_ids))
+    p.catIds = list(np.unique([c["id"] for c in gt["categories"]]))
+    p.maxDets = sorted(p.maxDets)
+    dts_all = load_results(results, iou_type)
+    if not set(a["image_id"] for a in dts_all) <= set(img_ids):
+        raise ValueError("Results do not correspond to current coco set")
+
+    # _prepare (:85-120): group by (image, category), keeping the data set's / the result file's order within a group
+    in_imgs, in_cats = set(p.imgIds), set(p.catIds)
+    gts, dts = {}, {}
+    for ann in gt["annotations"]:
+        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
+            gts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
+    for ann in dts_all:
+        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
+            dts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
+    if iou_type == "segm":
+        for key, anns in gts.items():
+            for ann in anns:
+                if _is_polygon(ann["segmentation"]):
+                    raise NotImplementedError(
+                        f"annotation {ann.get('id')}: polygon segmentations are out of scope (rleFrPoly is not implemented); "
+                        "give RLE ground truth, or evaluate iou_type='bbox'")
+
+    # computeIoU's ordering (:174-177): -score mergesort, cut at maxDets[-1]
+    keys = [k for k in sorted(set(gts) | set(dts))]
+    max_det = p.maxDets[-1]
+    for key in keys:
+        d = dts.get(key, [])
+        inds = np.argsort([-x["score"] for x in d], kind="mergesort")
+        dts[key] = [d[i] for i in inds][:max_det]
+        gts.setdefault(key, [])
+    dt_flat = [x for key in keys for x in dts[key]]
+    gt_flat = [x for key in keys for x in gts[key]]
+    dt_n = np.array([len(dts[key]) for key in keys], dtype=np.int64)
+    gt_n = np.array([len(gts[key]) for key in keys], dtype=np.int64)
+    dt_off = np.concatenate([[0], np.cumsum(dt_n)])
+    gt_off = np.concatenate([[0], np.cumsum(gt_n)])
+    out_off = np.concatenate([[0], np.cumsum(dt_n * gt_n)])
+    K, N, M, out_len = len(keys), int(dt_off[-1]), int(gt_off[-1]), int(out_off[-1])
+    iscrowd = np.array([int(g["iscrowd"]) if "iscrowd" in g else 0 for g in gt_flat], dtype=np.uint8)
+    # gt['ignore'] = 'iscrowd' in gt and gt['iscrowd'] (:110)
+    gt_ignore_flag = np.array([1 if ("iscrowd" in g and g["iscrowd"]) else 0 for g in gt_flat], dtype=np.uint8)
+    dt_area = np.array([float(d["area"]) for d in dt_flat], dtype=np.float64)
+    gt_area = np.array([float(g["area"]) for g in gt_flat], dtype=np.float64)
+
+    dev = torch.device(device)
+    dev_of = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    T, A = len(p.iouThrs), len(p.areaRng)
+    if K:
+        offs = (dev_of(dt_off.astype(np.int32)), dev_of(gt_off.astype(np.int32)), dev_of(out_off.astype(np.int64)))
+        if iou_type == "segm":
+            rows_d = [_seg_counts(d["segmentation"], i, dev) for i, d in enumerate(dt_flat)]
+            rows_g = [_seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
+            for k, key in enumerate(keys):
+                sizes = {_seg_size(x["segmentation"]) for x in dts[key] + gts[key]}
+                if len(sizes) > 1:
+                    raise ValueError(f"image {key[0]}, category {key[1]}: masks of different sizes {sorted(sizes)}")
+            ious_dev = ops.rle_iou(image._pack_table(rows_d, dev), image._pack_table(rows_g, dev), dev_of(iscrowd), *offs,
+                                   out_len=out_len)
+        else:
+            boxes = lambda anns: np.array([[float(v) for v in x["bbox"]] for x in anns], dtype=np.float64).reshape(-1, 4)
+            ious_dev = ops.bbox_iou(dev_of(boxes(dt_flat)), dev_of(boxes(gt_flat)), dev_of(iscrowd), *offs, out_len=out_len)
+        match = ops.coco_match(ious_dev, *offs, dev_of(dt_area), dev_of(gt_area), dev_of(gt_ignore_flag),
+                               dev_of(np.array(p.areaRng, dtype=np.float64)), dev_of(np.asarray(p.iouThrs, dtype=np.float64)))
+        ious_flat = ious_dev.cpu().numpy()
+        dt_match, gt_match, dt_ignore, gt_ignore = [m.cpu().numpy() for m in match]
+    else:
+        ious_flat = np.zeros(0)
+        dt_match = gt_match = np.zeros((A, T, 0), np.int32)
+        dt_ignore, gt_ignore = np.zeros((A, T, 0), np.uint8), np.zeros((A, 0), np.uint8)
+
+    index = {key: k for k, key in enumerate(keys)}
+    ious = {}
+    for img in p.imgIds:
+        for cat in p.catIds:
+            k = index.get((img, cat))
+            if k is None or dt_n[k] == 0 or gt_n[k] == 0:
+                ious[img, cat] = []
+            else:
+                ious[img, cat] = ious_flat[out_off[k]:out_off[k + 1]].reshape(int(gt_n[k]), int(dt_n[k])).T
+
+    eval_imgs = []
+    for cat in p.catIds:
+        for a, rng in enumerate(p.areaRng):
+            for img in p.imgIds:
+                k = index.get((img, cat))
+                if k is None:
+                    eval_imgs.append(None)
+                    continue
+                d0, d1, g0, g1 = int(dt_off[k]), int(dt_off[k + 1]), int(gt_off[k]), int(gt_off[k + 1])
+                d, g = dts[img, cat], gts[img, cat]
+                gt_ig = gt_ignore[a, g0:g1]
+                gtind = np.argsort(gt_ig, kind="mergesort")            # regular first, ignored last (:258)
+                gt_ids = np.array([x["id"] for x in g], dtype=np.float64)
+                dt_ids = np.array([x["id"] for x in d], dtype=np.float64)
+                pos_d = dt_match[a, :, d0:d1]
+                dtm = np.where(pos_d > 0, gt_ids[np.maximum(pos_d, 1) - 1] if len(g) else 0.0, 0.0).reshape(T, d1 - d0)
+                pos_g = gt_match[a, :, g0:g1][:, gtind]
+                gtm = np.where(pos_g > 0, dt_ids[np.maximum(pos_g, 1) - 1] if len(d) else 0.0, 0.0).reshape(T, g1 - g0)
+                outside = np.array([x["area"] < rng[0] or x["area"] > rng[1] for x in d], dtype=bool).reshape(1, len(d))
+                dt_ig = np.logical_or(dt_ignore[a, :, d0:d1] != 0, np.logical_and(dtm == 0, np.repeat(outside, T, 0)))
+                eval_imgs.append({
+                    "image_id": img, "category_id": cat, "aRng": rng, "maxDet": max_det,
+                    "dtIds": [x["id"] for x in d], "gtIds": [g[i]["id"] for i in gtind],
+                    "dtMatches": dtm, "gtMatches": gtm, "dtScores": [x["score"] for x in d],
+                    "gtIgnore": gt_ig[gtind].astype(np.int64), "dtIgnore": dt_ig,
+                })
+    return CocoEval(p, ious, eval_imgs)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="COCO AP / AR of a result file (predict.py --coco-json) against ground truth")
+    ap.add_argument("gt", help="COCO annotation file (RLE segmentations for --type segm)")
+    ap.add_argument("results", help="COCO result records")
+    ap.add_argument("--type", default="segm", choices=("segm", "bbox"), dest="iou_type")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    print("\n".join(evaluate(args.gt, args.results, args.iou_type, args.device).summary()))
+
+
+if __name__ == "__main__":
+    main()

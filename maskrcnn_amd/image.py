@@ -161,6 +161,15 @@ class RleMasks:
         h, w = self.size
         return [{"size": [h, w], "counts": packed[e - b:e].tobytes()} for b, e in zip(nbytes.tolist(), ends.tolist())]
 
+    def iou(self, other, iscrowd=None) -> torch.Tensor:
+        """maskUtils.iou(self, other, iscrowd): float64 [len(self), len(other)] on the device, the bits of rleIou. `other` is an
+        RleMasks of the same size or (num_runs, counts) device tensors (rle_table); iscrowd uint8 [len(other)] or a list."""
+        if isinstance(other, RleMasks) and other.size != self.size:
+            raise ValueError(f"RleMasks.iou: masks of {self.size} against masks of {other.size}")
+        if iscrowd is not None and not isinstance(iscrowd, torch.Tensor):
+            iscrowd = torch.tensor(np.asarray(iscrowd, dtype=np.uint8), device=self.num_runs.device)
+        return ops.rle_iou(self, other, iscrowd)
+
 
 def rle_masks(masks: torch.Tensor, threshold: int = 0) -> RleMasks:
     """ops.rle_encode of uint8 / bool masks [N,H,W] as an RleMasks in which every mask fits: when one has more runs than the
@@ -196,6 +205,42 @@ def rle_counts(obj) -> np.ndarray:
         cnts.append(x)
         x, k = 0, 0
     return np.asarray(cnts, dtype=np.uint32)
+
+
+def _checked_counts(obj, h: int, w: int, i: int) -> np.ndarray:
+    """rle_counts(obj), checked against ops.rle_iou's contract on its inputs for an h x w mask (ValueError otherwise)."""
+    if isinstance(obj, dict) and [int(v) for v in obj["size"]] != [h, w]:
+        raise ValueError(f"rle_table: mask {i} is {list(obj['size'])}, the table is {[h, w]}")
+    cnts = rle_counts(obj)
+    if int(cnts.astype(np.int64).sum()) != h * w:
+        raise ValueError(f"rle_table: the runs of mask {i} cover {int(cnts.astype(np.int64).sum())} pixels, the mask has {h} x {w}")
+    if cnts.size > 1 and not cnts[1:].all():
+        raise ValueError(f"rle_table: mask {i} has an empty run after the first one")
+    return cnts
+
+
+def _pack_table(rows, device, capacity=None):
+    """Run-length rows (uint32 arrays) → (num_runs int32 [N], counts int32 [N,capacity]) on the device, one copy each."""
+    longest = max([r.size for r in rows], default=0)
+    if capacity is None:
+        capacity = max(1, longest)
+    if int(capacity) < max(1, longest):
+        raise ValueError(f"rle_table: capacity {capacity} is less than the longest mask's {longest} runs")
+    table = np.zeros((len(rows), int(capacity)), dtype=np.uint32)
+    for i, r in enumerate(rows):
+        table[i, :r.size] = r
+    num_runs = np.array([r.size for r in rows], dtype=np.int32)
+    device = torch.device(device)
+    return torch.from_numpy(num_runs).to(device), torch.from_numpy(table.view(np.int32)).to(device)
+
+
+def rle_table(objs, size, device="cuda:0", capacity=None):
+    """A list of COCO RLEs (dicts {"size", "counts"}, compressed strings or count lists) of ONE size (h, w) → (num_runs int32
+    [N], counts int32 [N,capacity]) on the device: the table layout ops.rle_encode writes and ops.rle_iou reads, built with one
+    host-to-device copy. Every entry goes through rle_counts and is checked against rle_iou's contract: the runs cover exactly
+    h*w pixels and only the leading run may be empty (ValueError otherwise)."""
+    h, w = int(size[0]), int(size[1])
+    return _pack_table([_checked_counts(obj, h, w, i) for i, obj in enumerate(objs)], device, capacity)
 
 
 def rle_decode(obj, size=None) -> np.ndarray:

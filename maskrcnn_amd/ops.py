@@ -31,7 +31,7 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
-           "rle_encode"]
+           "rle_encode", "rle_iou", "bbox_iou", "coco_match"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1249,6 +1249,167 @@ def rle_encode(masks: torch.Tensor, threshold: int = 0, capacity: int | None = N
 _LIB.define("rle_encode(Tensor masks, int threshold=0, int? capacity=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
 _LIB.impl("rle_encode", rle_encode, "CUDA")
 _LIB.impl("rle_encode", lambda masks, *a: _need_gpu(masks), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# COCO evaluation: grouped RLE / box IoU and the matching of evaluateImg (csrc/cocoeval.hip)
+# --------------------------------------------------------------------------------------------------
+def _rle_table(obj, who: str):
+    """(num_runs int32 [N], counts [N,capacity] as int32) of an image.RleMasks or of the two tensors themselves."""
+    if hasattr(obj, "num_runs") and hasattr(obj, "counts"):
+        obj = (obj.num_runs, obj.counts)
+    if not (isinstance(obj, (tuple, list)) and len(obj) == 2 and all(isinstance(t, torch.Tensor) for t in obj)):
+        raise RuntimeError(f"{who}: expected an RleMasks or the (num_runs, counts) tensors")
+    num_runs, counts = obj
+    _need_gpu(num_runs, counts)
+    if counts.dtype == getattr(torch, "uint32", None):
+        counts = counts.view(torch.int32)
+    if num_runs.dtype != torch.int32 or counts.dtype != torch.int32 or num_runs.dim() != 1 or counts.dim() != 2 \
+            or counts.size(0) != num_runs.size(0) or counts.size(1) < 1:
+        raise RuntimeError(f"{who}: expected num_runs int32 [N] and counts int32 / uint32 [N,capacity >= 1], got "
+                           f"{num_runs.dtype} {tuple(num_runs.shape)} and {counts.dtype} {tuple(counts.shape)}")
+    return num_runs.contiguous(), counts.contiguous()
+
+
+def _group_offsets(who, m: int, n: int, dt_off, gt_off, out_off, out_len, dev):
+    """The three offset tensors of a grouped call (int32, int32, int64, [K+1] each, on the device) and the output length;
+    all None = ONE group of every detection against every ground truth."""
+    given = [o is not None for o in (dt_off, gt_off, out_off)]
+    if not any(given):
+        dt_off = torch.tensor([0, m], dtype=torch.int32, device=dev)
+        gt_off = torch.tensor([0, n], dtype=torch.int32, device=dev)
+        out_off = torch.tensor([0, m * n], dtype=torch.int64, device=dev)
+        return dt_off, gt_off, out_off, m * n, True
+    if not all(given):
+        raise RuntimeError(f"{who}: dt_off, gt_off and out_off come together")
+    _need_gpu(dt_off, gt_off, out_off)
+    if dt_off.dtype != torch.int32 or gt_off.dtype != torch.int32 or out_off.dtype != torch.int64 or dt_off.dim() != 1 \
+            or dt_off.numel() < 1 or dt_off.shape != gt_off.shape or dt_off.shape != out_off.shape:
+        raise RuntimeError(f"{who}: offsets are int32 [K+1], int32 [K+1] and int64 [K+1] device tensors")
+    if out_len is None:
+        out_len = int(out_off[-1])   # one host read; pass out_len to stay asynchronous
+    return dt_off.contiguous(), gt_off.contiguous(), out_off.contiguous(), int(out_len), False
+
+
+def _crowd(who, iscrowd, n: int):
+    if iscrowd is None:
+        return None
+    _need_gpu(iscrowd)
+    if iscrowd.dtype == torch.bool:
+        iscrowd = iscrowd.view(torch.uint8)
+    if iscrowd.dtype != torch.uint8 or iscrowd.shape != (n,):
+        raise RuntimeError(f"{who}: iscrowd is a uint8 / bool [{n}] tensor, got {iscrowd.dtype} {tuple(iscrowd.shape)}")
+    return iscrowd.contiguous()
+
+
+def _iou_out(who, out, out_len: int, dev):
+    if out is None:
+        return torch.zeros(out_len, dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or out.dim() != 1 or out.numel() < out_len or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"{who}: out must be a contiguous float64 [{out_len}] tensor on {dev}")
+    return out
+
+
+@_on_device
+def _rle_iou(dt_num_runs: torch.Tensor, dt_counts: torch.Tensor, gt_num_runs: torch.Tensor, gt_counts: torch.Tensor,
+             iscrowd: torch.Tensor | None = None, dt_off: torch.Tensor | None = None, gt_off: torch.Tensor | None = None,
+             out_off: torch.Tensor | None = None, out_len: int | None = None, out: torch.Tensor | None = None):
+    dnr, dc = _rle_table((dt_num_runs, dt_counts), "rle_iou")
+    gnr, gc = _rle_table((gt_num_runs, gt_counts), "rle_iou")
+    m, n, dev = dnr.size(0), gnr.size(0), dnr.device
+    crowd = _crowd("rle_iou", iscrowd, n)
+    dt_off, gt_off, out_off, out_len, single = _group_offsets("rle_iou", m, n, dt_off, gt_off, out_off, out_len, dev)
+    res = _iou_out("rle_iou", out, out_len, dev)
+    nbytes = int(lib.mrcnn_rle_iou_workspace_bytes(m, dc.size(1), n, gc.size(1)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _launch(lib.mrcnn_rle_iou_f64,
+            (dnr.data_ptr(), dc.data_ptr(), m, dc.size(1), gnr.data_ptr(), gc.data_ptr(), n, gc.size(1), _ptr(crowd),
+             dt_off.data_ptr(), gt_off.data_ptr(), out_off.data_ptr(), dt_off.numel() - 1, res.data_ptr(), out_len,
+             ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (m, n, out_len), 4 * (dc.numel() + gc.numel()) + 8 * out_len, "rle_iou"))
+    return res[:m * n].view(n, m).t() if single else res
+
+
+def rle_iou(dt, gt, iscrowd: torch.Tensor | None = None, dt_off=None, gt_off=None, out_off=None, out_len=None, out=None):
+    """maskUtils.iou on run-length masks (rleIou of cocoapi/common/maskApi.c:77-96, the same bits) on the GPU. dt and gt are
+    image.RleMasks or their (num_runs int32 [N], counts [N,capacity]) device tensors — what rle_encode returns, no host trip.
+    iscrowd: uint8 [len(gt)]. Without offsets: every detection against every ground truth → float64 [m, n] (a Fortran-order
+    view, as _mask.pyx:239 returns). Grouped (include/maskrcnn_hip.h): dt_off / gt_off int32 [K+1] and out_off int64 [K+1]
+    device tensors name K groups; → the flat float64 [out_len] buffer with group k's o[g*m + d] matrix at out_off[k] (elements
+    of no group stay 0). A pair with a mask that did not fit its capacity is -1."""
+    return _rle_iou(*_rle_table(dt, "rle_iou"), *_rle_table(gt, "rle_iou"), iscrowd, dt_off, gt_off, out_off, out_len, out)
+
+
+@_on_device
+def bbox_iou(dt: torch.Tensor, gt: torch.Tensor, iscrowd: torch.Tensor | None = None, dt_off=None, gt_off=None, out_off=None,
+             out_len=None, out=None):
+    """maskUtils.iou on boxes (bbIou of maskApi.c:109-120, operation by operation in fp64) for float64 (x, y, w, h) boxes
+    dt [m,4] and gt [n,4] on the GPU; single-group and grouped forms and the result layout as rle_iou."""
+    _need_gpu(dt, gt)
+    for name, b in (("dt", dt), ("gt", gt)):
+        if b.dtype != torch.float64 or b.dim() != 2 or b.size(1) != 4:
+            raise RuntimeError(f"bbox_iou: {name} must be a float64 [N,4] tensor, got {b.dtype} {tuple(b.shape)}")
+    dt, gt = dt.contiguous(), gt.contiguous()
+    m, n, dev = dt.size(0), gt.size(0), dt.device
+    crowd = _crowd("bbox_iou", iscrowd, n)
+    dt_off, gt_off, out_off, out_len, single = _group_offsets("bbox_iou", m, n, dt_off, gt_off, out_off, out_len, dev)
+    res = _iou_out("bbox_iou", out, out_len, dev)
+    _launch(lib.mrcnn_bbox_iou_f64,
+            (dt.data_ptr(), m, gt.data_ptr(), n, _ptr(crowd), dt_off.data_ptr(), gt_off.data_ptr(), out_off.data_ptr(),
+             dt_off.numel() - 1, res.data_ptr(), out_len, _stream()),
+            lambda: (0, (m, n, out_len), 32 * (m + n) + 8 * out_len, "bbox_iou"))
+    return res[:m * n].view(n, m).t() if single else res
+
+
+@_on_device
+def coco_match(ious: torch.Tensor, dt_off: torch.Tensor, gt_off: torch.Tensor, out_off: torch.Tensor, dt_area: torch.Tensor,
+               gt_area: torch.Tensor, gt_iscrowd: torch.Tensor, area_ranges: torch.Tensor, thresholds: torch.Tensor, out=None):
+    """The matching of COCOeval.evaluateImg (cocoeval.py:251-300) for every group x area range x IoU threshold in one launch.
+    ious: the flat float64 buffer of a grouped rle_iou / bbox_iou with the same offsets; dt_area float64 [N] (detections of a
+    group sorted by descending score, cut at maxDet), gt_area float64 [M], gt_iscrowd uint8 [M], area_ranges float64 [A,2],
+    thresholds float64 [T], all on the device. → (dt_match int32 [A,T,N], gt_match int32 [A,T,M], dt_ignore uint8 [A,T,N],
+    gt_ignore uint8 [A,M]); matches are 1-based positions within the group in input order, 0 = none. `out` = those four
+    tensors, preallocated."""
+    _need_gpu(ious, dt_off, gt_off, out_off, dt_area, gt_area, gt_iscrowd, area_ranges, thresholds)
+    n_dt, n_gt, dev = dt_area.numel(), gt_area.numel(), dt_area.device
+    if gt_iscrowd.dtype == torch.bool:
+        gt_iscrowd = gt_iscrowd.view(torch.uint8)
+    if ious.dtype != torch.float64 or dt_area.dtype != torch.float64 or gt_area.dtype != torch.float64 \
+            or area_ranges.dtype != torch.float64 or thresholds.dtype != torch.float64 or gt_iscrowd.dtype != torch.uint8:
+        raise RuntimeError("coco_match: ious, areas, area_ranges and thresholds are float64 tensors, gt_iscrowd uint8")
+    if area_ranges.dim() != 2 or area_ranges.size(1) != 2 or thresholds.dim() != 1 or gt_iscrowd.numel() != n_gt \
+            or area_ranges.size(0) < 1 or thresholds.numel() < 1:
+        raise RuntimeError("coco_match: area_ranges is [A,2], thresholds [T], gt_iscrowd as long as gt_area")
+    dt_off, gt_off, out_off, _, _ = _group_offsets("coco_match", n_dt, n_gt, dt_off, gt_off, out_off, 0, dev)
+    ious, dt_area, gt_area, gt_iscrowd = ious.contiguous().view(-1), dt_area.contiguous(), gt_area.contiguous(), gt_iscrowd.contiguous()
+    area_ranges, thresholds = area_ranges.contiguous(), thresholds.contiguous()
+    a, t = area_ranges.size(0), thresholds.numel()
+    shapes = ((a, t, n_dt), (a, t, n_gt), (a, t, n_dt), (a, n_gt))
+    dtypes = (torch.int32, torch.int32, torch.uint8, torch.uint8)
+    if out is None:
+        out = tuple(torch.zeros(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    for o, s, d in zip(out, shapes, dtypes):
+        if o.dtype != d or tuple(o.shape) != s or not o.is_contiguous() or o.device != dev:
+            raise RuntimeError(f"coco_match: out tensors must be contiguous {dtypes} of shapes {shapes} on {dev}")
+    dt_match, gt_match, dt_ignore, gt_ignore = out
+    _launch(lib.mrcnn_coco_match,
+            (ious.data_ptr() if ious.numel() else None, ious.numel(), dt_off.data_ptr(), gt_off.data_ptr(), out_off.data_ptr(),
+             dt_off.numel() - 1, _ptr(dt_area) if n_dt else None, n_dt, _ptr(gt_area) if n_gt else None,
+             _ptr(gt_iscrowd) if n_gt else None, n_gt, area_ranges.data_ptr(), a, thresholds.data_ptr(), t,
+             _ptr(dt_match) if n_dt else None, _ptr(gt_match) if n_gt else None, _ptr(dt_ignore) if n_dt else None,
+             _ptr(gt_ignore) if n_gt else None, _stream()),
+            lambda: (0, (dt_off.numel() - 1, a, t), 8 * ious.numel(), "coco_match"))
+    return dt_match, gt_match, dt_ignore, gt_ignore
+
+
+_LIB.define("rle_iou(Tensor dt_num_runs, Tensor dt_counts, Tensor gt_num_runs, Tensor gt_counts, Tensor? iscrowd=None, "
+            "Tensor? dt_off=None, Tensor? gt_off=None, Tensor? out_off=None, int? out_len=None) -> Tensor")
+_LIB.impl("rle_iou", _rle_iou, "CUDA")
+_LIB.impl("rle_iou", lambda dt_num_runs, *a: _need_gpu(dt_num_runs), "CPU")
+_LIB.define("bbox_iou(Tensor dt, Tensor gt, Tensor? iscrowd=None, Tensor? dt_off=None, Tensor? gt_off=None, "
+            "Tensor? out_off=None, int? out_len=None) -> Tensor")
+_LIB.impl("bbox_iou", bbox_iou, "CUDA")
+_LIB.impl("bbox_iou", lambda dt, *a: _need_gpu(dt), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------

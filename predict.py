@@ -47,7 +47,8 @@ def main(argv=None):
     ap.add_argument("--precision", default="f32", choices=["f32", "f16x3", "f32+f16x3", "f16"])
     ap.add_argument("--save", default=None, help="write class_ids / scores / boxes / masks to this .npz")
     ap.add_argument("--coco-json", default=None, help="write COCO result records (image_id, category_id, bbox, score, "
-                                                     "segmentation as RLE: build_coco_results, coco.py:53-60) to this file")
+                                                     "segmentation as RLE: build_coco_results, coco.py:53-60) to this file; score it with "
+                                                     "`python -m maskrcnn_amd.cocoeval GT.json FILE`")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("image", type=str, help="image file")
     args = ap.parse_args(argv)
