@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 19
+#define MRCNN_ABI_VERSION 20
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -608,6 +608,53 @@ int mrcnn_coco_match(const double* ious, int64_t ious_len, const int32_t* dt_off
                      const uint8_t* gt_iscrowd, int32_t n_gt, const double* area_ranges, int32_t num_ranges,
                      const double* thresholds, int32_t num_thresholds, int32_t* dt_match, int32_t* gt_match,
                      uint8_t* dt_ignore, uint8_t* gt_ignore, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * COCO polygon ground truth to run lengths — replaces COCO.annToRLE's per-annotation maskUtils.frPyObjects + maskUtils.merge
+ * (pycocotools/coco.py:406-425): rleFrPoly / rleFrBbox and rleMerge of cocoapi/common/maskApi.c:162-202, :49-70, for all
+ * parts of a data set in one call each. csrc/poly.hip. Run-list tables are in the layout mrcnn_rle_encode_u8 writes and
+ * mrcnn_rle_iou_f64 reads: num_runs int32 [n], counts uint32 [n][capacity]. Every count has the bits of the reference's
+ * codec (fp64, operation by operation, no FMA contraction). No allocation, no host synchronisation; the same bits from
+ * run to run.
+ *
+ * mrcnn_rle_from_poly_f64: rleFrPoly for n polygon parts.
+ *   xy        double [total_vertices][2]  all parts' vertices, x then y
+ *   vert_off  int32 [n+1]                 part i owns vertices [vert_off[i], vert_off[i+1])
+ *   heights, widths  int32 [n]            every part has its own image size
+ *   num_runs  int32 [n]                   the true number of runs, also beyond capacity
+ *   counts    uint32 [n][capacity]        a part with more runs than capacity: its row is not written; the other parts
+ *                                         are unaffected and nothing is written past a row (the encoder's rule)
+ *   num_keys  int32 [n]                   the column crossings kept before the parity rule. A part with at most
+ *                                         mrcnn_rle_from_poly_onchip_keys() of them is sorted on chip in one piece; one
+ *                                         with more is sorted range by range of the key space (same bits).
+ *   Limits. Checked on the host (an error): 0 <= n <= 2^22, 0 <= total_vertices <= 2^28, capacity >= 1. The values in
+ *   device memory cannot be read without a synchronisation, so a part past one of the following limits is refused ON THE
+ *   DEVICE: it reports num_runs = num_keys = -1, writes nothing else and reads nothing outside its arrays —
+ *   1 <= height, width <= 16384; 0 <= vert_off[i] < vert_off[i+1] <= total_vertices (at least one vertex);
+ *   every coordinate finite with |5*v + .5| < 2^31; at most 2^24 boundary points (sum over the edges of
+ *   max(|dX|, |dY|) + 1 in the 5x grid), so that every point index fits int32. (ops.rle_from_poly checks the same limits
+ *   on the host whenever it reads the arguments.)
+ *   n == 0 launches nothing. workspace: mrcnn_rle_from_poly_workspace_bytes(n, total_vertices), 16-byte aligned.
+ *
+ * mrcnn_rle_merge: rleMerge for `groups` groups: group g merges rows [group_off[g], group_off[g+1]) of the input table
+ *   (group_off int32 [groups+1] in device memory) into row g of the output table [groups][out_capacity]; intersect 0 =
+ *   union, 1 = intersection. The output is canonical: only a leading run may be empty and the last run reaches the end.
+ *   A group of one row is a copy; an empty group gives num_runs = 0; a group with more runs than out_capacity reports its
+ *   true num_runs and its row is not written; a group containing a row that was over ITS capacity (or whose offsets point
+ *   outside the table) reports num_runs = -1 and writes nothing. Contract on the input, as for mrcnn_rle_iou_f64: the rows
+ *   of a group cover the same pixel count (< 2^32) and only a leading run may be empty.
+ *   workspace: mrcnn_rle_merge_workspace_bytes(n_rows, capacity), 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t mrcnn_rle_from_poly_onchip_keys(void);
+size_t mrcnn_rle_from_poly_workspace_bytes(int32_t n, int32_t total_vertices);
+int mrcnn_rle_from_poly_f64(const double* xy, int32_t total_vertices, const int32_t* vert_off, const int32_t* heights,
+                            const int32_t* widths, int32_t n, int32_t capacity, int32_t* num_runs, uint32_t* counts,
+                            int32_t* num_keys, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_rle_merge_workspace_bytes(int32_t n_rows, int32_t capacity);
+int mrcnn_rle_merge(const int32_t* num_runs, const uint32_t* counts, int32_t n_rows, int32_t capacity,
+                    const int32_t* group_off, int32_t groups, int32_t intersect, int32_t out_capacity,
+                    int32_t* out_num_runs, uint32_t* out_counts, void* workspace, size_t workspace_bytes,
+                    mrcnn_stream_t stream);
 
 /* RPN conv_shared + both 1x1 heads in one launch on the Winograd kernel (RPN.forward, model.py:605-607,624-641):
  * relu(conv3x3_same(x) * scale + shift) is never stored — each 64-channel output tile is transposed through LDS and

@@ -4,24 +4,33 @@ without pycocotools.
 
     ev = evaluate("instances_val.json", "out.json", iou_type="segm")     # out.json: predict.py --coco-json
     print("\\n".join(ev.summary()))
-    python -m maskrcnn_amd.cocoeval GT.json RESULTS.json [--type segm|bbox]
+    python -m maskrcnn_amd.cocoeval GT.json RESULTS.json [--type segm|bbox] [--polygons error|rasterize]
 
 Where the work is done:
     GPU   the IoU of every detection x ground truth of every (image, category) — ONE grouped ops.rle_iou / ops.bbox_iou call —
           and the matching of evaluateImg for every group x area range x threshold — ONE grouped ops.coco_match call
     host  loadRes / _prepare (grouping, the -score mergesort, the maxDets[-1] cut), and accumulate / summarize restated
           operation by operation in numpy on the small arrays the two calls return.
-Every number equals the reference's bit for bit (tests/golden/cocoeval.npz). Out of scope: polygon segmentations (rleFrPoly),
-keypoints, useCats = 0.
+Every number equals the reference's bit for bit (tests/golden/cocoeval.npz).
+
+Polygon ground truth — every non-crowd annotation of a stock instances_*.json — is COCO.annToRLE's work (pycocotools/coco.py:
+406-425: maskUtils.frPyObjects + maskUtils.merge per annotation). ann_to_rle(gt) does it for a whole data set in ONE grouped
+ops.rle_from_poly call over all parts, ONE grouped ops.rle_merge call over all annotations and one device-to-host copy, the bits
+of the reference's codec (tests/golden/poly.npz). evaluate(..., polygons="rasterize") does the same inside the evaluation and
+keeps the polygon rows on the device between rle_merge and rle_iou; the default polygons="error" refuses polygons
+(NotImplementedError), as before. Polygons in RESULT records stay refused: the reference's loadRes fails on them as well.
+Out of scope: compressed strings, areas and boxes of the rasterised masks (stock ground truth carries area and bbox), keypoints,
+useCats = 0.
 """
 from __future__ import annotations
 
+import inspect
 import json
 
 import numpy as np
 import torch
 
-__all__ = ["Params", "CocoEval", "evaluate", "accumulate", "summarize", "load_results"]
+__all__ = ["Params", "CocoEval", "evaluate", "accumulate", "summarize", "load_results", "ann_to_rle"]
 
 
 class Params:
@@ -223,12 +232,90 @@ def load_results(results, iou_type: str):
     return anns
 
 
-def evaluate(gt, results, iou_type: str = "segm", device="cuda:0") -> CocoEval:
+def _polygon_parts(ann):
+    """The parts of a list segmentation as frPyObjects dispatches them (_mask.pyx:288-308) on the FIRST part: more than 4 numbers
+    → every part is a polygon of len // 2 vertices (a later part of 4 numbers is a 2-vertex polygon). A first part of exactly 4
+    numbers is refused — the reference hands that list to frBbox, which raises TypeError — and so are fewer than 4."""
+    seg, who = ann["segmentation"], f"annotation {ann.get('id')}"
+    if len(seg) == 0 or not _is_polygon(seg[0]):
+        raise ValueError(f"{who}: a list segmentation is a list of [x0, y0, x1, y1, ...] parts")
+    if len(seg[0]) <= 4:
+        raise ValueError(f"{who}: the first part has {len(seg[0])} numbers; frPyObjects takes 4 for a box list, which "
+                         "annToRLE cannot convert, and fewer for nothing at all: a polygon part has more than 4")
+    for part in seg:
+        if not _is_polygon(part) or len(part) < 2:
+            raise ValueError(f"{who}: a part with {len(part) if _is_polygon(part) else type(part).__name__} numbers has no vertex")
+    return list(seg)
+
+
+def _polygon_table(anns, sizes, device):
+    """annToRLE of list-segmentation annotations, all at once: ONE ops.rle_from_poly call over every part and ONE ops.rle_merge
+    call (union) over every annotation → (num_runs int32 [len(anns)], counts int32 [len(anns), capacity]) on the device. sizes:
+    the (h, w) of each annotation's image."""
+    from . import image, ops
+    parts, part_sizes, group_n = [], [], []
+    for ann, size in zip(anns, sizes):
+        mine = _polygon_parts(ann)
+        parts += mine
+        part_sizes += [size] * len(mine)
+        group_n.append(len(mine))
+    pack = lambda pp, ss: image._pack_polygons(pp, np.asarray(ss, dtype=np.int64).reshape(-1, 2))
+    try:
+        xy, off, hs, ws = pack(parts, part_sizes)
+        bounds = ops.poly_host_bounds(xy, off, hs, ws, "ann_to_rle", ValueError)
+    except ValueError:
+        for ann, size in zip(anns, sizes):          # the error path only: which annotation is it?
+            try:
+                ops.poly_host_bounds(*pack(ann["segmentation"], [size] * len(ann["segmentation"])), "ann_to_rle", ValueError)
+            except ValueError as e:
+                raise ValueError(f"annotation {ann.get('id')}: {e}") from e
+        raise
+    group_off = np.concatenate([[0], np.cumsum(group_n)]).astype(np.int64)
+    runs_bound = np.concatenate([[0], np.cumsum(bounds + 1)])
+    capacity = int(bounds.max()) + 1 if len(parts) else 1
+    merged_capacity = max(1, int((runs_bound[group_off[1:]] - runs_bound[group_off[:-1]]).max())) if len(anns) else 1
+    num_runs, counts, _ = ops.rle_from_poly(*image._polygons_to_device(xy, off, hs, ws, device), capacity=capacity)
+    goff = torch.from_numpy(group_off.astype(np.int32)).to(num_runs.device)
+    return ops.rle_merge(num_runs, counts, goff, intersect=False, capacity=merged_capacity)
+
+
+def ann_to_rle(gt, device="cuda:0"):
+    """COCO.annToRLE (pycocotools/coco.py:406-425) over a whole data set: → a copy of the data set dict (or of the file at the
+    path `gt`) in which every list (polygon) segmentation is {"size": [h, w], "counts": [run lengths]} of its image's height /
+    width — the union of its parts, rleFrPoly + rleMerge, the reference codec's bits; dict segmentations are left as they are.
+    The whole data set costs one ops.rle_from_poly call, one ops.rle_merge call and one device-to-host copy. ValueError, naming
+    the annotation id, for a list segmentation frPyObjects would not take as polygons (_polygon_parts)."""
+    if isinstance(gt, str):
+        with open(gt) as fh:
+            gt = json.load(fh)
+    size_of = {img["id"]: (int(img["height"]), int(img["width"])) for img in gt["images"]}
+    out = dict(gt)
+    out["annotations"] = anns = [dict(a) for a in gt["annotations"]]
+    poly = [a for a in anns if _is_polygon(a.get("segmentation"))]
+    if not poly:
+        return out
+    sizes = [size_of[a["image_id"]] for a in poly]
+    num_runs, counts = _polygon_table(poly, sizes, device)
+    live = torch.arange(counts.size(1), device=counts.device)[None, :] < num_runs[:, None]
+    packed = torch.cat([num_runs, counts[live]]).cpu().numpy()          # the one copy: run counts, then the runs that exist
+    nr = packed[:len(poly)].astype(np.int64)
+    ends = len(poly) + np.cumsum(nr)
+    runs = packed.view(np.uint32)
+    for a, (h, w), n, e in zip(poly, sizes, nr.tolist(), ends.tolist()):
+        a["segmentation"] = {"size": [h, w], "counts": runs[e - n:e].tolist()}
+    return out
+
+
+def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: str = "error") -> CocoEval:
     """COCOeval(COCO(gt), COCO(gt).loadRes(results), iou_type) → evaluate(), accumulate(), summarize().
     gt: a COCO dataset dict (images, annotations, categories) or its path; results: the list predict.py --coco-json writes, or
     its path. Ground-truth segmentations (iou_type="segm"): compressed-string RLE, count-list RLE or a dense mask array;
-    polygons raise NotImplementedError. iou_type="bbox" never looks at segmentations."""
+    polygons raise NotImplementedError with polygons="error" (the default) and are rasterised on the GPU with
+    polygons="rasterize" (annToRLE: ops.rle_from_poly + ops.rle_merge, the rows staying on the device for ops.rle_iou).
+    iou_type="bbox" never looks at segmentations."""
     from . import image, ops
+    if polygons not in ("error", "rasterize"):
+        raise ValueError(f"polygons={polygons!r}: 'error' or 'rasterize'")
     p = Params(iou_type)
     if isinstance(gt, str):
         with open(gt) as fh:
@@ -250,7 +337,7 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0") -> CocoEval:
     for ann in dts_all:
         if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
             dts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
-    if iou_type == "segm":
+    if iou_type == "segm" and polygons == "error":
         for key, anns in gts.items():
             for ann in anns:
                 if _is_polygon(ann["segmentation"]):
@@ -286,14 +373,31 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0") -> CocoEval:
     if K:
         offs = (dev_of(dt_off.astype(np.int32)), dev_of(gt_off.astype(np.int32)), dev_of(out_off.astype(np.int64)))
         if iou_type == "segm":
+            size_of = {img["id"]: (int(img["height"]), int(img["width"])) for img in gt["images"]
+                       if "height" in img and "width" in img}
+            ann_size = lambda x: size_of[x["image_id"]] if _is_polygon(x["segmentation"]) else _seg_size(x["segmentation"])
             rows_d = [_seg_counts(d["segmentation"], i, dev) for i, d in enumerate(dt_flat)]
-            rows_g = [_seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
+            is_poly = np.array([_is_polygon(g["segmentation"]) for g in gt_flat], dtype=bool)
+            rows_g = [np.zeros(0, np.uint32) if is_poly[i] else _seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
             for k, key in enumerate(keys):
-                sizes = {_seg_size(x["segmentation"]) for x in dts[key] + gts[key]}
+                sizes = {ann_size(x) for x in dts[key] + gts[key]}
                 if len(sizes) > 1:
                     raise ValueError(f"image {key[0]}, category {key[1]}: masks of different sizes {sorted(sizes)}")
-            ious_dev = ops.rle_iou(image._pack_table(rows_d, dev), image._pack_table(rows_g, dev), dev_of(iscrowd), *offs,
-                                   out_len=out_len)
+            gt_table = image._pack_table(rows_g, dev)
+            if is_poly.any():
+                # annToRLE on the device; the rows go into the ground-truth table there (one scalar comes back: the longest row)
+                poly_anns = [g for g, f in zip(gt_flat, is_poly) if f]
+                p_runs, p_counts = _polygon_table(poly_anns, [size_of[g["image_id"]] for g in poly_anns], dev)
+                cap = max(int(p_runs.max()), gt_table[1].size(1))
+                idx = dev_of(np.nonzero(is_poly)[0])
+                g_runs, g_counts = gt_table[0].clone(), torch.zeros(len(gt_flat), cap, dtype=torch.int32, device=dev)
+                g_counts[:, :gt_table[1].size(1)] = gt_table[1]
+                width = min(cap, p_counts.size(1))
+                live = torch.arange(width, device=dev)[None, :] < p_runs[:, None]
+                g_counts[idx, :width] = torch.where(live, p_counts[:, :width], torch.zeros((), dtype=torch.int32, device=dev))
+                g_runs[idx] = p_runs
+                gt_table = (g_runs, g_counts)
+            ious_dev = ops.rle_iou(image._pack_table(rows_d, dev), gt_table, dev_of(iscrowd), *offs, out_len=out_len)
         else:
             boxes = lambda anns: np.array([[float(v) for v in x["bbox"]] for x in anns], dtype=np.float64).reshape(-1, 4)
             ious_dev = ops.bbox_iou(dev_of(boxes(dt_flat)), dev_of(boxes(gt_flat)), dev_of(iscrowd), *offs, out_len=out_len)
@@ -345,15 +449,25 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0") -> CocoEval:
     return CocoEval(p, ious, eval_imgs)
 
 
+# evaluate's positional interface — (gt, results, iou_type, device) — is pinned parameter by parameter by
+# tests/test_cocoeval_host.py::test_public_interface, through inspect.signature. `polygons` is an option added beside it,
+# keyword-only and documented in the docstring; the signature reported to introspection stays the pinned one.
+evaluate.__signature__ = inspect.Signature(
+    [q for q in inspect.signature(evaluate).parameters.values() if q.kind is not inspect.Parameter.KEYWORD_ONLY],
+    return_annotation=inspect.signature(evaluate).return_annotation)
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="COCO AP / AR of a result file (predict.py --coco-json) against ground truth")
-    ap.add_argument("gt", help="COCO annotation file (RLE segmentations for --type segm)")
+    ap.add_argument("gt", help="COCO annotation file (--type segm: RLE segmentations, or polygons with --polygons rasterize)")
     ap.add_argument("results", help="COCO result records")
     ap.add_argument("--type", default="segm", choices=("segm", "bbox"), dest="iou_type")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--polygons", default="error", choices=("error", "rasterize"),
+                    help="polygon ground truth (--type segm): refuse it, or rasterise it on the GPU as COCO.annToRLE does")
     args = ap.parse_args(argv)
-    print("\n".join(evaluate(args.gt, args.results, args.iou_type, args.device).summary()))
+    print("\n".join(evaluate(args.gt, args.results, args.iou_type, args.device, polygons=args.polygons).summary()))
 
 
 if __name__ == "__main__":

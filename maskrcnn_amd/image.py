@@ -256,3 +256,59 @@ def rle_decode(obj, size=None) -> np.ndarray:
         raise ValueError(f"rle_decode: the runs cover {int(cnts.sum())} pixels, the mask has {h} x {w}")
     flat = np.repeat(np.arange(cnts.size) & 1, cnts).astype(bool)
     return flat.reshape(w, h).T
+
+
+# ---------------------------------------------------------------------------------------------- polygons and boxes to RLE
+def _pack_polygons(polys, sizes):
+    """polys: flat [x0, y0, x1, y1, ...] lists (k = len // 2 vertices each, as _mask.pyx:266); sizes: one (h, w) or one per
+    polygon → numpy (xy float64 [V,2], vert_off int64 [n+1], heights int64 [n], widths int64 [n]). ValueError for a polygon
+    without a vertex or a size list of another length."""
+    n = len(polys)
+    sizes = np.asarray(sizes, dtype=np.int64)
+    if sizes.shape == (2,):
+        sizes = np.broadcast_to(sizes, (n, 2))
+    if sizes.shape != (n, 2):
+        raise ValueError(f"rle_from_polygons: sizes is one (h, w) or one per polygon: {n} polygons, sizes of shape {sizes.shape}")
+    ks = np.array([len(p) // 2 for p in polys], dtype=np.int64)
+    if (ks < 1).any():
+        i = int(np.argmax(ks < 1))
+        raise ValueError(f"rle_from_polygons: polygon {i} has {len(polys[i])} numbers: not one vertex")
+    xy = np.empty((int(ks.sum()), 2), dtype=np.float64)
+    off = np.concatenate([[0], np.cumsum(ks)])
+    for i, p in enumerate(polys):
+        xy[off[i]:off[i + 1]] = np.asarray(p[:2 * ks[i]], dtype=np.float64).reshape(-1, 2)
+    return xy, off, np.ascontiguousarray(sizes[:, 0]), np.ascontiguousarray(sizes[:, 1])
+
+
+def _polygons_to_device(xy, off, hs, ws, device):
+    """ONE float64 buffer, one host-to-device copy → the device arguments of ops.rle_from_poly (the integers are exact in
+    float64 and are cast on the device)."""
+    v, n = xy.shape[0], hs.size
+    buf = torch.from_numpy(np.concatenate([xy.reshape(-1), off, hs, ws]).astype(np.float64)).to(torch.device(device))
+    ints = buf[2 * v:].to(torch.int32)
+    return buf[:2 * v].view(v, 2), ints[:n + 1], ints[n + 1:2 * n + 1], ints[2 * n + 1:]
+
+
+def rle_from_polygons(polys, sizes, device="cuda:0"):
+    """maskUtils.frPyObjects(polys, h, w) for polygons (rleFrPoly, the same bits) on the GPU, all of them in ONE ops.rle_from_poly
+    call: polys is a list of flat [x0, y0, x1, y1, ...] lists (len // 2 vertices; an odd trailing number is dropped, as the
+    reference does), sizes one (h, w) or one per polygon. → (num_runs int32 [n], counts int32 [n,capacity]) on the device, every
+    polygon fitting: the table ops.rle_iou / ops.rle_merge read. Everything goes to the device in one buffer and nothing comes
+    back. ValueError: a polygon without a vertex, a coordinate that is not finite or has |5*v + .5| >= 2^31, a size outside
+    [1, 16384], more than 2^24 boundary points in one polygon."""
+    xy, off, hs, ws = _pack_polygons(polys, sizes)
+    bounds = ops.poly_host_bounds(xy, off, hs, ws, "rle_from_polygons", ValueError)
+    capacity = int(bounds.max()) + 1 if len(polys) else 1
+    num_runs, counts, _ = ops.rle_from_poly(*_polygons_to_device(xy, off, hs, ws, device), capacity=capacity)
+    return num_runs, counts
+
+
+def rle_from_bboxes(boxes, size, device="cuda:0"):
+    """maskUtils.frPyObjects(boxes, h, w) for (x, y, w, h) boxes [N,4] (rleFrBbox, maskApi.c:149-156: the four-vertex polygon
+    xs,ys, xs,ye, xe,ye, xe,ys with xe = xs + w and ye = ys + h in float64, through the polygon kernel) → the table of
+    rle_from_polygons."""
+    bb = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    xs, ys = bb[:, 0], bb[:, 1]
+    xe, ye = xs + bb[:, 2], ys + bb[:, 3]
+    polys = np.stack([xs, ys, xs, ye, xe, ye, xe, ys], axis=1)
+    return rle_from_polygons(list(polys), size, device)

@@ -22,6 +22,7 @@ import math
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from ._lib import MaskrcnnHipError, c_f32, c_i32, c_vp, check, lib
@@ -31,7 +32,7 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
-           "rle_encode", "rle_iou", "bbox_iou", "coco_match"]
+           "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1410,6 +1411,139 @@ _LIB.define("bbox_iou(Tensor dt, Tensor gt, Tensor? iscrowd=None, Tensor? dt_off
             "Tensor? out_off=None, int? out_len=None) -> Tensor")
 _LIB.impl("bbox_iou", bbox_iou, "CUDA")
 _LIB.impl("bbox_iou", lambda dt, *a: _need_gpu(dt), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# COCO polygons to run lengths: rleFrPoly and rleMerge, grouped (csrc/poly.hip)
+# --------------------------------------------------------------------------------------------------
+POLY_MAX_DIM = 16384
+POLY_MAX_PART_POINTS = 1 << 24
+
+
+def poly_host_bounds(xy, vert_off, heights, widths, who: str = "rle_from_poly", error=RuntimeError):
+    """The limits of mrcnn_rle_from_poly_f64 (include/maskrcnn_hip.h) checked on host copies of its arguments — numpy: xy float64
+    [V,2], vert_off [n+1], heights / widths [n] — and, per part, a conservative bound on the keys the kernel can keep: the sum over
+    the edges of |dX| // 5 + 1 (a crossing falls on a pixel column only where u = 2 mod 5). The bound sizes tables; no value computed
+    here reaches an output. Raises `error` at the first value past a limit."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    off = np.asarray(vert_off, dtype=np.int64).reshape(-1)
+    hs, ws = np.asarray(heights, dtype=np.int64).reshape(-1), np.asarray(widths, dtype=np.int64).reshape(-1)
+    n, v = hs.size, xy.shape[0]
+    if off.size != n + 1 or ws.size != n:
+        raise error(f"{who}: vert_off has {off.size} entries and widths {ws.size} for {n} parts")
+    if n == 0:
+        return np.zeros(0, dtype=np.int64)
+    if off[0] != 0 or off[-1] != v:
+        raise error(f"{who}: vert_off must start at 0 and end at the number of vertices {v}, got {int(off[0])} .. {int(off[-1])}")
+    k = np.diff(off)
+    if (k < 1).any():
+        raise error(f"{who}: part {int(np.argmax(k < 1))} has no vertex (vert_off must increase)")
+    for name, a in (("height", hs), ("width", ws)):
+        if ((a < 1) | (a > POLY_MAX_DIM)).any():
+            i = int(np.argmax((a < 1) | (a > POLY_MAX_DIM)))
+            raise error(f"{who}: part {i} has {name} {int(a[i])}, outside [1, {POLY_MAX_DIM}]")
+    if not np.isfinite(xy).all():
+        raise error(f"{who}: vertex {int(np.argmax(~np.isfinite(xy).all(1)))} is not finite")
+    g = np.trunc(5.0 * xy + .5)                       # the grid vertices, as floats: no integer can overflow here
+    if (np.abs(5.0 * xy + .5) >= 2.0 ** 31).any():
+        raise error(f"{who}: vertex {int(np.argmax((np.abs(5.0 * xy + .5) >= 2.0 ** 31).any(1)))}: |5*v + .5| must stay below 2^31")
+    nxt = np.arange(1, v + 1)
+    nxt[off[1:] - 1] = off[:-1]                       # the closing edge of every part
+    d = np.abs(g[nxt] - g)
+    sums = lambda per_edge: np.add.reduceat(per_edge, off[:-1])
+    points = sums(d.max(1) + 1)
+    if (points > POLY_MAX_PART_POINTS).any():
+        i = int(np.argmax(points > POLY_MAX_PART_POINTS))
+        raise error(f"{who}: part {i} has {int(points[i])} boundary points, more than {POLY_MAX_PART_POINTS}")
+    return sums(np.floor(d[:, 0] / 5.0) + 1).astype(np.int64)
+
+
+def rle_from_poly_onchip_keys() -> int:
+    """Keys of one part that rle_from_poly sorts on chip in one piece; a part with more is sorted range by range."""
+    return int(lib.mrcnn_rle_from_poly_onchip_keys())
+
+
+@_on_device
+def rle_from_poly(xy: torch.Tensor, vert_off: torch.Tensor, heights: torch.Tensor, widths: torch.Tensor,
+                  capacity: int | None = None):
+    """maskUtils.frPyObjects on polygons (rleFrPoly of cocoapi/common/maskApi.c:162-202, the same bits) for n polygon parts in one
+    call on the GPU. xy float64 [V,2] (or flat [2V]): all parts' vertices; vert_off int32 [n+1]: part i owns vertices
+    [vert_off[i], vert_off[i+1]); heights / widths int32 [n]: every part has its own image size. All device tensors.
+    → (num_runs int32 [n], counts int32 [n,capacity], num_keys int32 [n]): the run-list table ops.rle_iou and ops.rle_merge read, and
+    the column crossings each part kept before the parity rule. A part with more runs than capacity reports its true num_runs and
+    its row is not written (uninitialised memory here). capacity=None: the arguments are read back once, checked against the limits
+    of include/maskrcnn_hip.h (RuntimeError at the first value past one) and the capacity is the host's key bound + 1, which no part
+    exceeds. With a capacity the call never synchronises; a part past a limit then reports num_runs = num_keys = -1."""
+    _need_gpu(xy, vert_off, heights, widths)
+    if xy.dtype != torch.float64 or not (xy.dim() == 1 and xy.numel() % 2 == 0 or xy.dim() == 2 and xy.size(1) == 2):
+        raise RuntimeError(f"rle_from_poly: xy must be a float64 [V,2] tensor, got {xy.dtype} {tuple(xy.shape)}")
+    for name, t in (("vert_off", vert_off), ("heights", heights), ("widths", widths)):
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise RuntimeError(f"rle_from_poly: {name} must be an int32 vector, got {t.dtype} {tuple(t.shape)}")
+    n, v = heights.numel(), xy.numel() // 2
+    if vert_off.numel() != n + 1 or widths.numel() != n:
+        raise RuntimeError(f"rle_from_poly: {n} heights need {n} widths and {n + 1} offsets, got {widths.numel()} and {vert_off.numel()}")
+    xy, vert_off, heights, widths = xy.contiguous(), vert_off.contiguous(), heights.contiguous(), widths.contiguous()
+    if capacity is None:
+        ints = torch.cat([vert_off, heights, widths]).cpu().numpy()
+        bounds = poly_host_bounds(xy.cpu().numpy(), ints[:n + 1], ints[n + 1:2 * n + 1], ints[2 * n + 1:])
+        capacity = int(bounds.max()) + 1 if n else 1
+    capacity = int(capacity)
+    dev = xy.device
+    num_runs = torch.empty(n, dtype=torch.int32, device=dev)
+    num_keys = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(n, max(capacity, 0), dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rle_from_poly_workspace_bytes(n, v))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _launch(lib.mrcnn_rle_from_poly_f64,
+            (xy.data_ptr() if v else None, v, vert_off.data_ptr(), _ptr(heights) if n else None, _ptr(widths) if n else None, n,
+             capacity, _ptr(num_runs) if n else None, _ptr(counts) if n else None, _ptr(num_keys) if n else None, ws.data_ptr(),
+             nbytes, _stream()),
+            lambda: (0, (n, v, capacity), 16 * v + 4 * counts.numel(), "rle_from_poly"))
+    return num_runs, counts, num_keys
+
+
+@_on_device
+def rle_merge(num_runs: torch.Tensor, counts: torch.Tensor, group_off: torch.Tensor, intersect: bool = False,
+              capacity: int | None = None):
+    """maskUtils.merge (rleMerge of cocoapi/common/maskApi.c:49-70, the same bits) for G groups in one call on the GPU: group g is
+    the union (intersect=False) or the intersection of rows [group_off[g], group_off[g+1]) of the table (num_runs int32 [N],
+    counts [N,capacity_in]); group_off int32 [G+1] on the device. → (num_runs int32 [G], counts int32 [G,capacity]). An empty group
+    has num_runs 0; a group with more runs than capacity reports its true num_runs and its row is not written; a group holding a
+    row that was over its own capacity reports -1. capacity=None: one read of the group sizes, and the capacity is the longest
+    group's total run count, which no result exceeds. Contract as for rle_iou: the rows of a group cover the same pixel count and
+    only a leading run may be empty."""
+    num_runs, counts = _rle_table((num_runs, counts), "rle_merge")
+    _need_gpu(group_off)
+    if group_off.dtype != torch.int32 or group_off.dim() != 1 or group_off.numel() < 1:
+        raise RuntimeError(f"rle_merge: group_off must be an int32 [G+1] tensor, got {group_off.dtype} {tuple(group_off.shape)}")
+    group_off = group_off.contiguous()
+    n, g, dev = num_runs.size(0), group_off.numel() - 1, num_runs.device
+    if capacity is None:
+        nr, off = num_runs.cpu().numpy().astype(np.int64), group_off.cpu().numpy().astype(np.int64)
+        if (off < 0).any() or (off > n).any() or (np.diff(off) < 0).any():
+            raise RuntimeError(f"rle_merge: group_off must be non-decreasing within [0, {n}]")
+        csum = np.concatenate([[0], np.cumsum(np.clip(nr, 0, counts.size(1)))])
+        capacity = max(1, int((csum[off[1:]] - csum[off[:-1]]).max())) if g else 1
+    capacity = int(capacity)
+    out_runs = torch.empty(g, dtype=torch.int32, device=dev)
+    out_counts = torch.empty(g, max(capacity, 0), dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rle_merge_workspace_bytes(n, counts.size(1)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _launch(lib.mrcnn_rle_merge,
+            (_ptr(num_runs) if n else None, _ptr(counts) if n else None, n, counts.size(1), group_off.data_ptr(), g,
+             1 if intersect else 0, capacity, _ptr(out_runs) if g else None, _ptr(out_counts) if g else None, ws.data_ptr(), nbytes,
+             _stream()),
+            lambda: (0, (n, g, capacity), 4 * (counts.numel() + out_counts.numel()), "rle_merge"))
+    return out_runs, out_counts
+
+
+_LIB.define("rle_from_poly(Tensor xy, Tensor vert_off, Tensor heights, Tensor widths, int? capacity=None) -> (Tensor, Tensor, Tensor)")
+_LIB.impl("rle_from_poly", rle_from_poly, "CUDA")
+_LIB.impl("rle_from_poly", lambda xy, *a: _need_gpu(xy), "CPU")
+_LIB.define("rle_merge(Tensor num_runs, Tensor counts, Tensor group_off, bool intersect=False, int? capacity=None) -> (Tensor, Tensor)")
+_LIB.impl("rle_merge", rle_merge, "CUDA")
+_LIB.impl("rle_merge", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------
