@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 20
+#define MRCNN_ABI_VERSION 22
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -655,6 +655,58 @@ int mrcnn_rle_merge(const int32_t* num_runs, const uint32_t* counts, int32_t n_r
                     const int32_t* group_off, int32_t groups, int32_t intersect, int32_t out_capacity,
                     int32_t* out_num_runs, uint32_t* out_counts, void* workspace, size_t workspace_bytes,
                     mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The rest of the COCO RLE codec on run-list TABLES — rleFrString, rleToString, rleArea + rleToBbox and rleDecode of
+ * cocoapi/common/maskApi.c:218-231, :204-216, :72-75 + :133-147, :43-47 — for n rows in one call each. csrc/codec.hip.
+ * Tables are in the layout mrcnn_rle_encode_u8 writes: num_runs int32 [n], counts uint32 [n][capacity], off run first. A row
+ * with num_runs < 0 (refused) or num_runs > capacity (never written) is called UNUSABLE below. Strings travel packed:
+ * bytes uint8 [total], str_off int64 [n+1]; string i is bytes[str_off[i] : str_off[i+1]), not NUL-terminated, possibly empty.
+ * Every value has the bits of the reference's codec. No allocation, no host synchronisation, no atomics; the same bits from run
+ * to run. Host-checked limits (an error): 0 <= n <= 2^24 (mrcnn_rle_decode_u8: 65535), capacity >= 1. n == 0 launches nothing
+ * (mrcnn_rle_to_string still writes str_off[0] = 0).
+ *
+ * mrcnn_rle_from_string: rleFrString for n strings. A token ends at a character c with (c - 48) & 0x20 == 0; its value is the
+ *   little-endian 5-bit groups, sign-extended when the last group has 0x10; cnts[m] = x[m] + cnts[m-2] for m > 2, in uint32
+ *   wrap-around. heights / widths int32 [n] are used for the checks only. status int32 [n] is a bit set:
+ *     refused on the device — num_runs = -1, the row untouched, the other rows unaffected:
+ *       1  a byte outside 48..111          2  a token longer than 6 characters (the reference's int shift is undefined from
+ *       4  the string ends inside a token     the seventh; a difference of a mask of at most 2^28 pixels fits in 6)
+ *       8  height or width outside [1, 16384]      64  str_off[i] > str_off[i+1], or outside [0, total_bytes]
+ *     flagged, the row still written:
+ *       16 an empty run after the first    32 the runs' sum (taken in 64 bits) differs from heights[i] * widths[i]
+ *   A row with more runs than capacity reports its true num_runs and status 0 and is not written (the encoder's rule; bits
+ *   16 and 32 are not computed for it). Nothing is written past num_runs in a row.
+ * mrcnn_rle_area_bbox: rleArea and rleToBbox of every row: areas int32 [n], bboxes int32 [n][4] (x, y, w, h), the encoder's
+ *   types, with per-row heights / widths. uint32 arithmetic as the reference's, its quirks kept: m = (m/2)*2 (the last run of
+ *   an odd row is ignored), m == 0 gives four zeros, t = cc - j%2, an on run whose end lies in a later column than its start
+ *   sets ys = 0, ye = h-1. An unusable row, or one with a height or width outside [1, 16384], gets area -1 and bbox -1.
+ * mrcnn_rle_to_string: rleToString of every row into the packed buffer bytes [bytes_capacity]. str_off [n+1] always holds the
+ *   true offsets, str_off[n] the true total; an unusable row contributes 0 bytes. A row with str_off[i+1] > bytes_capacity is
+ *   not written, and nothing is written past the buffer (bytes may be NULL with bytes_capacity 0: offsets only).
+ *   row_stride > 0 selects the encoder's fixed-stride layout instead of the packed one: row i is written at bytes +
+ *   i*row_stride (str_off still holds the packed offsets, so str_off[i+1] - str_off[i] is its length); a row longer than
+ *   row_stride, or whose slot crosses bytes_capacity, is not written. have_offsets = 1: str_off already holds the offsets of
+ *   THIS table (an earlier call wrote them) and only the write pass is launched.
+ *   workspace: mrcnn_rle_to_string_workspace_bytes(n), 16-byte aligned.
+ * mrcnn_rle_decode_u8: rleDecode of n rows of ONE size into row-major 0 / 1 masks: mask i at out + i*image_stride, rows
+ *   row_stride bytes apart (>= width), pixels contiguous (what mrcnn_rle_encode_u8 reads). Every byte of every mask is written
+ *   and none outside; runs past height*width are clipped, pixels the runs do not reach are 0, an unusable row decodes to zeros.
+ *   1 <= height, width <= 16384. workspace: mrcnn_rle_decode_workspace_bytes(n, capacity), 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_rle_from_string(const uint8_t* bytes, int64_t total_bytes, const int64_t* str_off, const int32_t* heights,
+                          const int32_t* widths, int32_t n, int32_t capacity, int32_t* num_runs, uint32_t* counts,
+                          int32_t* status, mrcnn_stream_t stream);
+int mrcnn_rle_area_bbox(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, const int32_t* heights,
+                        const int32_t* widths, int32_t* areas, int32_t* bboxes, mrcnn_stream_t stream);
+size_t mrcnn_rle_to_string_workspace_bytes(int32_t n);
+int mrcnn_rle_to_string(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, uint8_t* bytes,
+                        int64_t bytes_capacity, int64_t row_stride, int32_t have_offsets, int64_t* str_off, void* workspace,
+                        size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_rle_decode_workspace_bytes(int32_t n, int32_t capacity);
+int mrcnn_rle_decode_u8(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, int32_t height,
+                        int32_t width, uint8_t* out, int64_t image_stride, int64_t row_stride, void* workspace,
+                        size_t workspace_bytes, mrcnn_stream_t stream);
 
 /* RPN conv_shared + both 1x1 heads in one launch on the Winograd kernel (RPN.forward, model.py:605-607,624-641):
  * relu(conv3x3_same(x) * scale + shift) is never stored — each 64-channel output tile is transposed through LDS and

@@ -19,8 +19,12 @@ ops.rle_from_poly call over all parts, ONE grouped ops.rle_merge call over all a
 of the reference's codec (tests/golden/poly.npz). evaluate(..., polygons="rasterize") does the same inside the evaluation and
 keeps the polygon rows on the device between rle_merge and rle_iou; the default polygons="error" refuses polygons
 (NotImplementedError), as before. Polygons in RESULT records stay refused: the reference's loadRes fails on them as well.
-Out of scope: compressed strings, areas and boxes of the rasterised masks (stock ground truth carries area and bbox), keypoints,
-useCats = 0.
+
+Compressed strings — every record of a result file — are decoded on the GPU: load_results(..., device=) sends all strings of the file
+through ONE ops.rle_from_string call and ONE ops.rle_area_bbox call (rleFrString, rleArea, rleToBbox: tests/golden/codec.npz), and
+evaluate() keeps that table on the device and gathers it into computeIoU's order with an index tensor, so each string is decoded
+once and there is no per-character host work; compressed ground truth takes the same route. ann_to_rle(compress=True) writes the
+compressed strings COCO.annToRLE returns (ops.rle_to_string). Out of scope: keypoints, useCats = 0.
 """
 from __future__ import annotations
 
@@ -197,9 +201,27 @@ def _seg_counts(seg, i: int, device) -> np.ndarray:
     raise TypeError(f"segmentation {i}: expected an RLE dict or a dense mask array, got {type(seg).__name__}")
 
 
-def load_results(results, iou_type: str):
+class _Decoded:
+    """What _load's device route decoded on the GPU: table = (num_runs, counts) of the compressed strings on the device, runs /
+    status their host copies (int32 [S]), row_of {record id (loadRes' i + 1): row}."""
+
+    def __init__(self, table, runs, status, row_of):
+        self.table, self.runs, self.status, self.row_of = table, runs, status, row_of
+
+
+def load_results(results, iou_type: str, device=None):
     """COCO.loadRes (pycocotools/coco.py:297-352) on a list of result records: id = i + 1, iscrowd = 0, and — decided by the
-    FIRST record, as there — area = w*h of the box where records carry a bbox, else the RLE's area and bbox = toBbox."""
+    FIRST record, as there — area = w*h of the box where records carry a bbox, else the RLE's area and bbox = toBbox.
+    device=None: the RLEs are read on the host (image.rle_counts, numpy). A GPU device: all compressed strings of the file go
+    through ONE ops.rle_from_string and ONE ops.rle_area_bbox call and one copy back — the same areas and boxes, values and types;
+    a malformed string is a ValueError naming the record. Count lists keep the host route."""
+    return _load(results, iou_type, device)[0]
+
+
+def _load(results, iou_type: str, device=None):
+    """load_results → (records, a _Decoded with the table the device route made, or None)."""
+    decoded = None
+    on_gpu = device is not None and torch.device(device).type != "cpu"
     if isinstance(results, str):
         with open(results) as fh:
             results = json.load(fh)
@@ -207,7 +229,7 @@ def load_results(results, iou_type: str):
         raise TypeError("results in not an array of objects")
     anns = [dict(r) for r in results]
     if not anns:
-        return anns
+        return anns, None
     if "bbox" in anns[0] and not anns[0]["bbox"] == []:
         for i, ann in enumerate(anns):
             bb = ann["bbox"]
@@ -215,21 +237,42 @@ def load_results(results, iou_type: str):
             ann["id"] = i + 1
             ann["iscrowd"] = 0
     elif "segmentation" in anns[0]:
+        from . import image, ops
+        on_device = []
         for i, ann in enumerate(anns):
             seg = ann["segmentation"]
             if _is_polygon(seg):
                 raise NotImplementedError("polygon segmentations are out of scope (rleFrPoly is not implemented): give RLE")
             h, w = _seg_size(seg)
-            from . import image
-            area, bbox = _rle_area_bbox(image.rle_counts(seg), h, w)
-            ann["area"] = np.uint32(area)
-            if "bbox" not in ann:
-                ann["bbox"] = np.array(bbox)
+            if on_gpu and isinstance(seg, dict) and image._string_of(seg) is not None:
+                on_device.append(i)
+            else:
+                area, bbox = _rle_area_bbox(image.rle_counts(seg), h, w)
+                ann["area"] = np.uint32(area)
+                if "bbox" not in ann:
+                    ann["bbox"] = np.array(bbox)
             ann["id"] = i + 1
             ann["iscrowd"] = 0
+        if on_device:
+            segs = [anns[i]["segmentation"] for i in on_device]
+            hs, ws = [int(s["size"][0]) for s in segs], [int(s["size"][1]) for s in segs]
+            num_runs, counts, status = image._strings_to_device([image._string_of(s) for s in segs], hs, ws, device)
+            sizes = torch.tensor([hs, ws], dtype=torch.int32).to(num_runs.device)
+            areas, bboxes = ops.rle_area_bbox(num_runs, counts, sizes[0], sizes[1])
+            back = torch.cat([num_runs[:, None], status[:, None], areas[:, None], bboxes], dim=1).cpu().numpy()   # the one copy back
+            for k in np.nonzero(back[:, 0] < 0)[0].tolist():
+                raise image._string_error(int(back[k, 1]), f"result {on_device[k]}: the segmentation")
+            area_u, boxes = back[:, 2].astype(np.uint32), back[:, 3:7].astype(np.float64)
+            for k, i in enumerate(on_device):
+                ann = anns[i]
+                ann["area"] = area_u[k]
+                if "bbox" not in ann:
+                    ann["bbox"] = boxes[k].copy()
+            decoded = _Decoded((num_runs, counts), back[:, 0].copy(), back[:, 1].copy(),
+                               {anns[i]["id"]: k for k, i in enumerate(on_device)})
     else:
         raise ValueError("result records carry neither 'bbox' nor 'segmentation'")
-    return anns
+    return anns, decoded
 
 
 def _polygon_parts(ann):
@@ -279,12 +322,14 @@ def _polygon_table(anns, sizes, device):
     return ops.rle_merge(num_runs, counts, goff, intersect=False, capacity=merged_capacity)
 
 
-def ann_to_rle(gt, device="cuda:0"):
+def ann_to_rle(gt, device="cuda:0", compress: bool = False):
     """COCO.annToRLE (pycocotools/coco.py:406-425) over a whole data set: → a copy of the data set dict (or of the file at the
     path `gt`) in which every list (polygon) segmentation is {"size": [h, w], "counts": [run lengths]} of its image's height /
     width — the union of its parts, rleFrPoly + rleMerge, the reference codec's bits; dict segmentations are left as they are.
     The whole data set costs one ops.rle_from_poly call, one ops.rle_merge call and one device-to-host copy. ValueError, naming
-    the annotation id, for a list segmentation frPyObjects would not take as polygons (_polygon_parts)."""
+    the annotation id, for a list segmentation frPyObjects would not take as polygons (_polygon_parts).
+    compress=True: "counts" is the compressed string (bytes) annToRLE itself returns — ops.rle_to_string on the merged table, one
+    read of the total length and, again, one device-to-host copy."""
     if isinstance(gt, str):
         with open(gt) as fh:
             gt = json.load(fh)
@@ -296,6 +341,15 @@ def ann_to_rle(gt, device="cuda:0"):
         return out
     sizes = [size_of[a["image_id"]] for a in poly]
     num_runs, counts = _polygon_table(poly, sizes, device)
+    if compress:
+        from . import ops
+        chars, str_off = ops.rle_to_string(num_runs, counts)
+        packed = torch.cat([str_off.view(torch.uint8), chars]).cpu().numpy()      # the one copy: offsets, then the characters
+        head = 8 * (len(poly) + 1)
+        off = (packed[:head].view(np.int64) + head).tolist()
+        for k, (a, (h, w)) in enumerate(zip(poly, sizes)):
+            a["segmentation"] = {"size": [h, w], "counts": packed[off[k]:off[k + 1]].tobytes()}
+        return out
     live = torch.arange(counts.size(1), device=counts.device)[None, :] < num_runs[:, None]
     packed = torch.cat([num_runs, counts[live]]).cpu().numpy()          # the one copy: run counts, then the runs that exist
     nr = packed[:len(poly)].astype(np.int64)
@@ -306,16 +360,79 @@ def ann_to_rle(gt, device="cuda:0"):
     return out
 
 
+def _device_table(flat, skip, dev, decoded=None):
+    """The run-list table of the segmentations of `flat` (annotations in computeIoU's order) on the device, compressed strings
+    decoded THERE: rows _load already decoded (decoded: its _Decoded, keyed by record id) are gathered from its table with an index tensor, the
+    other compressed strings go through one ops.rle_from_string call, count lists and dense masks keep _seg_counts. skip[i]: a
+    row left empty (a polygon, filled in later). The checks of image._checked_counts — the runs cover the mask, only a leading
+    run is empty — come from the status the kernel wrote, with its errors."""
+    from . import image
+    errors, host_rows, host_idx, pre_idx, pre_row, new_idx = {}, [], [], [], [], []
+    for i, x in enumerate(flat):
+        if skip is not None and skip[i]:
+            continue
+        seg = x["segmentation"]
+        if isinstance(seg, dict) and image._string_of(seg) is not None:
+            k = decoded.row_of.get(x["id"]) if decoded is not None else None
+            if k is None:
+                new_idx.append(i)
+            else:
+                pre_idx.append(i)
+                pre_row.append(k)
+        else:
+            try:
+                host_rows.append(_seg_counts(seg, i, dev))
+                host_idx.append(i)
+            except ValueError as e:
+                errors[i] = e
+    parts = []
+    if host_rows:
+        parts.append((host_idx, *image._pack_table(host_rows, dev)))
+
+    def check(idx, rows, runs, status, counts):
+        for j in np.nonzero(status[rows])[0].tolist():
+            i, k = idx[j], rows[j]
+            h, w = _seg_size(flat[i]["segmentation"])
+            errors[i] = image._string_error(int(status[k]), f"rle_table: mask {i}") or \
+                image._run_errors(int(status[k]), i, h, w, lambda: counts[k, :int(runs[k])].cpu().numpy().view(np.uint32))
+
+    if pre_idx:
+        rows = np.asarray(pre_row, dtype=np.int64)
+        check(pre_idx, rows, decoded.runs, decoded.status, decoded.table[1])
+        at = torch.from_numpy(rows).to(dev)
+        parts.append((pre_idx, decoded.table[0][at], decoded.table[1][at]))
+    if new_idx:
+        segs = [flat[i]["segmentation"] for i in new_idx]
+        nr, cnt, status = image._strings_to_device([image._string_of(s) for s in segs], [int(s["size"][0]) for s in segs],
+                                                   [int(s["size"][1]) for s in segs], dev)
+        back = torch.stack([nr, status]).cpu().numpy()
+        check(new_idx, np.arange(len(new_idx)), back[0], back[1], cnt)
+        parts.append((new_idx, nr, cnt))
+    if errors:
+        raise errors[min(errors)]
+    return image._merge_tables(len(flat), parts, dev)
+
+
 def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: str = "error") -> CocoEval:
     """COCOeval(COCO(gt), COCO(gt).loadRes(results), iou_type) → evaluate(), accumulate(), summarize().
     gt: a COCO dataset dict (images, annotations, categories) or its path; results: the list predict.py --coco-json writes, or
     its path. Ground-truth segmentations (iou_type="segm"): compressed-string RLE, count-list RLE or a dense mask array;
     polygons raise NotImplementedError with polygons="error" (the default) and are rasterised on the GPU with
     polygons="rasterize" (annToRLE: ops.rle_from_poly + ops.rle_merge, the rows staying on the device for ops.rle_iou).
-    iou_type="bbox" never looks at segmentations."""
+    iou_type="bbox" never looks at segmentations. Compressed strings, of results and of ground truth, are decoded on the GPU,
+    each once (_load's device route, _device_table)."""
+    return _evaluate(gt, results, iou_type, device, polygons, "device")
+
+
+def _evaluate(gt, results, iou_type, device, polygons, codec):
+    """evaluate(); codec = "device" decodes compressed strings on the GPU, "host" is the per-character route of image.rle_counts
+    that load_results(device=None) and rle_table(device="cpu") still are — kept so that tools/codec_microbench.py and the tests
+    can compare the two in one process. Every number is the same."""
     from . import image, ops
     if polygons not in ("error", "rasterize"):
         raise ValueError(f"polygons={polygons!r}: 'error' or 'rasterize'")
+    if codec not in ("device", "host"):
+        raise ValueError(f"codec={codec!r}: 'device' or 'host'")
     p = Params(iou_type)
     if isinstance(gt, str):
         with open(gt) as fh:
@@ -324,7 +441,7 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: 
     p.imgIds = list(np.unique(img_ids))
     p.catIds = list(np.unique([c["id"] for c in gt["categories"]]))
     p.maxDets = sorted(p.maxDets)
-    dts_all = load_results(results, iou_type)
+    dts_all, decoded = _load(results, iou_type, device if codec == "device" and iou_type == "segm" else None)
     if not set(a["image_id"] for a in dts_all) <= set(img_ids):
         raise ValueError("Results do not correspond to current coco set")
 
@@ -376,14 +493,18 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: 
             size_of = {img["id"]: (int(img["height"]), int(img["width"])) for img in gt["images"]
                        if "height" in img and "width" in img}
             ann_size = lambda x: size_of[x["image_id"]] if _is_polygon(x["segmentation"]) else _seg_size(x["segmentation"])
-            rows_d = [_seg_counts(d["segmentation"], i, dev) for i, d in enumerate(dt_flat)]
             is_poly = np.array([_is_polygon(g["segmentation"]) for g in gt_flat], dtype=bool)
-            rows_g = [np.zeros(0, np.uint32) if is_poly[i] else _seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
+            if codec == "device":
+                dt_table = _device_table(dt_flat, None, dev, decoded)
+                gt_table = _device_table(gt_flat, is_poly, dev)
+            else:
+                rows_d = [_seg_counts(d["segmentation"], i, dev) for i, d in enumerate(dt_flat)]
+                rows_g = [np.zeros(0, np.uint32) if is_poly[i] else _seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
+                dt_table, gt_table = image._pack_table(rows_d, dev), image._pack_table(rows_g, dev)
             for k, key in enumerate(keys):
                 sizes = {ann_size(x) for x in dts[key] + gts[key]}
                 if len(sizes) > 1:
                     raise ValueError(f"image {key[0]}, category {key[1]}: masks of different sizes {sorted(sizes)}")
-            gt_table = image._pack_table(rows_g, dev)
             if is_poly.any():
                 # annToRLE on the device; the rows go into the ground-truth table there (one scalar comes back: the longest row)
                 poly_anns = [g for g, f in zip(gt_flat, is_poly) if f]
@@ -397,7 +518,7 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: 
                 g_counts[idx, :width] = torch.where(live, p_counts[:, :width], torch.zeros((), dtype=torch.int32, device=dev))
                 g_runs[idx] = p_runs
                 gt_table = (g_runs, g_counts)
-            ious_dev = ops.rle_iou(image._pack_table(rows_d, dev), gt_table, dev_of(iscrowd), *offs, out_len=out_len)
+            ious_dev = ops.rle_iou(dt_table, gt_table, dev_of(iscrowd), *offs, out_len=out_len)
         else:
             boxes = lambda anns: np.array([[float(v) for v in x["bbox"]] for x in anns], dtype=np.float64).reshape(-1, 4)
             ious_dev = ops.bbox_iou(dev_of(boxes(dt_flat)), dev_of(boxes(gt_flat)), dev_of(iscrowd), *offs, out_len=out_len)

@@ -146,7 +146,8 @@ class RleMasks:
     def to_coco(self):
         """→ [{"size": [h, w], "counts": bytes}] per mask: the dict maskUtils.encode returns (pycocotools' compressed RLE).
         The string characters are gathered on the device and come to the host in ONE small copy together with the lengths
-        (a few KB per mask instead of h*w bytes). A mask that did not fit the encode's capacity has no string: RuntimeError."""
+        (a few KB per mask instead of h*w bytes). A mask that did not fit the encode's capacity has no string: RuntimeError;
+        so has a row of a table that was refused (num_runs -1) or has runs and no characters (rle_masks_from_table)."""
         n = len(self)
         if n == 0:
             return []
@@ -154,12 +155,22 @@ class RleMasks:
         head = torch.stack([self.num_runs, self.string_bytes]).contiguous().view(torch.uint8).reshape(-1)
         packed = torch.cat([head, self.strings[live]]).cpu().numpy()
         runs, nbytes = packed[:8 * n].view(np.int32).reshape(2, n)
+        if (runs < 0).any():
+            raise RuntimeError(f"RleMasks.to_coco: masks {np.nonzero(runs < 0)[0].tolist()} were refused (num_runs -1): they have "
+                               "no runs and no string")
         if (runs > self.capacity).any():
             raise RuntimeError(f"RleMasks.to_coco: masks {np.nonzero(runs > self.capacity)[0].tolist()} have more runs than the "
                                f"capacity {self.capacity} they were encoded with; encode again with capacity >= {int(runs.max())}")
+        if ((runs > 0) & (nbytes == 0)).any():
+            raise RuntimeError(f"RleMasks.to_coco: masks {np.nonzero((runs > 0) & (nbytes == 0))[0].tolist()} have runs and no string "
+                               "(a refused row, or a string longer than 6 characters per run)")
         ends = 8 * n + np.cumsum(nbytes, dtype=np.int64)
         h, w = self.size
         return [{"size": [h, w], "counts": packed[e - b:e].tobytes()} for b, e in zip(nbytes.tolist(), ends.tolist())]
+
+    def decode(self) -> torch.Tensor:
+        """maskUtils.decode: uint8 [N,h,w] on the device, row-major, 0 / 1 (ops.rle_decode)."""
+        return ops.rle_decode(self.num_runs, self.counts, self.size[0], self.size[1])
 
     def iou(self, other, iscrowd=None) -> torch.Tensor:
         """maskUtils.iou(self, other, iscrowd): float64 [len(self), len(other)] on the device, the bits of rleIou. `other` is an
@@ -180,6 +191,21 @@ def rle_masks(masks: torch.Tensor, threshold: int = 0) -> RleMasks:
         if longest > enc[1].size(1):
             enc = ops.rle_encode(masks, threshold, capacity=longest)
     return RleMasks(masks.shape[-2:], *enc)
+
+
+def rle_masks_from_table(size, num_runs: torch.Tensor, counts: torch.Tensor) -> RleMasks:
+    """A run-list table of masks of ONE size (h, w) on the device — what ops.rle_from_poly / ops.rle_merge / rle_table return — as
+    an RleMasks: strings, string_bytes, areas and bboxes come from ops.rle_to_string and ops.rle_area_bbox, so to_coco() gives the
+    dicts maskUtils.encode would. No host synchronisation and no packed intermediate: the kernel writes each row's characters (at
+    most 6 per run for masks of up to 2^28 pixels) straight into the [N, 6*capacity] layout (ops.rle_to_string_rows). A row that
+    was refused or is over its capacity keeps its num_runs and has string_bytes 0, area -1 and bbox -1; to_coco() raises on it."""
+    h, w = int(size[0]), int(size[1])
+    num_runs, counts = ops._rle_table((num_runs, counts), "rle_masks_from_table")
+    n, cap, dev = num_runs.size(0), counts.size(1), num_runs.device
+    sizes = torch.tensor([h, w], dtype=torch.int32, device=dev)
+    areas, bboxes = ops.rle_area_bbox(num_runs, counts, sizes[0].expand(n).contiguous(), sizes[1].expand(n).contiguous())
+    strings, string_bytes = ops.rle_to_string_rows(num_runs, counts)
+    return RleMasks((h, w), num_runs, counts, strings, string_bytes, areas, bboxes)
 
 
 def rle_counts(obj) -> np.ndarray:
@@ -234,13 +260,124 @@ def _pack_table(rows, device, capacity=None):
     return torch.from_numpy(num_runs).to(device), torch.from_numpy(table.view(np.int32)).to(device)
 
 
+def _string_of(obj):
+    """The compressed string of an RLE entry (a dict or the string itself) as bytes; None for a count list."""
+    c = obj["counts"] if isinstance(obj, dict) else obj
+    if isinstance(c, str):
+        return c.encode("ascii")
+    if isinstance(c, (bytes, bytearray)):
+        return bytes(c)
+    return None
+
+
+def _strings_to_device(strs, hs, ws, device):
+    """Compressed strings (bytes) with their sizes → ONE ops.rle_from_string call: (num_runs int32 [n], counts int32 [n,capacity],
+    status int32 [n]) on the device, every well-formed string fitting. The capacity is the host's token count (numpy, one
+    cumulative sum: ops.rle_string_tokens); two host-to-device copies (the characters; offsets and sizes)."""
+    device = torch.device(device)
+    n = len(strs)
+    data = np.frombuffer(b"".join(strs), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, strs), dtype=np.int64, count=n), out=off[1:])
+    capacity = max(1, int(ops.rle_string_tokens(data, off).max())) if n else 1
+    ints = torch.from_numpy(np.concatenate([off, np.asarray(hs, dtype=np.int64), np.asarray(ws, dtype=np.int64)])).to(device)
+    sizes = ints[n + 1:].to(torch.int32)
+    return ops.rle_from_string(torch.from_numpy(data.copy()).to(device), ints[:n + 1], sizes[:n], sizes[n:], capacity=capacity)
+
+
+def _string_error(st: int, what: str):
+    """The ValueError of a string ops.rle_from_string refused (status bits), or None."""
+    for bit, why in ((ops.RLE_BAD_SIZE, "a height or width outside [1, 16384]"),
+                     (ops.RLE_BAD_BYTE, "a character outside '0'..'o' (bytes 48..111) in its compressed string"),
+                     (ops.RLE_LONG_TOKEN, "a run of more than 6 characters in its compressed string"),
+                     (ops.RLE_OPEN_TOKEN, "a compressed string that ends inside a run"),
+                     (ops.RLE_BAD_OFFSETS, "string offsets outside the buffer")):
+        if st & bit:
+            return ValueError(f"{what} has {why}")
+    return None
+
+
+def _run_errors(st: int, i: int, h: int, w: int, row):
+    """The ValueError _checked_counts raises for a written row with status bits set, in its order and wording, or None. row():
+    the row's counts on the host (fetched on this error path only)."""
+    if st & ops.RLE_PIXEL_SUM:
+        return ValueError(f"rle_table: the runs of mask {i} cover {int(row().astype(np.int64).sum())} pixels, the mask has {h} x {w}")
+    if st & ops.RLE_EMPTY_RUN:
+        return ValueError(f"rle_table: mask {i} has an empty run after the first one")
+    return None
+
+
+def _merge_tables(n: int, parts, device, capacity=None):
+    """parts: [(indices (numpy int64), num_runs [k], counts [k,c])] on the device, disjoint, covering what they cover of n rows →
+    one zero-padded table (num_runs int32 [n], counts int32 [n,capacity]); rows no part covers are empty (num_runs 0)."""
+    device = torch.device(device)
+    cap = max([1] + [int(c.size(1)) for _, _, c in parts]) if capacity is None else int(capacity)
+    num_runs = torch.zeros(n, dtype=torch.int32, device=device)
+    counts = torch.zeros(n, cap, dtype=torch.int32, device=device)
+    for idx, nr, c in parts:
+        if len(idx) == 0:
+            continue
+        at = torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(device)
+        width = min(cap, int(c.size(1)))
+        live = torch.arange(width, device=device)[None, :] < nr[:, None]
+        counts[at, :width] = torch.where(live, c[:, :width], torch.zeros((), dtype=torch.int32, device=device))
+        num_runs[at] = nr
+    return num_runs, counts
+
+
+def _rle_table_device(objs, h: int, w: int, device, capacity):
+    errors, strs, str_idx, rows, row_idx = {}, [], [], [], []
+    for i, obj in enumerate(objs):
+        s = _string_of(obj)
+        try:
+            if s is None:
+                rows.append(_checked_counts(obj, h, w, i))
+                row_idx.append(i)
+            elif isinstance(obj, dict) and [int(v) for v in obj["size"]] != [h, w]:
+                raise ValueError(f"rle_table: mask {i} is {list(obj['size'])}, the table is {[h, w]}")
+            else:
+                strs.append(s)
+                str_idx.append(i)
+        except ValueError as e:
+            errors[i] = e
+    parts = []
+    if rows:
+        parts.append((row_idx, *_pack_table(rows, device)))
+    if strs:
+        nr, cnt, status = _strings_to_device(strs, [h] * len(strs), [w] * len(strs), device)
+        back = torch.stack([nr, status]).cpu().numpy()          # the one read-back
+        for k in np.nonzero(back[1])[0].tolist():
+            i, st = str_idx[k], int(back[1][k])
+            errors[i] = _string_error(st, f"rle_table: mask {i}") or \
+                _run_errors(st, i, h, w, lambda: cnt[k, :int(back[0][k])].cpu().numpy().view(np.uint32))
+        parts.append((str_idx, nr, cnt))
+    if errors:
+        raise errors[min(errors)]
+    longest = max([1] + [int(c.size(1)) for _, _, c in parts])
+    if capacity is not None and int(capacity) < longest:
+        raise ValueError(f"rle_table: capacity {capacity} is less than the longest mask's {longest} runs")
+    return _merge_tables(len(objs), parts, device, capacity)
+
+
 def rle_table(objs, size, device="cuda:0", capacity=None):
     """A list of COCO RLEs (dicts {"size", "counts"}, compressed strings or count lists) of ONE size (h, w) → (num_runs int32
-    [N], counts int32 [N,capacity]) on the device: the table layout ops.rle_encode writes and ops.rle_iou reads, built with one
-    host-to-device copy. Every entry goes through rle_counts and is checked against rle_iou's contract: the runs cover exactly
-    h*w pixels and only the leading run may be empty (ValueError otherwise)."""
+    [N], counts int32 [N,capacity]) on the device: the table layout ops.rle_encode writes and ops.rle_iou reads. Every entry is
+    checked against rle_iou's contract: the runs cover exactly h*w pixels and only the leading run may be empty (ValueError
+    otherwise). On a GPU device all compressed strings are decoded there in ONE ops.rle_from_string call (no per-character host
+    work; a malformed string — a byte outside 48..111, a run of more than 6 characters, an end inside a run — is a ValueError
+    too), count lists are packed on the host, the two are merged by index on the device, and the checks read num_runs / status
+    back once. device="cpu": every entry goes through rle_counts on the host, and the library is not touched."""
     h, w = int(size[0]), int(size[1])
+    if torch.device(device).type != "cpu":
+        return _rle_table_device(list(objs), h, w, device, capacity)
     return _pack_table([_checked_counts(obj, h, w, i) for i, obj in enumerate(objs)], device, capacity)
+
+
+def rle_decode_masks(objs, size, device="cuda:0") -> torch.Tensor:
+    """COCO.annToMask for a list of RLEs of one size (dicts, compressed strings or count lists): uint8 [N,h,w] on the device,
+    row-major, 0 / 1 — rle_table, then ops.rle_decode."""
+    num_runs, counts = rle_table(objs, size, device)
+    return ops.rle_decode(num_runs, counts, int(size[0]), int(size[1]))
 
 
 def rle_decode(obj, size=None) -> np.ndarray:

@@ -32,7 +32,8 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
-           "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge"]
+           "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
+           "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1544,6 +1545,178 @@ _LIB.impl("rle_from_poly", lambda xy, *a: _need_gpu(xy), "CPU")
 _LIB.define("rle_merge(Tensor num_runs, Tensor counts, Tensor group_off, bool intersect=False, int? capacity=None) -> (Tensor, Tensor)")
 _LIB.impl("rle_merge", rle_merge, "CUDA")
 _LIB.impl("rle_merge", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# The COCO RLE codec on tables: rleFrString, rleToString, rleArea + rleToBbox, rleDecode (csrc/codec.hip)
+# --------------------------------------------------------------------------------------------------
+# status bits of rle_from_string (include/maskrcnn_hip.h): the first five refuse the row (num_runs = -1), the last two flag it
+RLE_BAD_BYTE, RLE_LONG_TOKEN, RLE_OPEN_TOKEN, RLE_BAD_SIZE, RLE_BAD_OFFSETS = 1, 2, 4, 8, 64
+RLE_EMPTY_RUN, RLE_PIXEL_SUM = 16, 32
+
+
+def rle_string_tokens(data, str_off) -> np.ndarray:
+    """Tokens (= runs) of every string of a packed HOST buffer — numpy uint8 [total] and offsets [n+1] — as int64 [n]: the
+    characters with ((b - 48) & 0x20) == 0, counted with one cumulative sum read at the offsets. No Python loop per character or
+    per string; this is how a front end finds the capacity for rle_from_string."""
+    data = np.asarray(data, dtype=np.uint8).reshape(-1)
+    off = np.asarray(str_off, dtype=np.int64).reshape(-1)
+    ends = np.concatenate([[0], np.cumsum(((data.astype(np.int16) - 48) & 0x20) == 0, dtype=np.int64)])
+    return ends[off[1:]] - ends[off[:-1]]
+
+
+def _sizes(who, heights, widths, n: int):
+    for name, t in (("heights", heights), ("widths", widths)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n:
+            raise RuntimeError(f"{who}: {name} must be an int32 [{n}] tensor, got {t.dtype} {tuple(t.shape)}")
+    return heights.contiguous(), widths.contiguous()
+
+
+@_on_device
+def rle_from_string(bytes: torch.Tensor, str_off: torch.Tensor, heights: torch.Tensor, widths: torch.Tensor,
+                    capacity: int | None = None):
+    """maskUtils.frPyObjects on compressed strings (rleFrString of cocoapi/common/maskApi.c:218-231, the same bits) for n strings
+    in one call on the GPU. bytes uint8 [total] and str_off int64 [n+1]: string i is bytes[str_off[i]:str_off[i+1]], packed,
+    no terminator; heights / widths int32 [n] serve the checks only. All device tensors. → (num_runs int32 [n], counts int32
+    [n,capacity], status int32 [n]); the status bits are RLE_* above: a malformed string (a byte outside 48..111, a token of more
+    than 6 characters, an end inside a token, a size outside [1, 16384]) reports num_runs = -1 and its row is not written; an
+    empty run after the first and a wrong pixel sum are flagged and the row is written; a string with more runs than capacity
+    reports its true num_runs and its row is not written (uninitialised memory here). capacity is required: the op never
+    synchronises, and the characters it would have to count live on the device — a front end counts them on its host copy
+    (rle_string_tokens)."""
+    _need_gpu(bytes, str_off, heights, widths)
+    if capacity is None:
+        raise RuntimeError("rle_from_string: capacity is required (count the tokens on the host copy: ops.rle_string_tokens)")
+    if bytes.dtype != torch.uint8 or bytes.dim() != 1:
+        raise RuntimeError(f"rle_from_string: bytes must be a uint8 vector, got {bytes.dtype} {tuple(bytes.shape)}")
+    if str_off.dtype != torch.int64 or str_off.dim() != 1 or str_off.numel() < 1:
+        raise RuntimeError(f"rle_from_string: str_off must be an int64 [n+1] tensor, got {str_off.dtype} {tuple(str_off.shape)}")
+    n = str_off.numel() - 1
+    heights, widths = _sizes("rle_from_string", heights, widths, n)
+    bytes, str_off = bytes.contiguous(), str_off.contiguous()
+    capacity = int(capacity)
+    dev = str_off.device
+    num_runs = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(n, max(capacity, 0), dtype=torch.int32, device=dev)
+    total = bytes.numel()
+    _launch(lib.mrcnn_rle_from_string,
+            (bytes.data_ptr() if total else None, total, str_off.data_ptr(), _ptr(heights) if n else None,
+             _ptr(widths) if n else None, n, capacity, _ptr(num_runs) if n else None, _ptr(counts) if n else None,
+             _ptr(status) if n else None, _stream()),
+            lambda: (0, (n, total, capacity), total + 4 * counts.numel(), "rle_from_string"))
+    return num_runs, counts, status
+
+
+@_on_device
+def rle_area_bbox(num_runs: torch.Tensor, counts: torch.Tensor, heights: torch.Tensor, widths: torch.Tensor):
+    """maskUtils.area and maskUtils.toBbox (rleArea, rleToBbox of maskApi.c:72-75, :133-147, the same values) of every row of a
+    table (num_runs int32 [N], counts [N,capacity]) with per-row heights / widths int32 [N] → (areas int32 [N], bboxes int32
+    [N,4] as (x, y, w, h)): what rle_encode returns for dense masks. A row that was refused or is over its capacity gets -1s."""
+    num_runs, counts = _rle_table((num_runs, counts), "rle_area_bbox")
+    _need_gpu(heights, widths)
+    n, dev = num_runs.size(0), num_runs.device
+    heights, widths = _sizes("rle_area_bbox", heights, widths, n)
+    areas = torch.empty(n, dtype=torch.int32, device=dev)
+    bboxes = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    if n:
+        _launch(lib.mrcnn_rle_area_bbox,
+                (num_runs.data_ptr(), counts.data_ptr(), n, counts.size(1), heights.data_ptr(), widths.data_ptr(), areas.data_ptr(),
+                 bboxes.data_ptr(), _stream()),
+                lambda: (0, (n, counts.size(1), 1), 4 * counts.numel(), "rle_area_bbox"))
+    return areas, bboxes
+
+
+@_on_device
+def rle_to_string(num_runs: torch.Tensor, counts: torch.Tensor, total_bytes: int | None = None):
+    """rleToString (maskApi.c:204-216, the same characters) of every row of a table → (bytes uint8 [total_bytes], str_off int64
+    [N+1]) on the device, packed: string i is bytes[str_off[i]:str_off[i+1]]. str_off always holds the true offsets. With
+    total_bytes given the call never synchronises; rows that would cross the end of the buffer are not written (str_off[N] >
+    total_bytes tells). total_bytes=None costs one host read of the scanned total and allocates exactly. A row that was refused
+    or is over its capacity has an empty string."""
+    num_runs, counts = _rle_table((num_runs, counts), "rle_to_string")
+    n, dev = num_runs.size(0), num_runs.device
+    str_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    nbytes = int(lib.mrcnn_rle_to_string_workspace_bytes(n))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    have = 0
+    if total_bytes is None:
+        _to_string_launch(num_runs, counts, None, 0, have, str_off, ws, nbytes)      # offsets only
+        total_bytes, have = int(str_off[n]), 1                                     # the one host read; the write pass alone follows
+    out = torch.empty(max(int(total_bytes), 0), dtype=torch.uint8, device=dev)
+    _to_string_launch(num_runs, counts, out, 0, have, str_off, ws, nbytes)
+    return out, str_off
+
+
+def _to_string_launch(num_runs, counts, buf, row_stride, have_offsets, str_off, ws, nbytes):
+    n = num_runs.size(0)
+    _launch(lib.mrcnn_rle_to_string,
+            (_ptr(num_runs) if n else None, _ptr(counts) if n else None, n, counts.size(1),
+             buf.data_ptr() if buf is not None and buf.numel() else None, buf.numel() if buf is not None else 0, int(row_stride),
+             int(have_offsets), str_off.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (n, counts.size(1), 1), 4 * counts.numel(), "rle_to_string"))
+
+
+@_on_device
+def rle_to_string_rows(num_runs: torch.Tensor, counts: torch.Tensor, row_stride: int | None = None):
+    """rle_to_string into the ENCODER's layout: → (strings uint8 [N,row_stride], string_bytes int32 [N]), row i holding its
+    characters from column 0 (the rest zero) — what rle_encode returns, written by the kernel itself, no packed intermediate and
+    no host synchronisation. row_stride defaults to 6*capacity (6 characters a run cover masks of up to 2^28 pixels). A row whose
+    string is longer than row_stride, or that was refused or is over its capacity, has string_bytes 0 and an all-zero row."""
+    num_runs, counts = _rle_table((num_runs, counts), "rle_to_string_rows")
+    n, dev = num_runs.size(0), num_runs.device
+    stride = 6 * counts.size(1) if row_stride is None else int(row_stride)
+    if stride < 1:
+        raise RuntimeError(f"rle_to_string_rows: row_stride={stride} must be >= 1")
+    strings = torch.zeros(n, stride, dtype=torch.uint8, device=dev)
+    str_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    nbytes = int(lib.mrcnn_rle_to_string_workspace_bytes(n))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _to_string_launch(num_runs, counts, strings, stride, 0, str_off, ws, nbytes)
+    lengths = str_off[1:] - str_off[:-1]
+    return strings, torch.where(lengths <= stride, lengths, torch.zeros_like(lengths)).to(torch.int32)
+
+
+@_on_device
+def rle_decode(num_runs: torch.Tensor, counts: torch.Tensor, height: int, width: int, out: torch.Tensor | None = None):
+    """maskUtils.decode (rleDecode of maskApi.c:43-47) of every row of a table of H x W masks → uint8 [N,H,W] on the device,
+    row-major, 0 / 1 — what rle_encode reads. `out`: a uint8 [N,H,W] tensor to fill (unit last stride, free image and row
+    strides); every byte of it is written. Runs past H*W are clipped, pixels the runs do not reach are 0, and a row that was
+    refused or is over its capacity decodes to zeros."""
+    num_runs, counts = _rle_table((num_runs, counts), "rle_decode")
+    n, dev = num_runs.size(0), num_runs.device
+    h, w = int(height), int(width)
+    if out is None:
+        out = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    _need_gpu(out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w) or (w > 1 and out.stride(2) != 1):
+        raise RuntimeError(f"rle_decode: out must be a uint8 [{n},{h},{w}] tensor with unit last stride, got {out.dtype} "
+                           f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    if n == 0:
+        return out
+    image_stride = out.stride(0) if n > 1 else 0
+    row_stride = out.stride(1) if h > 1 else w
+    nbytes = int(lib.mrcnn_rle_decode_workspace_bytes(n, counts.size(1)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _launch(lib.mrcnn_rle_decode_u8,
+            (num_runs.data_ptr(), counts.data_ptr(), n, counts.size(1), h, w, out.data_ptr(), image_stride, row_stride,
+             ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (n, h, w), n * h * w + 4 * counts.numel(), "rle_decode"))
+    return out
+
+
+_LIB.define("rle_from_string(Tensor bytes, Tensor str_off, Tensor heights, Tensor widths, int? capacity=None) -> (Tensor, Tensor, Tensor)")
+_LIB.impl("rle_from_string", rle_from_string, "CUDA")
+_LIB.impl("rle_from_string", lambda bytes, *a: _need_gpu(bytes), "CPU")
+_LIB.define("rle_area_bbox(Tensor num_runs, Tensor counts, Tensor heights, Tensor widths) -> (Tensor, Tensor)")
+_LIB.impl("rle_area_bbox", rle_area_bbox, "CUDA")
+_LIB.impl("rle_area_bbox", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
+_LIB.define("rle_to_string(Tensor num_runs, Tensor counts, int? total_bytes=None) -> (Tensor, Tensor)")
+_LIB.impl("rle_to_string", rle_to_string, "CUDA")
+_LIB.impl("rle_to_string", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
+_LIB.define("rle_decode(Tensor num_runs, Tensor counts, int height, int width) -> Tensor")   # `out` is the Python binding's
+_LIB.impl("rle_decode", lambda num_runs, counts, height, width: rle_decode(num_runs, counts, height, width), "CUDA")
+_LIB.impl("rle_decode", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------
