@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import inspect
 import json
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -186,12 +187,8 @@ def _seg_size(seg):
 
 
 def _seg_counts(seg, i: int, device) -> np.ndarray:
-    """Run lengths of one segmentation: an RLE dict (compressed string or count list), or a dense mask array, which is
-    encoded on the GPU (ops.rle_encode)."""
+    """Run lengths of a segmentation that is no RLE dict: a dense mask array, which is encoded on the GPU (ops.rle_encode)."""
     from . import image
-    if isinstance(seg, dict):
-        h, w = _seg_size(seg)
-        return image._checked_counts(seg, h, w, i)
     if isinstance(seg, (np.ndarray, torch.Tensor)):
         t = torch.as_tensor(np.ascontiguousarray(seg) if isinstance(seg, np.ndarray) else seg)
         if t.dtype not in (torch.uint8, torch.bool):
@@ -199,14 +196,6 @@ def _seg_counts(seg, i: int, device) -> np.ndarray:
         enc = image.rle_masks(t.to(device)[None])
         return enc.counts[0, :int(enc.num_runs[0])].cpu().numpy().view(np.uint32)
     raise TypeError(f"segmentation {i}: expected an RLE dict or a dense mask array, got {type(seg).__name__}")
-
-
-class _Decoded:
-    """What _load's device route decoded on the GPU: table = (num_runs, counts) of the compressed strings on the device, runs /
-    status their host copies (int32 [S]), row_of {record id (loadRes' i + 1): row}."""
-
-    def __init__(self, table, runs, status, row_of):
-        self.table, self.runs, self.status, self.row_of = table, runs, status, row_of
 
 
 def load_results(results, iou_type: str, device=None):
@@ -219,7 +208,8 @@ def load_results(results, iou_type: str, device=None):
 
 
 def _load(results, iou_type: str, device=None):
-    """load_results → (records, a _Decoded with the table the device route made, or None)."""
+    """load_results → (records, what the device route decoded on the GPU or None: (an image._Decoded of the compressed strings,
+    {record id (loadRes' i + 1): its row}))."""
     decoded = None
     on_gpu = device is not None and torch.device(device).type != "cpu"
     if isinstance(results, str):
@@ -260,16 +250,16 @@ def _load(results, iou_type: str, device=None):
             sizes = torch.tensor([hs, ws], dtype=torch.int32).to(num_runs.device)
             areas, bboxes = ops.rle_area_bbox(num_runs, counts, sizes[0], sizes[1])
             back = torch.cat([num_runs[:, None], status[:, None], areas[:, None], bboxes], dim=1).cpu().numpy()   # the one copy back
-            for k in np.nonzero(back[:, 0] < 0)[0].tolist():
-                raise image._string_error(int(back[k, 1]), f"result {on_device[k]}: the segmentation")
+            table = image._Decoded(num_runs, counts, back[:, 0].copy(), back[:, 1].copy())
+            for k in np.nonzero(table.runs < 0)[0].tolist():
+                raise image._status_error(table, k, f"result {on_device[k]}: the segmentation")
             area_u, boxes = back[:, 2].astype(np.uint32), back[:, 3:7].astype(np.float64)
             for k, i in enumerate(on_device):
                 ann = anns[i]
                 ann["area"] = area_u[k]
                 if "bbox" not in ann:
                     ann["bbox"] = boxes[k].copy()
-            decoded = _Decoded((num_runs, counts), back[:, 0].copy(), back[:, 1].copy(),
-                               {anns[i]["id"]: k for k, i in enumerate(on_device)})
+            decoded = (table, {anns[i]["id"]: k for k, i in enumerate(on_device)})
     else:
         raise ValueError("result records carry neither 'bbox' nor 'segmentation'")
     return anns, decoded
@@ -360,57 +350,160 @@ def ann_to_rle(gt, device="cuda:0", compress: bool = False):
     return out
 
 
-def _device_table(flat, skip, dev, decoded=None):
-    """The run-list table of the segmentations of `flat` (annotations in computeIoU's order) on the device, compressed strings
-    decoded THERE: rows _load already decoded (decoded: its _Decoded, keyed by record id) are gathered from its table with an index tensor, the
-    other compressed strings go through one ops.rle_from_string call, count lists and dense masks keep _seg_counts. skip[i]: a
-    row left empty (a polygon, filled in later). The checks of image._checked_counts — the runs cover the mask, only a leading
-    run is empty — come from the status the kernel wrote, with its errors."""
+class _Groups(NamedTuple):
+    """What _group returns: keys, the sorted (image, category) pairs with an annotation or a detection; dts / gts {key: its
+    records}, the detections by descending score and cut at maxDets[-1]; dt_flat / gt_flat, the records of all keys in that
+    order; dt_n / gt_n int64 [K]; dt_off / gt_off int64 [K+1] into the flat lists, out_off int64 [K+1] into the flat IoU array
+    (dt_n * gt_n numbers a group); iscrowd / gt_ignore uint8 [M] and dt_area / gt_area float64 [N] / [M] of the flat lists."""
+    keys: list
+    dts: dict
+    gts: dict
+    dt_flat: list
+    gt_flat: list
+    dt_n: np.ndarray
+    gt_n: np.ndarray
+    dt_off: np.ndarray
+    gt_off: np.ndarray
+    out_off: np.ndarray
+    iscrowd: np.ndarray
+    gt_ignore: np.ndarray
+    dt_area: np.ndarray
+    gt_area: np.ndarray
+
+
+def _group(annotations, dts_all, p: Params, refuse_polygons: bool = False) -> _Groups:
+    """evaluate, stage 1 (host only): _prepare and computeIoU's ordering. refuse_polygons: a list segmentation among the grouped
+    ground truths is a NotImplementedError."""
+    # _prepare (:85-120): group by (image, category), keeping the data set's / the result file's order within a group
+    in_imgs, in_cats = set(p.imgIds), set(p.catIds)
+    gts, dts = {}, {}
+    for ann in annotations:
+        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
+            gts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
+    for ann in dts_all:
+        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
+            dts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
+    if refuse_polygons:
+        for anns in gts.values():
+            for ann in anns:
+                if _is_polygon(ann["segmentation"]):
+                    raise NotImplementedError(
+                        f"annotation {ann.get('id')}: polygon segmentations are out of scope (rleFrPoly is not implemented); "
+                        "give RLE ground truth, or evaluate iou_type='bbox'")
+
+    # computeIoU's ordering (:174-177): -score mergesort, cut at maxDets[-1]
+    keys = sorted(set(gts) | set(dts))
+    for key in keys:
+        d = dts.get(key, [])
+        inds = np.argsort([-x["score"] for x in d], kind="mergesort")
+        dts[key] = [d[i] for i in inds][:p.maxDets[-1]]
+        gts.setdefault(key, [])
+    dt_n = np.array([len(dts[key]) for key in keys], dtype=np.int64)
+    gt_n = np.array([len(gts[key]) for key in keys], dtype=np.int64)
+    offsets = lambda n: np.concatenate([[0], np.cumsum(n)])
+    dt_flat, gt_flat = [x for key in keys for x in dts[key]], [x for key in keys for x in gts[key]]
+    iscrowd = np.array([int(x["iscrowd"]) if "iscrowd" in x else 0 for x in gt_flat], dtype=np.uint8)
+    # gt['ignore'] = 'iscrowd' in gt and gt['iscrowd'] (:110)
+    gt_ignore = np.array([1 if ("iscrowd" in x and x["iscrowd"]) else 0 for x in gt_flat], dtype=np.uint8)
+    dt_area = np.array([float(x["area"]) for x in dt_flat], dtype=np.float64)
+    gt_area = np.array([float(x["area"]) for x in gt_flat], dtype=np.float64)
+    return _Groups(keys, dts, gts, dt_flat, gt_flat, dt_n, gt_n, offsets(dt_n), offsets(gt_n), offsets(dt_n * gt_n),
+                   iscrowd, gt_ignore, dt_area, gt_area)
+
+
+def _segm_tables(g: _Groups, images, decoded, dev, host_strings: bool):
+    """evaluate, stage 2: the run-list tables (num_runs, counts) of dt_flat and of gt_flat on the device, through
+    image._table_parts: RLE dicts are checked and their compressed strings decoded where host_strings says (detections _load
+    decoded already — decoded, what it returned — are gathered from its table), dense masks go through _seg_counts. Polygon
+    ground truths are rasterised on the device (_polygon_table) and are one more part of the ground-truth table's one merge."""
     from . import image
-    errors, host_rows, host_idx, pre_idx, pre_row, new_idx = {}, [], [], [], [], []
-    for i, x in enumerate(flat):
-        if skip is not None and skip[i]:
-            continue
-        seg = x["segmentation"]
-        if isinstance(seg, dict) and image._string_of(seg) is not None:
-            k = decoded.row_of.get(x["id"]) if decoded is not None else None
-            if k is None:
-                new_idx.append(i)
+    is_poly = np.array([_is_polygon(x["segmentation"]) for x in g.gt_flat], dtype=bool)
+    how = dict(other=lambda s, i: _seg_counts(s, i, dev), host_strings=host_strings)
+    if decoded is not None:
+        decoded = (decoded[0], {i: decoded[1][x["id"]] for i, x in enumerate(g.dt_flat) if x["id"] in decoded[1]})
+    dt_table = image._build_table([x["segmentation"] for x in g.dt_flat], None, dev, decoded=decoded, **how)
+    gt_parts = image._table_parts([x["segmentation"] for x in g.gt_flat], None, dev, skip=is_poly, **how)
+    size_of = {img["id"]: (int(img["height"]), int(img["width"])) for img in images if "height" in img and "width" in img}
+    ann_size = lambda x: size_of[x["image_id"]] if _is_polygon(x["segmentation"]) else _seg_size(x["segmentation"])
+    for key in g.keys:
+        sizes = {ann_size(x) for x in g.dts[key] + g.gts[key]}
+        if len(sizes) > 1:
+            raise ValueError(f"image {key[0]}, category {key[1]}: masks of different sizes {sorted(sizes)}")
+    capacity = None
+    if is_poly.any():
+        # annToRLE on the device. One scalar comes back, the longest row: rle_merge's own capacity is a loose bound, and
+        # ops.rle_iou's workspace and time would pay for it
+        poly_anns = [x for x, f in zip(g.gt_flat, is_poly) if f]
+        p_runs, p_counts = _polygon_table(poly_anns, [size_of[x["image_id"]] for x in poly_anns], dev)
+        capacity = max(int(p_runs.max()), image._widest(gt_parts))
+        gt_parts.append((np.nonzero(is_poly)[0], p_runs, p_counts))
+    return dt_table, image._merge_tables(len(g.gt_flat), gt_parts, dev, capacity)
+
+
+def _match_on_device(g: _Groups, p: Params, iou_type: str, tables, dev):
+    """evaluate, stage 3: ONE grouped IoU call (ops.rle_iou on tables = (dt_table, gt_table) for "segm", ops.bbox_iou on the
+    records' boxes for "bbox") and ONE ops.coco_match call → numpy: ious_flat float64 [out_off[-1]] (a group's IoUs at
+    out_off[k], ground truth slowest), dt_match int32 [A,T,N] and gt_match int32 [A,T,M] (1-based positions within the group, 0
+    = none), dt_ignore uint8 [A,T,N], gt_ignore uint8 [A,M]. No group: empty arrays, and the device is not touched."""
+    T, A = len(p.iouThrs), len(p.areaRng)
+    if not g.keys:
+        return (np.zeros(0), np.zeros((A, T, 0), np.int32), np.zeros((A, T, 0), np.int32), np.zeros((A, T, 0), np.uint8),
+                np.zeros((A, 0), np.uint8))
+    from . import ops
+    dev_of = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    offs = (dev_of(g.dt_off.astype(np.int32)), dev_of(g.gt_off.astype(np.int32)), dev_of(g.out_off.astype(np.int64)))
+    if iou_type == "segm":
+        ious_dev = ops.rle_iou(*tables, dev_of(g.iscrowd), *offs, out_len=int(g.out_off[-1]))
+    else:
+        boxes = lambda anns: np.array([[float(v) for v in x["bbox"]] for x in anns], dtype=np.float64).reshape(-1, 4)
+        ious_dev = ops.bbox_iou(dev_of(boxes(g.dt_flat)), dev_of(boxes(g.gt_flat)), dev_of(g.iscrowd), *offs, out_len=int(g.out_off[-1]))
+    match = ops.coco_match(ious_dev, *offs, dev_of(g.dt_area), dev_of(g.gt_area), dev_of(g.gt_ignore),
+                           dev_of(np.array(p.areaRng, dtype=np.float64)), dev_of(np.asarray(p.iouThrs, dtype=np.float64)))
+    return (ious_dev.cpu().numpy(), *[m.cpu().numpy() for m in match])
+
+
+def _rebuild(g: _Groups, p: Params, ious_flat, dt_match, gt_match, dt_ignore, gt_ignore):
+    """evaluate, stage 4 (host only): COCOeval.ious and COCOeval.evalImgs from the five arrays of _match_on_device → (ious
+    {(image_id, category_id): float64 [D,G] or []}, eval_imgs [K x A x I], category slowest: ids for positions, ground truths
+    listed regular first)."""
+    T, max_det = len(p.iouThrs), p.maxDets[-1]
+    index = {key: k for k, key in enumerate(g.keys)}
+    ious = {}
+    for img in p.imgIds:
+        for cat in p.catIds:
+            k = index.get((img, cat))
+            if k is None or g.dt_n[k] == 0 or g.gt_n[k] == 0:
+                ious[img, cat] = []
             else:
-                pre_idx.append(i)
-                pre_row.append(k)
-        else:
-            try:
-                host_rows.append(_seg_counts(seg, i, dev))
-                host_idx.append(i)
-            except ValueError as e:
-                errors[i] = e
-    parts = []
-    if host_rows:
-        parts.append((host_idx, *image._pack_table(host_rows, dev)))
+                ious[img, cat] = ious_flat[g.out_off[k]:g.out_off[k + 1]].reshape(int(g.gt_n[k]), int(g.dt_n[k])).T
 
-    def check(idx, rows, runs, status, counts):
-        for j in np.nonzero(status[rows])[0].tolist():
-            i, k = idx[j], rows[j]
-            h, w = _seg_size(flat[i]["segmentation"])
-            errors[i] = image._string_error(int(status[k]), f"rle_table: mask {i}") or \
-                image._run_errors(int(status[k]), i, h, w, lambda: counts[k, :int(runs[k])].cpu().numpy().view(np.uint32))
-
-    if pre_idx:
-        rows = np.asarray(pre_row, dtype=np.int64)
-        check(pre_idx, rows, decoded.runs, decoded.status, decoded.table[1])
-        at = torch.from_numpy(rows).to(dev)
-        parts.append((pre_idx, decoded.table[0][at], decoded.table[1][at]))
-    if new_idx:
-        segs = [flat[i]["segmentation"] for i in new_idx]
-        nr, cnt, status = image._strings_to_device([image._string_of(s) for s in segs], [int(s["size"][0]) for s in segs],
-                                                   [int(s["size"][1]) for s in segs], dev)
-        back = torch.stack([nr, status]).cpu().numpy()
-        check(new_idx, np.arange(len(new_idx)), back[0], back[1], cnt)
-        parts.append((new_idx, nr, cnt))
-    if errors:
-        raise errors[min(errors)]
-    return image._merge_tables(len(flat), parts, dev)
+    eval_imgs = []
+    for cat in p.catIds:
+        for a, rng in enumerate(p.areaRng):
+            for img in p.imgIds:
+                k = index.get((img, cat))
+                if k is None:
+                    eval_imgs.append(None)
+                    continue
+                d0, d1, g0, g1 = int(g.dt_off[k]), int(g.dt_off[k + 1]), int(g.gt_off[k]), int(g.gt_off[k + 1])
+                d, gg = g.dts[img, cat], g.gts[img, cat]
+                gt_ig = gt_ignore[a, g0:g1]
+                gtind = np.argsort(gt_ig, kind="mergesort")            # regular first, ignored last (:258)
+                gt_ids = np.array([x["id"] for x in gg], dtype=np.float64)
+                dt_ids = np.array([x["id"] for x in d], dtype=np.float64)
+                pos_d = dt_match[a, :, d0:d1]
+                dtm = np.where(pos_d > 0, gt_ids[np.maximum(pos_d, 1) - 1] if len(gg) else 0.0, 0.0).reshape(T, d1 - d0)
+                pos_g = gt_match[a, :, g0:g1][:, gtind]
+                gtm = np.where(pos_g > 0, dt_ids[np.maximum(pos_g, 1) - 1] if len(d) else 0.0, 0.0).reshape(T, g1 - g0)
+                outside = np.array([x["area"] < rng[0] or x["area"] > rng[1] for x in d], dtype=bool).reshape(1, len(d))
+                dt_ig = np.logical_or(dt_ignore[a, :, d0:d1] != 0, np.logical_and(dtm == 0, np.repeat(outside, T, 0)))
+                eval_imgs.append({
+                    "image_id": img, "category_id": cat, "aRng": rng, "maxDet": max_det,
+                    "dtIds": [x["id"] for x in d], "gtIds": [gg[i]["id"] for i in gtind],
+                    "dtMatches": dtm, "gtMatches": gtm, "dtScores": [x["score"] for x in d],
+                    "gtIgnore": gt_ig[gtind].astype(np.int64), "dtIgnore": dt_ig,
+                })
+    return ious, eval_imgs
 
 
 def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: str = "error") -> CocoEval:
@@ -420,15 +513,15 @@ def evaluate(gt, results, iou_type: str = "segm", device="cuda:0", *, polygons: 
     polygons raise NotImplementedError with polygons="error" (the default) and are rasterised on the GPU with
     polygons="rasterize" (annToRLE: ops.rle_from_poly + ops.rle_merge, the rows staying on the device for ops.rle_iou).
     iou_type="bbox" never looks at segmentations. Compressed strings, of results and of ground truth, are decoded on the GPU,
-    each once (_load's device route, _device_table)."""
+    each once (_load's device route, image._build_table)."""
     return _evaluate(gt, results, iou_type, device, polygons, "device")
 
 
 def _evaluate(gt, results, iou_type, device, polygons, codec):
-    """evaluate(); codec = "device" decodes compressed strings on the GPU, "host" is the per-character route of image.rle_counts
-    that load_results(device=None) and rle_table(device="cpu") still are — kept so that tools/codec_microbench.py and the tests
-    can compare the two in one process. Every number is the same."""
-    from . import image, ops
+    """evaluate(), stage by stage: _load, _group, _segm_tables, _match_on_device, _rebuild. codec = "device" decodes compressed
+    strings on the GPU, "host" is the per-character route of image.rle_counts that load_results(device=None) and
+    rle_table(device="cpu") still are — kept so that tools/codec_microbench.py and the tests can compare the two in one process.
+    Every number is the same."""
     if polygons not in ("error", "rasterize"):
         raise ValueError(f"polygons={polygons!r}: 'error' or 'rasterize'")
     if codec not in ("device", "host"):
@@ -444,130 +537,10 @@ def _evaluate(gt, results, iou_type, device, polygons, codec):
     dts_all, decoded = _load(results, iou_type, device if codec == "device" and iou_type == "segm" else None)
     if not set(a["image_id"] for a in dts_all) <= set(img_ids):
         raise ValueError("Results do not correspond to current coco set")
-
-    # _prepare (:85-120): group by (image, category), keeping the data set's / the result file's order within a group
-    in_imgs, in_cats = set(p.imgIds), set(p.catIds)
-    gts, dts = {}, {}
-    for ann in gt["annotations"]:
-        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
-            gts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
-    for ann in dts_all:
-        if ann["image_id"] in in_imgs and ann["category_id"] in in_cats:
-            dts.setdefault((ann["image_id"], ann["category_id"]), []).append(ann)
-    if iou_type == "segm" and polygons == "error":
-        for key, anns in gts.items():
-            for ann in anns:
-                if _is_polygon(ann["segmentation"]):
-                    raise NotImplementedError(
-                        f"annotation {ann.get('id')}: polygon segmentations are out of scope (rleFrPoly is not implemented); "
-                        "give RLE ground truth, or evaluate iou_type='bbox'")
-
-    # computeIoU's ordering (:174-177): -score mergesort, cut at maxDets[-1]
-    keys = [k for k in sorted(set(gts) | set(dts))]
-    max_det = p.maxDets[-1]
-    for key in keys:
-        d = dts.get(key, [])
-        inds = np.argsort([-x["score"] for x in d], kind="mergesort")
-        dts[key] = [d[i] for i in inds][:max_det]
-        gts.setdefault(key, [])
-    dt_flat = [x for key in keys for x in dts[key]]
-    gt_flat = [x for key in keys for x in gts[key]]
-    dt_n = np.array([len(dts[key]) for key in keys], dtype=np.int64)
-    gt_n = np.array([len(gts[key]) for key in keys], dtype=np.int64)
-    dt_off = np.concatenate([[0], np.cumsum(dt_n)])
-    gt_off = np.concatenate([[0], np.cumsum(gt_n)])
-    out_off = np.concatenate([[0], np.cumsum(dt_n * gt_n)])
-    K, N, M, out_len = len(keys), int(dt_off[-1]), int(gt_off[-1]), int(out_off[-1])
-    iscrowd = np.array([int(g["iscrowd"]) if "iscrowd" in g else 0 for g in gt_flat], dtype=np.uint8)
-    # gt['ignore'] = 'iscrowd' in gt and gt['iscrowd'] (:110)
-    gt_ignore_flag = np.array([1 if ("iscrowd" in g and g["iscrowd"]) else 0 for g in gt_flat], dtype=np.uint8)
-    dt_area = np.array([float(d["area"]) for d in dt_flat], dtype=np.float64)
-    gt_area = np.array([float(g["area"]) for g in gt_flat], dtype=np.float64)
-
+    g = _group(gt["annotations"], dts_all, p, refuse_polygons=iou_type == "segm" and polygons == "error")
     dev = torch.device(device)
-    dev_of = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    T, A = len(p.iouThrs), len(p.areaRng)
-    if K:
-        offs = (dev_of(dt_off.astype(np.int32)), dev_of(gt_off.astype(np.int32)), dev_of(out_off.astype(np.int64)))
-        if iou_type == "segm":
-            size_of = {img["id"]: (int(img["height"]), int(img["width"])) for img in gt["images"]
-                       if "height" in img and "width" in img}
-            ann_size = lambda x: size_of[x["image_id"]] if _is_polygon(x["segmentation"]) else _seg_size(x["segmentation"])
-            is_poly = np.array([_is_polygon(g["segmentation"]) for g in gt_flat], dtype=bool)
-            if codec == "device":
-                dt_table = _device_table(dt_flat, None, dev, decoded)
-                gt_table = _device_table(gt_flat, is_poly, dev)
-            else:
-                rows_d = [_seg_counts(d["segmentation"], i, dev) for i, d in enumerate(dt_flat)]
-                rows_g = [np.zeros(0, np.uint32) if is_poly[i] else _seg_counts(g["segmentation"], i, dev) for i, g in enumerate(gt_flat)]
-                dt_table, gt_table = image._pack_table(rows_d, dev), image._pack_table(rows_g, dev)
-            for k, key in enumerate(keys):
-                sizes = {ann_size(x) for x in dts[key] + gts[key]}
-                if len(sizes) > 1:
-                    raise ValueError(f"image {key[0]}, category {key[1]}: masks of different sizes {sorted(sizes)}")
-            if is_poly.any():
-                # annToRLE on the device; the rows go into the ground-truth table there (one scalar comes back: the longest row)
-                poly_anns = [g for g, f in zip(gt_flat, is_poly) if f]
-                p_runs, p_counts = _polygon_table(poly_anns, [size_of[g["image_id"]] for g in poly_anns], dev)
-                cap = max(int(p_runs.max()), gt_table[1].size(1))
-                idx = dev_of(np.nonzero(is_poly)[0])
-                g_runs, g_counts = gt_table[0].clone(), torch.zeros(len(gt_flat), cap, dtype=torch.int32, device=dev)
-                g_counts[:, :gt_table[1].size(1)] = gt_table[1]
-                width = min(cap, p_counts.size(1))
-                live = torch.arange(width, device=dev)[None, :] < p_runs[:, None]
-                g_counts[idx, :width] = torch.where(live, p_counts[:, :width], torch.zeros((), dtype=torch.int32, device=dev))
-                g_runs[idx] = p_runs
-                gt_table = (g_runs, g_counts)
-            ious_dev = ops.rle_iou(dt_table, gt_table, dev_of(iscrowd), *offs, out_len=out_len)
-        else:
-            boxes = lambda anns: np.array([[float(v) for v in x["bbox"]] for x in anns], dtype=np.float64).reshape(-1, 4)
-            ious_dev = ops.bbox_iou(dev_of(boxes(dt_flat)), dev_of(boxes(gt_flat)), dev_of(iscrowd), *offs, out_len=out_len)
-        match = ops.coco_match(ious_dev, *offs, dev_of(dt_area), dev_of(gt_area), dev_of(gt_ignore_flag),
-                               dev_of(np.array(p.areaRng, dtype=np.float64)), dev_of(np.asarray(p.iouThrs, dtype=np.float64)))
-        ious_flat = ious_dev.cpu().numpy()
-        dt_match, gt_match, dt_ignore, gt_ignore = [m.cpu().numpy() for m in match]
-    else:
-        ious_flat = np.zeros(0)
-        dt_match = gt_match = np.zeros((A, T, 0), np.int32)
-        dt_ignore, gt_ignore = np.zeros((A, T, 0), np.uint8), np.zeros((A, 0), np.uint8)
-
-    index = {key: k for k, key in enumerate(keys)}
-    ious = {}
-    for img in p.imgIds:
-        for cat in p.catIds:
-            k = index.get((img, cat))
-            if k is None or dt_n[k] == 0 or gt_n[k] == 0:
-                ious[img, cat] = []
-            else:
-                ious[img, cat] = ious_flat[out_off[k]:out_off[k + 1]].reshape(int(gt_n[k]), int(dt_n[k])).T
-
-    eval_imgs = []
-    for cat in p.catIds:
-        for a, rng in enumerate(p.areaRng):
-            for img in p.imgIds:
-                k = index.get((img, cat))
-                if k is None:
-                    eval_imgs.append(None)
-                    continue
-                d0, d1, g0, g1 = int(dt_off[k]), int(dt_off[k + 1]), int(gt_off[k]), int(gt_off[k + 1])
-                d, g = dts[img, cat], gts[img, cat]
-                gt_ig = gt_ignore[a, g0:g1]
-                gtind = np.argsort(gt_ig, kind="mergesort")            # regular first, ignored last (:258)
-                gt_ids = np.array([x["id"] for x in g], dtype=np.float64)
-                dt_ids = np.array([x["id"] for x in d], dtype=np.float64)
-                pos_d = dt_match[a, :, d0:d1]
-                dtm = np.where(pos_d > 0, gt_ids[np.maximum(pos_d, 1) - 1] if len(g) else 0.0, 0.0).reshape(T, d1 - d0)
-                pos_g = gt_match[a, :, g0:g1][:, gtind]
-                gtm = np.where(pos_g > 0, dt_ids[np.maximum(pos_g, 1) - 1] if len(d) else 0.0, 0.0).reshape(T, g1 - g0)
-                outside = np.array([x["area"] < rng[0] or x["area"] > rng[1] for x in d], dtype=bool).reshape(1, len(d))
-                dt_ig = np.logical_or(dt_ignore[a, :, d0:d1] != 0, np.logical_and(dtm == 0, np.repeat(outside, T, 0)))
-                eval_imgs.append({
-                    "image_id": img, "category_id": cat, "aRng": rng, "maxDet": max_det,
-                    "dtIds": [x["id"] for x in d], "gtIds": [g[i]["id"] for i in gtind],
-                    "dtMatches": dtm, "gtMatches": gtm, "dtScores": [x["score"] for x in d],
-                    "gtIgnore": gt_ig[gtind].astype(np.int64), "dtIgnore": dt_ig,
-                })
-    return CocoEval(p, ious, eval_imgs)
+    tables = _segm_tables(g, gt["images"], decoded, dev, codec == "host") if g.keys and iou_type == "segm" else None
+    return CocoEval(p, *_rebuild(g, p, *_match_on_device(g, p, iou_type, tables, dev)))
 
 
 # evaluate's positional interface — (gt, results, iou_type, device) — is pinned parameter by parameter by

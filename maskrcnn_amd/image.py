@@ -11,6 +11,8 @@ expressions); every pixel is produced by libmaskrcnn_hip.so (csrc/image.hip), bi
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -233,15 +235,23 @@ def rle_counts(obj) -> np.ndarray:
     return np.asarray(cnts, dtype=np.uint32)
 
 
-def _checked_counts(obj, h: int, w: int, i: int) -> np.ndarray:
-    """rle_counts(obj), checked against ops.rle_iou's contract on its inputs for an h x w mask (ValueError otherwise)."""
-    if isinstance(obj, dict) and [int(v) for v in obj["size"]] != [h, w]:
-        raise ValueError(f"rle_table: mask {i} is {list(obj['size'])}, the table is {[h, w]}")
+def _run_error(prefix: str, i: int, h: int, w: int, bad_sum: bool, empty_run: bool, total):
+    """The ValueError of run lengths that break ops.rle_iou's contract on its inputs for an h x w mask — they do not cover h*w
+    pixels (total(): what they cover, asked for on this path only), or a run after the first is empty — or None."""
+    if bad_sum:
+        return ValueError(f"{prefix}: the runs of mask {i} cover {total()} pixels, the mask has {h} x {w}")
+    if empty_run:
+        return ValueError(f"{prefix}: mask {i} has an empty run after the first one")
+    return None
+
+
+def _checked_counts(obj, prefix: str, i: int, h: int, w: int) -> np.ndarray:
+    """rle_counts(obj), checked against ops.rle_iou's contract on its inputs for an h x w mask (_run_error's ValueError)."""
     cnts = rle_counts(obj)
-    if int(cnts.astype(np.int64).sum()) != h * w:
-        raise ValueError(f"rle_table: the runs of mask {i} cover {int(cnts.astype(np.int64).sum())} pixels, the mask has {h} x {w}")
-    if cnts.size > 1 and not cnts[1:].all():
-        raise ValueError(f"rle_table: mask {i} has an empty run after the first one")
+    total = int(cnts.astype(np.int64).sum())
+    bad = _run_error(prefix, i, h, w, total != h * w, cnts.size > 1 and not cnts[1:].all(), lambda: total)
+    if bad is not None:
+        raise bad
     return cnts
 
 
@@ -285,33 +295,38 @@ def _strings_to_device(strs, hs, ws, device):
     return ops.rle_from_string(torch.from_numpy(data.copy()).to(device), ints[:n + 1], sizes[:n], sizes[n:], capacity=capacity)
 
 
-def _string_error(st: int, what: str):
-    """The ValueError of a string ops.rle_from_string refused (status bits), or None."""
+class _Decoded(NamedTuple):
+    """The strings one ops.rle_from_string call decoded: num_runs int32 [S] and counts int32 [S,capacity] on the device, and the
+    host copies (numpy int32 [S]) of num_runs (runs) and of the status the kernel wrote."""
+    num_runs: torch.Tensor
+    counts: torch.Tensor
+    runs: np.ndarray
+    status: np.ndarray
+
+
+def _status_error(d: _Decoded, k: int, who: str, written=None):
+    """The ValueError for row k of d by its status bits, or None. A string the kernel refused (num_runs -1): "{who} has <what is
+    wrong with it>". A row it wrote and flagged, with written = (prefix, i, h, w): _run_error's, the row's counts being fetched
+    from the device for the pixel sum only; written=None leaves those two bits to a later stage."""
+    st = int(d.status[k])
     for bit, why in ((ops.RLE_BAD_SIZE, "a height or width outside [1, 16384]"),
                      (ops.RLE_BAD_BYTE, "a character outside '0'..'o' (bytes 48..111) in its compressed string"),
                      (ops.RLE_LONG_TOKEN, "a run of more than 6 characters in its compressed string"),
                      (ops.RLE_OPEN_TOKEN, "a compressed string that ends inside a run"),
                      (ops.RLE_BAD_OFFSETS, "string offsets outside the buffer")):
         if st & bit:
-            return ValueError(f"{what} has {why}")
-    return None
-
-
-def _run_errors(st: int, i: int, h: int, w: int, row):
-    """The ValueError _checked_counts raises for a written row with status bits set, in its order and wording, or None. row():
-    the row's counts on the host (fetched on this error path only)."""
-    if st & ops.RLE_PIXEL_SUM:
-        return ValueError(f"rle_table: the runs of mask {i} cover {int(row().astype(np.int64).sum())} pixels, the mask has {h} x {w}")
-    if st & ops.RLE_EMPTY_RUN:
-        return ValueError(f"rle_table: mask {i} has an empty run after the first one")
-    return None
+            return ValueError(f"{who} has {why}")
+    if written is None:
+        return None
+    return _run_error(*written, st & ops.RLE_PIXEL_SUM, st & ops.RLE_EMPTY_RUN,
+                      lambda: int(d.counts[k, :int(d.runs[k])].cpu().numpy().view(np.uint32).astype(np.int64).sum()))
 
 
 def _merge_tables(n: int, parts, device, capacity=None):
     """parts: [(indices (numpy int64), num_runs [k], counts [k,c])] on the device, disjoint, covering what they cover of n rows →
     one zero-padded table (num_runs int32 [n], counts int32 [n,capacity]); rows no part covers are empty (num_runs 0)."""
     device = torch.device(device)
-    cap = max([1] + [int(c.size(1)) for _, _, c in parts]) if capacity is None else int(capacity)
+    cap = _widest(parts) if capacity is None else int(capacity)
     num_runs = torch.zeros(n, dtype=torch.int32, device=device)
     counts = torch.zeros(n, cap, dtype=torch.int32, device=device)
     for idx, nr, c in parts:
@@ -325,37 +340,81 @@ def _merge_tables(n: int, parts, device, capacity=None):
     return num_runs, counts
 
 
-def _rle_table_device(objs, h: int, w: int, device, capacity):
-    errors, strs, str_idx, rows, row_idx = {}, [], [], [], []
+def _table_parts(objs, sizes, device, *, skip=None, decoded=None, other=None, host_strings=False, prefix="rle_table"):
+    """RLE entries (dicts {"size", "counts"}, compressed strings or count lists), checked → the parts _merge_tables makes their
+    table of: rows packed on the host, rows gathered on the device, strings decoded there. sizes: a list, one (h, w) per entry,
+    or None: every entry is a dict (or other's) and of its own "size"; skip[i]: a row no part covers; decoded = (a _Decoded,
+    {entry index: its row}): strings that are on the device already and are gathered from there; other(obj, i): given, the run
+    lengths of every entry that is no dict come from it, and are taken as they come.
+    Where compressed strings are decoded is the one decision: on the device, all of them in ONE ops.rle_from_string call and one
+    read of num_runs / status — or, on the CPU or with host_strings, by rle_counts, and then the library is not touched. All
+    else is shared: a dict of another size, runs that do not cover the mask, an empty run after the first one and a malformed
+    string are ValueErrors "{prefix}: ... mask {i} ...", and the lowest bad index is the one raised."""
+    device = torch.device(device)
+    if sizes is None:
+        size = lambda i: (int(objs[i]["size"][0]), int(objs[i]["size"][1]))
+    else:
+        size = lambda i: (int(sizes[i][0]), int(sizes[i][1]))
+    host_strings = host_strings or device.type == "cpu"
+    gathered = decoded[1] if decoded is not None else {}
+    errors, rows, strs, pre = {}, [], [], []
     for i, obj in enumerate(objs):
-        s = _string_of(obj)
+        if skip is not None and skip[i]:
+            continue
         try:
-            if s is None:
-                rows.append(_checked_counts(obj, h, w, i))
-                row_idx.append(i)
-            elif isinstance(obj, dict) and [int(v) for v in obj["size"]] != [h, w]:
-                raise ValueError(f"rle_table: mask {i} is {list(obj['size'])}, the table is {[h, w]}")
+            if i in gathered:
+                pre.append((i, gathered[i]))
+            elif other is not None and not isinstance(obj, dict):
+                rows.append((i, other(obj, i)))
             else:
-                strs.append(s)
-                str_idx.append(i)
+                h, w = size(i)
+                if sizes is not None and isinstance(obj, dict) and [int(v) for v in obj["size"]] != [h, w]:
+                    raise ValueError(f"{prefix}: mask {i} is {list(obj['size'])}, the table is {[h, w]}")
+                s = None if host_strings else _string_of(obj)
+                if s is None:
+                    rows.append((i, _checked_counts(obj, prefix, i, h, w)))
+                else:
+                    strs.append((i, s, h, w))
         except ValueError as e:
+            if host_strings:
+                raise               # nothing is pending on the host: the entries are checked in index order
             errors[i] = e
+
+    def flagged(idx, at, d):
+        for j in np.nonzero(d.status[at])[0].tolist():
+            i = idx[j]
+            errors[i] = _status_error(d, int(at[j]), f"{prefix}: mask {i}", (prefix, i, *size(i)))
+
     parts = []
     if rows:
-        parts.append((row_idx, *_pack_table(rows, device)))
+        parts.append(([i for i, _ in rows], *_pack_table([r for _, r in rows], device)))
+    if pre:
+        idx, at = [i for i, _ in pre], np.array([k for _, k in pre], dtype=np.int64)
+        flagged(idx, at, decoded[0])
+        on_dev = torch.from_numpy(at).to(device)
+        parts.append((idx, decoded[0].num_runs[on_dev], decoded[0].counts[on_dev]))
     if strs:
-        nr, cnt, status = _strings_to_device(strs, [h] * len(strs), [w] * len(strs), device)
+        idx, strings, hs, ws = zip(*strs)
+        nr, cnt, status = _strings_to_device(strings, hs, ws, device)
         back = torch.stack([nr, status]).cpu().numpy()          # the one read-back
-        for k in np.nonzero(back[1])[0].tolist():
-            i, st = str_idx[k], int(back[1][k])
-            errors[i] = _string_error(st, f"rle_table: mask {i}") or \
-                _run_errors(st, i, h, w, lambda: cnt[k, :int(back[0][k])].cpu().numpy().view(np.uint32))
-        parts.append((str_idx, nr, cnt))
+        flagged(idx, np.arange(len(strs)), _Decoded(nr, cnt, back[0], back[1]))
+        parts.append((idx, nr, cnt))
     if errors:
         raise errors[min(errors)]
-    longest = max([1] + [int(c.size(1)) for _, _, c in parts])
-    if capacity is not None and int(capacity) < longest:
-        raise ValueError(f"rle_table: capacity {capacity} is less than the longest mask's {longest} runs")
+    return parts
+
+
+def _widest(parts) -> int:
+    """The capacity _merge_tables gives the table of these parts when it is not told one."""
+    return max([1] + [int(c.size(1)) for _, _, c in parts])
+
+
+def _build_table(objs, sizes, device, capacity=None, *, prefix="rle_table", **how):
+    """The (num_runs int32 [N], counts int32 [N,capacity]) table of RLE entries on the device: _table_parts (how: its other
+    keywords), the capacity check, _merge_tables."""
+    parts = _table_parts(objs, sizes, device, prefix=prefix, **how)
+    if capacity is not None and int(capacity) < _widest(parts):
+        raise ValueError(f"{prefix}: capacity {capacity} is less than the longest mask's {_widest(parts)} runs")
     return _merge_tables(len(objs), parts, device, capacity)
 
 
@@ -366,11 +425,9 @@ def rle_table(objs, size, device="cuda:0", capacity=None):
     otherwise). On a GPU device all compressed strings are decoded there in ONE ops.rle_from_string call (no per-character host
     work; a malformed string — a byte outside 48..111, a run of more than 6 characters, an end inside a run — is a ValueError
     too), count lists are packed on the host, the two are merged by index on the device, and the checks read num_runs / status
-    back once. device="cpu": every entry goes through rle_counts on the host, and the library is not touched."""
-    h, w = int(size[0]), int(size[1])
-    if torch.device(device).type != "cpu":
-        return _rle_table_device(list(objs), h, w, device, capacity)
-    return _pack_table([_checked_counts(obj, h, w, i) for i, obj in enumerate(objs)], device, capacity)
+    back once. device="cpu": every entry goes through rle_counts on the host, and the library is not touched (_build_table)."""
+    objs = list(objs)
+    return _build_table(objs, [(int(size[0]), int(size[1]))] * len(objs), device, capacity)
 
 
 def rle_decode_masks(objs, size, device="cuda:0") -> torch.Tensor:

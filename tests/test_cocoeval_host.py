@@ -368,6 +368,52 @@ def test_evaluate_img_restatement_equals_the_golden_on_every_entry(iou_type):
     assert matched > 500
 
 
+@pytest.mark.parametrize("iou_type", ["segm", "bbox"])
+def test_grouping_and_rebuilding_stages_equal_the_golden_without_a_gpu(iou_type):
+    """cocoeval._group and cocoeval._rebuild, the host stages either side of evaluate's device calls: the flat order and the
+    offsets of the first against golden_groups, and the second — fed the golden IoUs and what evaluate_img_ref computes, laid
+    out as ops.rle_iou / ops.coco_match return them — against the golden ious and evalImgs."""
+    from maskrcnn_amd import cocoeval
+    gt, results = golden_inputs()
+    p = cocoeval.Params(iou_type)
+    p.imgIds, p.catIds = list(np.unique([i["id"] for i in gt["images"]])), list(np.unique([c["id"] for c in gt["categories"]]))
+    g = cocoeval._group(gt["annotations"], cocoeval.load_results(results, iou_type), p)
+    groups, want_ious = golden_groups(), golden_ious(iou_type)
+    assert g.keys == sorted(groups) and len(g.keys) >= 30
+    for k, key in enumerate(g.keys):
+        d, gg = groups[key]
+        assert [x["id"] for x in g.dts[key]] == [x["id"] for x in d] and [x["id"] for x in g.gts[key]] == [x["id"] for x in gg], key
+        assert g.dt_flat[g.dt_off[k]:g.dt_off[k + 1]] == g.dts[key] and g.gt_flat[g.gt_off[k]:g.gt_off[k + 1]] == g.gts[key], key
+        assert (g.dt_n[k], g.gt_n[k], g.out_off[k + 1] - g.out_off[k]) == (len(d), len(gg), len(d) * len(gg)), key
+    assert len(g.dt_flat) == g.dt_off[-1] and len(g.gt_flat) == g.gt_off[-1] and g.dt_n.max() == 100
+    assert g.dt_off.dtype == g.gt_off.dtype == g.out_off.dtype == np.int64 and g.dt_off[0] == g.gt_off[0] == g.out_off[0] == 0
+    with pytest.raises(NotImplementedError, match="annotation 7: polygon"):
+        cocoeval._group([dict(gt["annotations"][0], id=7, segmentation=[[1.0, 1.0, 5.0, 1.0, 5.0, 5.0]])], [], p, refuse_polygons=True)
+
+    A, N, M = len(AREA_RNG), int(g.dt_off[-1]), int(g.gt_off[-1])
+    ious_flat = np.full(int(g.out_off[-1]), np.nan)
+    dt_match, gt_match = np.zeros((A, T, N), np.int32), np.zeros((A, T, M), np.int32)
+    dt_ignore, gt_ignore = np.zeros((A, T, N), np.uint8), np.zeros((A, M), np.uint8)
+    for k, key in enumerate(g.keys):
+        d, gg = groups[key]
+        if key in want_ious:
+            ious_flat[g.out_off[k]:g.out_off[k + 1]] = want_ious[key].T.reshape(-1)          # ground truth slowest
+        ds, gs = slice(g.dt_off[k], g.dt_off[k + 1]), slice(g.gt_off[k], g.gt_off[k + 1])
+        for a, rng in enumerate(AREA_RNG):
+            dt_match[a, :, ds], gt_match[a, :, gs], dt_ignore[a, :, ds], gt_ignore[a, gs], _ = evaluate_img_ref(
+                want_ious.get(key, []), [x["area"] for x in d], [x["area"] for x in gg], [x["iscrowd"] for x in gg], rng, IOU_THRS)
+    assert not np.isnan(ious_flat).any()
+    ious, eval_imgs = cocoeval._rebuild(g, p, ious_flat, dt_match, gt_match, dt_ignore, gt_ignore)
+    assert set(ious) == {(i, c) for i in p.imgIds for c in p.catIds}
+    for key, v in ious.items():
+        assert np.array_equal(v, want_ious[key]) if key in want_ious else (isinstance(v, list) and v == []), key
+    want = golden_eval_imgs(iou_type)
+    assert len(eval_imgs) == len(want) == len(p.catIds) * A * len(p.imgIds)
+    assert all(same_eval_img(x, y) for x, y in zip(eval_imgs, want)) and sum(e is not None for e in eval_imgs) >= 100
+    ev = cocoeval.CocoEval(p, ious, eval_imgs)                                                # and the rest of evaluate on them
+    assert np.array_equal(ev.stats, load_golden("cocoeval")[f"{iou_type}_stats"])
+
+
 def test_one_hip_runtime_whatever_is_imported_first():
     """`python -m maskrcnn_amd.cocoeval` imports the package before torch: the library must still share torch's HIP runtime (two
     copies of libamdhip64 in one process: the second one's launches fail with "no ROCm-capable device is detected")."""

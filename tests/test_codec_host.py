@@ -157,3 +157,60 @@ def test_host_routes_never_touch_the_library(monkeypatch):
     for i, obj in enumerate(mixed):
         want = image.rle_counts(obj)
         assert int(num_runs[i]) == want.size and np.array_equal(counts[i, :want.size].numpy().view(np.uint32), want)
+
+
+def test_merge_tables_places_rows_by_index_and_zero_fills():
+    """image._merge_tables on CPU tensors: parts of different widths out of index order, a row no part covers, stale values
+    behind num_runs in the input, and a capacity wider than every part."""
+    from maskrcnn_amd import image
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)
+    wide = ([3, 0], i32([2, 1]), i32([[7, 8, 99, 98], [5, 97, 96, 95]]))            # rows 3 and 0: 4 wide, stale tails
+    narrow = (np.array([2]), i32([4]), i32([[1, 2, 3, 4]]))
+    short = ([2], i32([2]), i32([[6, 9, 94]]))                                      # 3 wide
+    for parts, capacity, width in (([wide, narrow], None, 4), ([short, wide], None, 4), ([wide, narrow], 7, 7), ([short], None, 3)):
+        num_runs, counts = image._merge_tables(5, parts, "cpu", capacity)
+        assert num_runs.dtype == torch.int32 and counts.dtype == torch.int32 and tuple(counts.shape) == (5, width)
+        want = np.zeros((5, width), np.int64)
+        for idx, nr, c in parts:
+            for i, n, row in zip(list(idx), nr.tolist(), c.tolist()):
+                want[i, :n] = row[:n]
+        assert counts.tolist() == want.tolist()
+        assert num_runs.tolist() == [int(np.count_nonzero(r)) for r in want]         # every live run here is non-zero
+    assert image._merge_tables(5, [wide, narrow], "cpu")[0].tolist() == [1, 0, 4, 2, 0]
+    empty = image._merge_tables(3, [], "cpu")
+    assert empty[0].tolist() == [0, 0, 0] and tuple(empty[1].shape) == (3, 1) and not empty[1].any()
+
+
+def test_build_table_on_the_host_with_one_size_per_entry(monkeypatch):
+    """image._build_table with the host string decoder: dicts, bare strings, count lists and a skipped row of two sizes equal
+    _pack_table of rle_counts of each entry; of two bad entries the lower index is named. The library is not touched."""
+    from maskrcnn_amd import image, ops
+    from test_rle_host import golden_cases
+    for name in ("rle_from_string", "rle_area_bbox", "rle_encode"):
+        monkeypatch.setattr(ops, name, lambda *a, **k: pytest.fail("the host route called into the library"))
+    by_size = {}
+    for c in golden_cases():
+        by_size.setdefault(c["mask"].shape, []).append(c)
+    small, (big, big2) = by_size[29, 13][0], by_size[60, 90][:2]
+    objs = [{"size": [60, 90], "counts": big["string"]}, small["string"], big2["counts"].tolist(), [[1.0, 2.0, 3.0, 4.0, 5.0, 6.0]],
+            {"size": [29, 13], "counts": small["counts"].tolist()}, big2["string"].decode("ascii")]
+    sizes = [(60, 90), (29, 13), (60, 90), (0, 0), (29, 13), (60, 90)]
+    skip = [False, False, False, True, False, False]
+    rows = [np.zeros(0, np.uint32) if s else image.rle_counts(o) for o, s in zip(objs, skip)]
+    assert [r.size for r in rows] == [big["counts"].size, small["counts"].size, big2["counts"].size, 0, small["counts"].size, big2["counts"].size]
+    for device, host_strings in (("cpu", False), ("cpu", True)):
+        num_runs, counts = image._build_table(objs, sizes, device, skip=skip, host_strings=host_strings)
+        want = image._pack_table(rows, "cpu")
+        assert torch.equal(num_runs, want[0]) and torch.equal(counts, want[1]) and counts.dtype == torch.int32
+    wide = image._build_table(objs, sizes, "cpu", counts.size(1) + 3, skip=skip)
+    assert torch.equal(wide[1], image._pack_table(rows, "cpu", counts.size(1) + 3)[1])
+    with pytest.raises(ValueError, match="rle_table: capacity 5 is less than the longest mask's"):
+        image._build_table(objs, sizes, "cpu", 5, skip=skip)
+    with pytest.raises(ValueError, match=r"rle_table: mask 4 is \[29, 13\], the table is \[60, 90\]"):
+        image._build_table(objs, [(60, 90)] * 6, "cpu", skip=[False, True, False, True, False, False])
+    with pytest.raises(ValueError, match="rle_table: the runs of mask 0 cover 30 pixels, the mask has 60 x 90"):
+        image._build_table([[10, 20], [5000, 0, 400], big["string"]], [(60, 90)] * 3, "cpu")
+    with pytest.raises(ValueError, match="ground truth: mask 1 has an empty run after the first one"):
+        image._build_table([big["string"], [5000, 0, 400], [10, 20]], [(60, 90)] * 3, "cpu", prefix="ground truth")
+    with pytest.raises(ValueError, match="rle_table: mask 0 has an empty run after the first one"):
+        image.rle_table([[5000, 0, 400], [10, 20]], (60, 90), "cpu")

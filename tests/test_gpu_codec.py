@@ -399,6 +399,25 @@ def test_rle_table_on_the_device_merges_strings_and_count_lists_and_keeps_its_er
         image.rle_table(objs, (60, 90), DEV, capacity=2)
 
 
+def test_the_lowest_bad_entry_is_named_whatever_its_kind():
+    """A malformed string (found by the kernel's status) and a bad count list (found on the host) in one list: the error is the
+    lower index's, in either order, through rle_table and through evaluate's ground-truth table."""
+    from maskrcnn_amd import cocoeval, image
+    good = [c for c in rle_cases() if c["mask"].shape == (60, 90)][0]["string"]
+    open_string, short_list = good + b"P", [10, 20]
+    for bad, match in (([open_string, short_list], "mask 1 has a compressed string that ends inside a run"),
+                       ([short_list, open_string], "the runs of mask 1 cover 30 pixels, the mask has 60 x 90")):
+        with pytest.raises(ValueError, match=match):
+            image.rle_table([good] + bad, (60, 90), DEV)
+        seg = lambda c: {"size": [60, 90], "counts": c.decode("ascii") if isinstance(c, bytes) else c}
+        gt = dict(images=[dict(id=1, height=60, width=90), dict(id=2, height=60, width=90)], categories=[dict(id=1)],
+                  annotations=[dict(id=k + 1, image_id=min(k + 1, 2), category_id=1, iscrowd=0, area=100.0, bbox=[0.0, 0.0, 10.0, 10.0],
+                                    segmentation=seg(c)) for k, c in enumerate([good] + bad)])
+        results = [dict(image_id=1, category_id=1, score=0.5, segmentation=seg(good))]
+        with pytest.raises(ValueError, match=match):
+            cocoeval.evaluate(gt, results, "segm")
+
+
 def strip_bbox(results):
     return [{k: v for k, v in r.items() if k != "bbox"} for r in results]
 
@@ -465,3 +484,41 @@ def test_ann_to_rle_compress_writes_the_strings_of_the_uncompressed_result():
         else:
             assert b["segmentation"] == src["segmentation"]
     assert polys > 3
+
+
+COUNTED = ("rle_from_string", "rle_area_bbox", "rle_from_poly", "rle_merge", "rle_iou", "bbox_iou", "coco_match", "rle_encode")
+
+
+def test_library_calls_of_one_evaluation_are_counted(ops, monkeypatch):
+    """How many times each library entry point runs in one evaluate / load_results / ann_to_rle call. The numbers were recorded
+    on the commit before the table building of image.rle_table and cocoeval.evaluate was put in one place, with this test; the
+    host code around the kernels may be rearranged, the device work of a call may not."""
+    from maskrcnn_amd import cocoeval
+    from test_poly_host import eval_inputs
+    calls = dict.fromkeys(COUNTED, 0)
+
+    def counting(name, real):
+        def wrapper(*a, **k):
+            calls[name] += 1
+            return real(*a, **k)
+        return wrapper
+
+    for name in COUNTED:
+        monkeypatch.setattr(ops, name, counting(name, getattr(ops, name)))
+
+    def count(fn):
+        for name in COUNTED:
+            calls[name] = 0
+        fn()
+        return {k: v for k, v in calls.items() if v}
+
+    gt, results = golden_inputs()
+    poly_gt, poly_results = eval_inputs()
+    assert count(lambda: cocoeval.evaluate(gt, results, "segm")) == dict(rle_from_string=2, rle_iou=1, coco_match=1)
+    assert count(lambda: cocoeval.evaluate(gt, strip_bbox(results), "segm")) == \
+        dict(rle_from_string=2, rle_area_bbox=1, rle_iou=1, coco_match=1)
+    # poly.npz's ground truth holds polygons and count lists, no compressed string: the one decode is the results'
+    assert count(lambda: cocoeval.evaluate(poly_gt, poly_results, "segm", polygons="rasterize")) == \
+        dict(rle_from_string=1, rle_from_poly=1, rle_merge=1, rle_iou=1, coco_match=1)
+    assert count(lambda: cocoeval.load_results(strip_bbox(results), "segm", device=DEV)) == dict(rle_from_string=1, rle_area_bbox=1)
+    assert count(lambda: cocoeval.ann_to_rle(poly_gt, DEV)) == dict(rle_from_poly=1, rle_merge=1)
