@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 22
+#define MRCNN_ABI_VERSION 23
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -707,6 +707,32 @@ size_t mrcnn_rle_decode_workspace_bytes(int32_t n, int32_t capacity);
 int mrcnn_rle_decode_u8(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, int32_t height,
                         int32_t width, uint8_t* out, int64_t image_stride, int64_t row_stride, void* workspace,
                         size_t workspace_bytes, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Rendering detections onto the image — data.blend_image / data.blend_mask (data.py:346-403: per instance a PIL Image.blend at
+ * 0.2, two Image.composite and an inverted 3x3 ImageFilter.CONTOUR with the frame zeroed, then ImageDraw.rectangle at width 1)
+ * without the labels, the bits Pillow gives, in ONE launch. csrc/overlay.hip.
+ *   image   uint8 [height][width][3], rows image_row_stride bytes apart;  out likewise, rows out_row_stride bytes apart
+ *   masks   uint8, mask i at masks + i*mask_image_stride, rows mask_row_stride bytes apart, pixels contiguous; a pixel is ON
+ *           where its byte > threshold (0 for 0 / 1 masks, 127 for grey levels). mask_image_stride 0 reads one mask n times.
+ *   colors  uint8 [n][3];   boxes int32 [n][4] (y0, x0, y1, x1), or NULL: no rectangles
+ * For each pixel p, px starting as the image's, for i = 0 .. n-1 in order:
+ *   mask i on at p:  px = (uint8) trunc(float(px) + 0.2f * float(int(c_i) - int(px))) per channel, in fp32 (no FMA)
+ *   else:            px = c_i if one of p's 8 neighbours is on in mask i (outside the image: off) and p is not on the image
+ *                    frame (0 < y < height-1, 0 < x < width-1) — so an image with height < 3 or width < 3 has no outline.
+ * Then the rectangles for i = 0 .. n-1 in order (a later one overwrites an earlier one): rows y0 and y1 over columns x0..x1,
+ * columns x0 and x1 over rows min(y0+1, y1) .. max(y0+1, y1) (Pillow's: a box with y0 == y1 also colours row y0+1 at its two end
+ * columns), clipped to the image; y0+1 is taken in 64 bits, so any int32 coordinates are safe. y1 < y0 or x1 < x0 draws nothing.
+ * Every byte of out's height x 3*width region is written and none outside it; n == 0 copies the image. out == image with equal
+ * row strides is allowed (a pixel reads only its own image bytes); any other overlap of out with an input is the caller's error.
+ * Host-checked limits (an error): 1 <= height, width <= 16384; 0 <= n <= 65535; 0 <= threshold <= 254; image_row_stride and
+ * out_row_stride >= 3*width; mask_row_stride >= width; mask_image_stride >= 0. Operands whose base and strides are multiples of
+ * 16 bytes are read and written 16 bytes at a time (masks on their own, image and out together), the others byte by byte: the
+ * same bits. No workspace, no allocation, no host synchronisation, no atomics; the same bits from run to run.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_blend_instances_u8(const uint8_t* image, int64_t image_row_stride, const uint8_t* masks, int64_t mask_image_stride,
+                             int64_t mask_row_stride, const uint8_t* colors, const int32_t* boxes, int32_t n, int32_t height,
+                             int32_t width, int32_t threshold, uint8_t* out, int64_t out_row_stride, mrcnn_stream_t stream);
 
 /* RPN conv_shared + both 1x1 heads in one launch on the Winograd kernel (RPN.forward, model.py:605-607,624-641):
  * relu(conv3x3_same(x) * scale + shift) is never stored — each 64-channel output tile is transposed through LDS and

@@ -6,11 +6,15 @@ Mirrors the reference functions either side of MaskRCNN.predict:
     full_masks     data.py:287-314     28x28 masks → PIL resize to the box → paste → > 127
     decode_boxes   data.py:331-343     boxes back to the original image's frame
     decode_masks   data.py:264-284     masks back to the original image's size (CenterCrop + PIL resize)
+    random_colors  data.py:346-356     the instance palette
+    blend_image    data.py:359-403     masks, outlines and boxes drawn onto the image (without the labels)
 The host part below is the scalar bookkeeping (scale, sizes, pads — Python floats and round(), exactly the reference's
 expressions); every pixel is produced by libmaskrcnn_hip.so (csrc/image.hip), bit-identical to Pillow's resample.
 """
 from __future__ import annotations
 
+import colorsys
+import random
 from typing import NamedTuple
 
 import numpy as np
@@ -506,3 +510,119 @@ def rle_from_bboxes(boxes, size, device="cuda:0"):
     xe, ye = xs + bb[:, 2], ys + bb[:, 3]
     polys = np.stack([xs, ys, xs, ye, xe, ye, xe, ys], axis=1)
     return rle_from_polygons(list(polys), size, device)
+
+
+# ---------------------------------------------------------------------------------------------- rendering detections
+def random_colors(n: int, bright: bool = True, shuffle: bool = True):
+    """data.random_colors (data.py:346-356): n (r, g, b) tuples, hues i/n at full saturation through colorsys, int(v * 255),
+    shuffled with the GLOBAL random.shuffle — after random.seed(k) this is the reference's palette."""
+    brightness = 1.0 if bright else 0.7
+    colors = []
+    for i in range(n):
+        r, g, b = colorsys.hsv_to_rgb(i / n, 1, brightness)
+        colors.append((int(r * 255), int(g * 255), int(b * 255)))
+    if shuffle:
+        random.shuffle(colors)
+    return colors
+
+
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def _blend_host(image: np.ndarray, on: np.ndarray, colors: np.ndarray, boxes) -> np.ndarray:
+    """The rule of mrcnn_blend_instances_u8 (include/maskrcnn_hip.h) in numpy: image uint8 [H,W,3], on bool [N,H,W], colors uint8
+    [N,3], boxes int64 [N,4] (y0, x0, y1, x1) or None → a new uint8 [H,W,3]. The blend is float32 arithmetic, the box clipping
+    int64. An inverted box is a ValueError, as Pillow's."""
+    out = np.array(image, dtype=np.uint8)
+    h, w = out.shape[:2]
+    fifth = np.float32(0.2)
+    for m, c in zip(on, colors):
+        pad = np.zeros((h + 2, w + 2), dtype=bool)
+        pad[1:-1, 1:-1] = m
+        near = np.zeros((h, w), dtype=bool)
+        for dy in (0, 1, 2):
+            for dx in (0, 1, 2):
+                if (dy, dx) != (1, 1):
+                    near |= pad[dy:dy + h, dx:dx + w]
+        edge = near & ~m
+        edge[0, :] = edge[-1, :] = False
+        edge[:, 0] = edge[:, -1] = False
+        px = out.astype(np.float32)
+        diff = (c.astype(np.int32)[None, None, :] - out.astype(np.int32)).astype(np.float32)
+        blended = np.trunc(px + fifth * diff).astype(np.uint8)         # float32 throughout: fifth * diff rounds, then the sum
+        out[m] = blended[m]
+        out[edge] = c
+    if boxes is not None:
+        for (y0, x0, y1, x1), c in zip(np.asarray(boxes, dtype=np.int64).reshape(-1, 4).tolist(), colors):
+            if y1 < y0 or x1 < x0:
+                raise ValueError(f"blend_image: box ({y0}, {x0}, {y1}, {x1}) has y2 < y1 or x2 < x1")
+            xa, xb = max(x0, 0), min(x1, w - 1)
+            for y in (y0, y1):
+                if 0 <= y < h and xa <= xb:
+                    out[y, xa:xb + 1] = c
+            ya, yb = max(min(y0 + 1, y1), 0), min(max(y0 + 1, y1), h - 1)
+            for x in (x0, x1):
+                if 0 <= x < w and ya <= yb:
+                    out[ya:yb + 1, x] = c
+    return out
+
+
+def _boxes_i32(boxes: torch.Tensor) -> torch.Tensor:
+    """Box coordinates truncated toward zero to int32 where they are (device or host); values outside int32 saturate."""
+    if boxes.dtype == torch.int32:
+        return boxes
+    if boxes.dtype.is_floating_point:
+        boxes = boxes.to(torch.float64).trunc()
+    return boxes.clamp(INT32_MIN, INT32_MAX).to(torch.int32)
+
+
+def blend_image(image, boxes, masks, colors=None, threshold=None, device="cuda:0") -> torch.Tensor:
+    """data.blend_image(image, None, boxes, masks) (data.py:383-403) without the labels: every instance's mask blended at 0.2, its
+    outline and its box in the instance's colour, the bits Pillow gives → uint8 [H,W,3] on `device`.
+        image      numpy array or tensor uint8 [H,W,3]
+        boxes      [N,4] (y1, x1, y2, x2), any real dtype, or None: no rectangles; float coordinates are truncated toward zero on
+                   the device
+        masks      a dense uint8 / bool tensor [N,H,W], an RleMasks (decoded on the device; threshold 0) or None: boxes only
+        colors     [N,3] uint8 values (a list of tuples, an array or a tensor); None: random_colors(N), the reference's call
+        threshold  a pixel is on where mask > threshold. None: 0 for bool masks and RleMasks, 127 for uint8 masks — detect()'s
+                   grey levels for a resized image; give 0 for uint8 masks of 0 / 1 (the values are never inspected here)
+    On a GPU device everything is one ops.blend_instances launch and nothing comes back to the host. device="cpu" runs the same
+    rule in numpy (_blend_host) and does not touch the library; there an inverted box (y2 < y1 or x2 < x1) is a ValueError, as
+    Pillow's, while the kernel draws nothing for it."""
+    device = torch.device(device)
+    img = _to_device_u8(image, device)
+    h, w = int(img.size(0)), int(img.size(1))
+    if isinstance(masks, RleMasks):
+        if masks.size != (h, w):
+            raise ValueError(f"blend_image: masks of {masks.size} on an image of {(h, w)}")
+        if device.type == "cpu":
+            raise RuntimeError("blend_image: an RleMasks is decoded on the GPU; give device a GPU, or dense masks")
+        masks, threshold = masks.decode(), 0 if threshold is None else threshold
+    if masks is None and boxes is None:
+        raise ValueError("blend_image: neither masks nor boxes")
+    n = int(masks.size(0)) if masks is not None else len(boxes)
+    if boxes is not None:
+        boxes = _boxes_i32(torch.as_tensor(boxes).to(device).reshape(-1, 4))
+        if int(boxes.size(0)) != n:
+            raise ValueError(f"blend_image: {n} masks and {int(boxes.size(0))} boxes")
+    if masks is None:
+        masks, threshold = torch.zeros(1, h, w, dtype=torch.uint8, device=device).expand(n, h, w), 0
+    else:
+        masks = torch.as_tensor(masks).to(device)
+    if masks.dtype not in (torch.uint8, torch.bool) or tuple(masks.shape) != (n, h, w):
+        raise ValueError(f"blend_image: expected uint8 or bool masks [{n},{h},{w}], got {masks.dtype} {tuple(masks.shape)}")
+    if threshold is None:
+        threshold = 0 if masks.dtype == torch.bool else 127
+    if not 0 <= int(threshold) <= 254:
+        raise ValueError(f"blend_image: threshold={threshold} must be in [0, 254]")
+    if colors is None:
+        colors = random_colors(n) if n else []
+    if not isinstance(colors, torch.Tensor):
+        colors = torch.from_numpy(np.array(colors, dtype=np.uint8).reshape(-1, 3))
+    colors = colors.to(device)
+    if colors.dtype != torch.uint8 or tuple(colors.shape) != (n, 3):
+        raise ValueError(f"blend_image: expected uint8 colors [{n},3], got {colors.dtype} {tuple(colors.shape)}")
+    if device.type == "cpu":
+        on = masks.view(torch.uint8).numpy() > int(threshold) if masks.dtype == torch.bool else masks.numpy() > int(threshold)
+        return torch.from_numpy(_blend_host(img.numpy(), on, colors.numpy(), None if boxes is None else boxes.numpy()))
+    return ops.blend_instances(img, masks, colors, boxes, int(threshold))

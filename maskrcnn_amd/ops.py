@@ -33,7 +33,7 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
            "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
-           "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode"]
+           "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1717,6 +1717,54 @@ _LIB.impl("rle_to_string", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
 _LIB.define("rle_decode(Tensor num_runs, Tensor counts, int height, int width) -> Tensor")   # `out` is the Python binding's
 _LIB.impl("rle_decode", lambda num_runs, counts, height, width: rle_decode(num_runs, counts, height, width), "CUDA")
 _LIB.impl("rle_decode", lambda num_runs, *a: _need_gpu(num_runs), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# Rendering detections onto the image: data.blend_image without the labels (csrc/overlay.hip)
+# --------------------------------------------------------------------------------------------------
+@_on_device
+def blend_instances(image: torch.Tensor, masks: torch.Tensor, colors: torch.Tensor, boxes: torch.Tensor | None = None,
+                    threshold: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """data.blend_image (data.py:383-403: blend_mask per instance, then the rectangles) without the labels, the bits Pillow gives,
+    in one launch (mrcnn_blend_instances_u8 in include/maskrcnn_hip.h states the rule). image uint8 [H,W,3] with unit strides
+    inside a row (the row stride is free); masks uint8 or bool [N,H,W] with unit pixel stride (image and row strides free: a
+    cropped or expanded view needs no copy), a pixel on where its byte > threshold; colors uint8 [N,3]; boxes int32 [N,4]
+    (y1, x1, y2, x2) or None: no rectangles. → out, uint8 [H,W,3] on the device (a new tensor when none is given; `out is image`
+    renders in place). N == 0 copies the image. No host synchronisation."""
+    _need_gpu(image, masks, colors, boxes, out)
+    if image.dtype != torch.uint8 or image.dim() != 3 or image.size(2) != 3:
+        raise RuntimeError(f"blend_instances: expected an RGB uint8 [H,W,3] image, got {image.dtype} {tuple(image.shape)}")
+    h, w = int(image.size(0)), int(image.size(1))
+    if masks.dtype not in (torch.uint8, torch.bool) or masks.dim() != 3 or tuple(masks.shape[1:]) != (h, w):
+        raise RuntimeError(f"blend_instances: expected uint8 or bool masks [N,{h},{w}], got {masks.dtype} {tuple(masks.shape)}")
+    m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    n = int(m.size(0))
+    if n > 0 and w > 1 and m.stride(2) != 1:
+        raise RuntimeError(f"blend_instances: the masks' last stride must be 1, got strides {tuple(masks.stride())}")
+    if out is None:
+        out = torch.empty(h, w, 3, dtype=torch.uint8, device=image.device)
+    for name, t in (("image", image), ("out", out)):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (h, w, 3) or t.stride(2) != 1 or (w > 1 and t.stride(1) != 3):
+            raise RuntimeError(f"blend_instances: {name} must be a uint8 [{h},{w},3] tensor with unit strides inside a row, got "
+                               f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    if colors.dtype != torch.uint8 or tuple(colors.shape) != (n, 3):
+        raise RuntimeError(f"blend_instances: colors must be uint8 [{n},3], got {colors.dtype} {tuple(colors.shape)}")
+    colors = colors.contiguous()
+    if boxes is not None:
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4):
+            raise RuntimeError(f"blend_instances: boxes must be int32 [{n},4] or None, got {boxes.dtype} {tuple(boxes.shape)}")
+        boxes = boxes.contiguous()
+    row = lambda t: t.stride(0) if h > 1 else 3 * w
+    _launch(lib.mrcnn_blend_instances_u8,
+            (image.data_ptr(), row(image), m.data_ptr(), m.stride(0) if n > 1 else 0, m.stride(1) if n > 0 and h > 1 else w,
+             colors.data_ptr(), _ptr(boxes), n, h, w, int(threshold), out.data_ptr(), row(out), _stream()),
+            lambda: (0, (n, h, w), n * h * w + 6 * h * w, "blend_instances"))
+    return out
+
+
+_LIB.define("blend_instances(Tensor image, Tensor masks, Tensor colors, Tensor? boxes=None, int threshold=0) -> Tensor")   # `out` is the Python binding's
+_LIB.impl("blend_instances", lambda image, masks, colors, boxes=None, threshold=0: blend_instances(image, masks, colors, boxes, threshold), "CUDA")
+_LIB.impl("blend_instances", lambda image, *a: _need_gpu(image), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------

@@ -4,7 +4,9 @@ load the checkpoint (the reference's `MaskRCNN.state_dict()` key layout loads un
 `MaskRCNNInference.detect` — resize + pad + mean-subtract, ResNet-101-FPN trunk, RPN, proposal NMS, RoIAlign, heads, per-class
 NMS, mask head, full-size mask pasting, all on the GPU with one host synchronisation — and print one line per detection
 (class id, COCO class name, box, score), as the reference does. Its matplotlib window (`utils.display_instances`) is out of
-scope; `--save out.npz` stores class ids, scores, boxes and the full-size boolean masks instead.
+scope; `--save out.npz` stores class ids, scores, boxes and the full-size boolean masks instead, and `--render out.png` writes
+the picture the reference's deterministic renderer (`data.blend_image`) draws: masks, outlines and boxes composited on the GPU
+(`image.blend_image`), one [H,W,3] copy to the host, the labels drawn there with PIL.
 
 The reference's weights (models/mask_rcnn_coco.pth, a manual download) are not available offline: without `-model` the script
 refuses to guess, and `--random-weights` runs the same path on seeded random weights of the same architecture (plumbing /
@@ -49,6 +51,10 @@ def main(argv=None):
     ap.add_argument("--coco-json", default=None, help="write COCO result records (image_id, category_id, bbox, score, "
                                                      "segmentation as RLE: build_coco_results, coco.py:53-60) to this file; score it with "
                                                      "`python -m maskrcnn_amd.cocoeval GT.json FILE`")
+    ap.add_argument("--render", default=None, metavar="FILE",
+                    help="write the image with every instance's mask, outline, box and label on it (data.blend_image) to this file; "
+                         "the format follows the extension")
+    ap.add_argument("--seed", type=int, default=None, help="random.seed(K) before the instance colours of --render are drawn")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("image", type=str, help="image file")
     args = ap.parse_args(argv)
@@ -103,7 +109,29 @@ def main(argv=None):
                                 "segmentation": {"size": seg["size"], "counts": seg["counts"].decode("ascii")}})
         with open(args.coco_json, "w") as fh:
             json.dump(records, fh)
+    if args.render:
+        render(args.render, img, out, boxes, masks, args.seed, args.device)
     return out
+
+
+def render(path, img, detections, boxes, masks, seed=None, device="cuda:0"):
+    """data.blend_image(image, names, boxes, masks, scores) into a file: the device tensors detect() returned go through
+    image.blend_image as they are (no dense mask leaves the device), the rendered [H,W,3] image comes to the host once, and the
+    labels are drawn there as data.py:398-401 does. Unlike the reference, a later rectangle cannot overdraw an earlier label."""
+    import random
+    from PIL import Image, ImageDraw
+    from maskrcnn_amd import image as imagelib
+    if not detections:                                      # blend_image returns the image as it is (data.py:385-387)
+        Image.fromarray(img).save(path)
+        return
+    if seed is not None:
+        random.seed(seed)
+    colors = imagelib.random_colors(len(detections))
+    fusion = Image.fromarray(imagelib.blend_image(img, boxes, masks, colors, device=device).cpu().numpy())
+    draw = ImageDraw.Draw(fusion)
+    for (_, name, b, s), color in zip(detections, colors):
+        draw.text((b[1], b[0]), name + " {:.3f}".format(s), color)
+    fusion.save(path)
 
 
 if __name__ == "__main__":
