@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 23
+#define MRCNN_ABI_VERSION 24
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -802,6 +802,54 @@ int32_t mrcnn_bottleneck_plan(int32_t batch, int32_t height, int32_t width, int3
 int mrcnn_bottleneck_forward_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t planes,
                                  int32_t stride, const float* const weights[14], int32_t winograd4_min_tiles,
                                  int32_t fuse_conv3, void* workspace, size_t workspace_bytes, float* y, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RPN training targets — replaces  data.rpn_samples(anchors, gt_class_ids, gt_boxes, config)  (data.py:449-591, called per item
+ * at data.py:727) and its IoU helper  data.boxes_overlaps  (data.py:151-189), for a batch of B images (csrc/targets.hip).
+ *
+ * Shared by the three calls: anchors fp64 [A][4] (y1,x1,y2,x2), the reference's create_pyramid_anchors, one set for the batch;
+ * ground truth packed as the grouped calls of this library pack it: gt_boxes fp32 [M][4], gt_class_ids int32 [M], gt_off int32
+ * [B+1] (image b owns rows gt_off[b] .. gt_off[b+1]). The rule for one image:
+ *   1 crowd rule: with an id < 0 in the image, crowd rows = id < 0, kept rows = id > 0, id == 0 dropped; without one every row is
+ *     kept. no_crowd[a] = (max IoU of a over the crowd rows) < crowd_iou (true where there is no crowd row).
+ *   2 IoU of every anchor, NARROWED to fp32 (round to nearest), with every kept row, fp32, each operation rounded on its own:
+ *     y1 = max(a_y1, g_y1) ..., inter = max(x2-x1, 0) * max(y2-y1, 0), union = (a_area + g_area) - inter, inter / union correctly
+ *     rounded. 3 iou_argmax[a] = the FIRST kept row with the largest IoU, iou_max[a] that IoU.
+ *   4 match[a] = -1 where iou_max[a] < neg_iou and no_crowd[a], else 0. 5 for every kept row the FIRST anchor with the largest
+ *     IoU gets match 1 (a row no anchor touches: anchor 0). 6 match[a] = 1 where iou_max[a] >= pos_iou.
+ *   7 more than count/2 positives: the ones with the smallest (key, anchor index) stay, the rest become 0. 8 more than
+ *     count - (positives left) negatives: likewise. (The reference draws the ones to reset with np.random.choice; here the caller
+ *     hands in one non-negative int32 key per anchor — independent uniform keys give the same distribution.)
+ *   9 deltas of the positives in ascending anchor index against kept row iou_argmax[a], NumPy >= 2 promotion: gt_h = g_y2 - g_y1
+ *     and gt_cy = g_y1 + 0.5f * gt_h in fp32; a_h, a_cy from the fp64 anchors; dy = ((double)gt_cy - a_cy) / a_h, dh =
+ *     log((double)gt_h / a_h) (dx, dw alike), each divided by its fp64 std_dev and narrowed to fp32. A zero-height box: -inf.
+ * Preconditions for the reference's values: finite anchors with positive area, finite boxes with y2 >= y1, x2 >= x1. On anything
+ * else the calls stay memory-safe: every index is checked, row offsets are clamped into [0, M] and to 1024 rows per image.
+ * Limits: A in [1, 2^24], B in [1, 65535], B * A < 2^31, M <= 1024 * B (at most 1024 rows per image), count >= 1.
+ * No call synchronises with the host; the number of launches does not depend on B. Workspaces: device memory, 16-byte aligned.
+ * (mrcnn_sample_by_key_workspace_bytes: the histograms of the radix select, about 14.5 KB per image.)
+ *
+ * mrcnn_anchor_match — steps 1-6.
+ *   match int32 [B][A]; iou_argmax int32 [B][A]: the row's position within its image (counting all of the image's rows);
+ *   iou_max fp32 [B][A]; gt_argmax int32 [M]: step 5's anchor, -1 for crowd and dropped rows; status int32 [B]: bit 0 = the image
+ *   has no kept row (the reference's np.argmax raises): its match is 0, iou_argmax -1, iou_max 0.
+ * mrcnn_sample_by_key — steps 7-8 on match int32 [B][A] with keys int32 [B][A] → out int32 [B][A] (out == match: in place).
+ * mrcnn_rpn_deltas — step 9: rpn_bbox fp32 [B][count][4] (16-byte aligned; rows past the positives are 0), num_pos int32 [B] the
+ *   number of positives of the image. Positives beyond `count` rows are not written (they occur only when the sampling was
+ *   skipped); num_pos still counts them. std_dev: 4 host doubles.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mrcnn_anchor_match_workspace_bytes(int32_t num_rows);
+int mrcnn_anchor_match(const double* anchors, int32_t num_anchors, const float* gt_boxes, const int32_t* gt_class_ids,
+                       const int32_t* gt_off, int32_t num_rows, int32_t batch, float neg_iou, float pos_iou, float crowd_iou,
+                       int32_t* match, int32_t* iou_argmax, float* iou_max, int32_t* gt_argmax, int32_t* status,
+                       void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_sample_by_key_workspace_bytes(int32_t batch);
+int mrcnn_sample_by_key(const int32_t* match, const int32_t* keys, int32_t batch, int32_t num_anchors, int32_t count,
+                        int32_t* out, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_rpn_deltas_workspace_bytes(int32_t batch, int32_t num_anchors);
+int mrcnn_rpn_deltas(const double* anchors, int32_t num_anchors, const float* gt_boxes, const int32_t* gt_off, int32_t num_rows,
+                     int32_t batch, const int32_t* match, const int32_t* iou_argmax, int32_t count, const double std_dev[4],
+                     float* rpn_bbox, int32_t* num_pos, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

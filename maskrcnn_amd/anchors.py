@@ -22,10 +22,14 @@ def level_anchors(scale, ratios, shape, feature_stride, anchor_stride=1) -> np.n
     return out.reshape(-1, 4)
 
 
-def pyramid_anchors(cfg) -> torch.Tensor:
-    """float32 [sum_l H_l*W_l*R, 4] (261888 rows at 1024x1024)."""
+def pyramid_anchors(cfg, dtype=torch.float32) -> torch.Tensor:
+    """float32 [sum_l H_l*W_l*R, 4] (261888 rows at 1024x1024). dtype=torch.float64: the un-narrowed anchors the reference's
+    create_pyramid_anchors returns (utils.py:223-291), which the RPN training targets read (targets.rpn_targets)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"pyramid_anchors: dtype must be torch.float32 or torch.float64, got {dtype}")
     a = np.concatenate([level_anchors(cfg.rpn_anchor_scales[i], cfg.rpn_anchor_ratios,
                                       cfg.backbone_shapes[i], cfg.backbone_strides[i],
                                       cfg.rpn_anchor_stride)
                         for i in range(len(cfg.rpn_anchor_scales))], axis=0)
-    return torch.from_numpy(a).float()
+    t = torch.from_numpy(a)
+    return t.float() if dtype == torch.float32 else t

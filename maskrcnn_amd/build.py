@@ -50,6 +50,7 @@ SOURCES = {
     "poly.hip": ["-ffp-contract=off"],       # rleFrPoly's 5*x+.5 and ys+s*t+.5: an FMA changes which pixel a boundary point rounds to
     "codec.hip": [],                         # rleFrString / rleToString / rleArea / rleToBbox / rleDecode on tables: integer work only
     "overlay.hip": ["-ffp-contract=off"],    # blend_image: Image.blend's px + 0.2f*(c - px), separately rounded fp32
+    "targets.hip": ["-ffp-contract=off"],    # rpn_samples: boxes_overlaps' fp32 IoU and the fp64 deltas, operation by operation
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-fast-math",
           "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -33,7 +33,8 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
            "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
-           "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances"]
+           "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances",
+           "anchor_match", "sample_by_key", "rpn_deltas"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1765,6 +1766,140 @@ def blend_instances(image: torch.Tensor, masks: torch.Tensor, colors: torch.Tens
 _LIB.define("blend_instances(Tensor image, Tensor masks, Tensor colors, Tensor? boxes=None, int threshold=0) -> Tensor")   # `out` is the Python binding's
 _LIB.impl("blend_instances", lambda image, masks, colors, boxes=None, threshold=0: blend_instances(image, masks, colors, boxes, threshold), "CUDA")
 _LIB.impl("blend_instances", lambda image, *a: _need_gpu(image), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# RPN training targets: data.rpn_samples for a batch (csrc/targets.hip)
+# --------------------------------------------------------------------------------------------------
+def _target_anchors(who, anchors):
+    _need_gpu(anchors)
+    if anchors.dtype != torch.float64 or anchors.dim() != 2 or anchors.size(1) != 4 or anchors.size(0) < 1:
+        raise RuntimeError(f"{who}: anchors must be float64 [A,4] with A >= 1 (anchors.pyramid_anchors(cfg, dtype=torch.float64)), "
+                           f"got {anchors.dtype} {tuple(anchors.shape)}")
+    return anchors.contiguous()
+
+
+def _target_rows(who, gt_boxes, gt_off):
+    _need_gpu(gt_boxes, gt_off)
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 2 or gt_boxes.size(1) != 4:
+        raise RuntimeError(f"{who}: gt_boxes must be float32 [M,4], got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+    if gt_off.dtype != torch.int32 or gt_off.dim() != 1 or gt_off.numel() < 2:
+        raise RuntimeError(f"{who}: gt_off must be int32 [B+1] with B >= 1, got {gt_off.dtype} {tuple(gt_off.shape)}")
+    return gt_boxes.contiguous(), gt_off.contiguous()
+
+
+def _target_map(who, name, t, dtype, b: int, a: int):
+    _need_gpu(t)
+    if t.dtype != dtype or tuple(t.shape) != (b, a):
+        raise RuntimeError(f"{who}: {name} must be {dtype} [{b},{a}], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+@_on_device
+def anchor_match(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: torch.Tensor, gt_off: torch.Tensor,
+                 neg_iou: float = 0.3, pos_iou: float = 0.7, crowd_iou: float = 0.001):
+    """Steps 1-6 of data.rpn_samples (data.py:485-540; the rule is stated at mrcnn_anchor_match in include/maskrcnn_hip.h) for B
+    images: anchors float64 [A,4], ground truth packed as gt_boxes float32 [M,4], gt_class_ids int32 [M], gt_off int32 [B+1] →
+    (match int32 [B,A] of -1 / 0 / 1, iou_argmax int32 [B,A] (row position within the image), iou_max float32 [B,A], gt_argmax
+    int32 [M] (-1: crowd or dropped row), status int32 [B] (bit 0: no kept row in the image)). The thresholds are narrowed to
+    fp32. No host synchronisation."""
+    who = "anchor_match"
+    anchors = _target_anchors(who, anchors)
+    gt_boxes, gt_off = _target_rows(who, gt_boxes, gt_off)
+    _need_gpu(gt_class_ids)
+    m, a, b, dev = gt_boxes.size(0), anchors.size(0), gt_off.numel() - 1, anchors.device
+    if gt_class_ids.dtype != torch.int32 or tuple(gt_class_ids.shape) != (m,):
+        raise RuntimeError(f"{who}: gt_class_ids must be int32 [{m}], got {gt_class_ids.dtype} {tuple(gt_class_ids.shape)}")
+    gt_class_ids = gt_class_ids.contiguous()
+    match = torch.empty(b, a, dtype=torch.int32, device=dev)
+    iou_argmax = torch.empty(b, a, dtype=torch.int32, device=dev)
+    iou_max = torch.empty(b, a, dtype=torch.float32, device=dev)
+    gt_argmax = torch.empty(m, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_anchor_match_workspace_bytes(m))
+    ws = _workspace(nbytes, dev)
+    _launch(lib.mrcnn_anchor_match,
+            (anchors.data_ptr(), a, _ptr(gt_boxes) if m else None, _ptr(gt_class_ids) if m else None, gt_off.data_ptr(), m, b,
+             float(neg_iou), float(pos_iou), float(crowd_iou), match.data_ptr(), iou_argmax.data_ptr(), iou_max.data_ptr(),
+             _ptr(gt_argmax) if m else None, status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, m), 32 * a + 12 * b * a, "anchor_match"))
+    return match, iou_argmax, iou_max, gt_argmax, status
+
+
+@_on_device
+def sample_by_key(match: torch.Tensor, keys: torch.Tensor, count: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Steps 7-8 of data.rpn_samples (data.py:542-557) for match int32 [B,A]: of an image's positives the count // 2 with the
+    smallest (key, anchor index) stay positive, then of its negatives the count - (positives left) with the smallest stay
+    negative; the others become 0. keys int32 [B,A], non-negative (the caller's stand-in for np.random.choice: independent
+    uniform keys draw from the same distribution). → out int32 [B,A] (a new tensor when none is given; `out is match` works in
+    place). No host synchronisation."""
+    who = "sample_by_key"
+    _need_gpu(match, keys, out)
+    if match.dtype != torch.int32 or match.dim() != 2 or match.size(0) < 1 or match.size(1) < 1:
+        raise RuntimeError(f"{who}: match must be int32 [B,A] with B, A >= 1, got {match.dtype} {tuple(match.shape)}")
+    b, a = match.shape
+    same = out is match
+    match = _target_map(who, "match", match, torch.int32, b, a)
+    keys = _target_map(who, "keys", keys, torch.int32, b, a)
+    if out is None:
+        out = torch.empty(b, a, dtype=torch.int32, device=match.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (b, a) or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be a contiguous int32 [{b},{a}] tensor, got {out.dtype} {tuple(out.shape)} strides "
+                           f"{tuple(out.stride())}")
+    if same:
+        match = out
+    nbytes = int(lib.mrcnn_sample_by_key_workspace_bytes(b))
+    ws = _workspace(nbytes, match.device)
+    _launch(lib.mrcnn_sample_by_key,
+            (match.data_ptr(), keys.data_ptr(), b, a, int(count), out.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, int(count)), 8 * 8 * b * a, "sample_by_key"))
+    return out
+
+
+@_on_device
+def rpn_deltas(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_off: torch.Tensor, match: torch.Tensor, iou_argmax: torch.Tensor,
+               count: int, std_dev=(0.1, 0.1, 0.2, 0.2)):
+    """Step 9 of data.rpn_samples (data.py:559-589): the regression deltas of an image's positives (match == 1) in ascending
+    anchor index against row iou_argmax of the image, divided by std_dev (four host numbers, used as fp64) and narrowed to fp32,
+    with the reference's NumPy >= 2 promotion (mrcnn_rpn_deltas in include/maskrcnn_hip.h) → (rpn_bbox float32 [B,count,4], rows
+    past the positives 0; num_pos int32 [B]). Positives beyond `count` are counted, not written. No host synchronisation."""
+    who = "rpn_deltas"
+    anchors = _target_anchors(who, anchors)
+    gt_boxes, gt_off = _target_rows(who, gt_boxes, gt_off)
+    m, a, b, dev = gt_boxes.size(0), anchors.size(0), gt_off.numel() - 1, anchors.device
+    match = _target_map(who, "match", match, torch.int32, b, a)
+    iou_argmax = _target_map(who, "iou_argmax", iou_argmax, torch.int32, b, a)
+    count = int(count)
+    std = [float(v) for v in std_dev]
+    if len(std) != 4:
+        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    rpn_bbox = torch.empty(b, max(count, 0), 4, dtype=torch.float32, device=dev)
+    num_pos = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rpn_deltas_workspace_bytes(b, a))
+    ws = _workspace(nbytes, dev)
+    _launch(lib.mrcnn_rpn_deltas,
+            (anchors.data_ptr(), a, _ptr(gt_boxes) if m else None, gt_off.data_ptr(), m, b, match.data_ptr(), iou_argmax.data_ptr(),
+             count, (ctypes.c_double * 4)(*std), rpn_bbox.data_ptr() if count > 0 else None, num_pos.data_ptr(), ws.data_ptr(),
+             nbytes, _stream()),
+            lambda: (0, (b, a, count), 2 * 4 * b * a + 16 * b * count, "rpn_deltas"))
+    return rpn_bbox, num_pos
+
+
+_LIB.define("anchor_match(Tensor anchors, Tensor gt_boxes, Tensor gt_class_ids, Tensor gt_off, float neg_iou=0.3, float pos_iou=0.7, "
+            "float crowd_iou=0.001) -> (Tensor, Tensor, Tensor, Tensor, Tensor)")
+_LIB.impl("anchor_match", anchor_match, "CUDA")
+_LIB.impl("anchor_match", lambda anchors, *a: _need_gpu(anchors), "CPU")
+_LIB.define("sample_by_key(Tensor match, Tensor keys, int count) -> Tensor")   # `out` is the Python binding's
+_LIB.impl("sample_by_key", lambda match, keys, count: sample_by_key(match, keys, count), "CUDA")
+_LIB.impl("sample_by_key", lambda match, *a: _need_gpu(match), "CPU")
+_LIB.define("rpn_deltas(Tensor anchors, Tensor gt_boxes, Tensor gt_off, Tensor match, Tensor iou_argmax, int count, "
+            "float[] std_dev) -> (Tensor, Tensor)")
+_LIB.impl("rpn_deltas", rpn_deltas, "CUDA")
+_LIB.impl("rpn_deltas", lambda anchors, *a: _need_gpu(anchors), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------
