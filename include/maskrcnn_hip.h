@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 24
+#define MRCNN_ABI_VERSION 25
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -850,6 +850,64 @@ size_t mrcnn_rpn_deltas_workspace_bytes(int32_t batch, int32_t num_anchors);
 int mrcnn_rpn_deltas(const double* anchors, int32_t num_anchors, const float* gt_boxes, const int32_t* gt_off, int32_t num_rows,
                      int32_t batch, const int32_t* match, const int32_t* iou_argmax, int32_t count, const double std_dev[4],
                      float* rpn_bbox, int32_t* num_pos, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Detection training targets — replaces  model.mrn_samples(rpn_rois, gt_class_ids, gt_boxes, gt_masks, config)  (model.py:396-576,
+ * called from MaskRCNN.extract at model.py:1270; batch size 1 there) for a batch of B images (csrc/detection_targets.hip).
+ *
+ * Inputs: rois fp32 [B][N][4] (y1,x1,y2,x2), one N for the batch; zero rows are ordinary RoIs, as in the reference. Ground truth
+ * packed as for mrcnn_anchor_match: gt_boxes fp32 [M][4] in the RoIs' coordinates (the reference normalises both), gt_class_ids
+ * int32 [M], gt_off int32 [B+1]. gt_masks [M][H][W], one byte per pixel (uint8 / bool: the byte's value as a float) or fp32; row m
+ * is the mask of ground-truth row m; one H x W for the call. keys int32 [B][N], non-negative. The rule for one image:
+ *   1 crowd rule, exactly as mrcnn_anchor_match step 1 (crowd_iou is 0.001 in the reference): with an id < 0 in the image, crowd
+ *     rows = id < 0, kept rows = id > 0, id == 0 dropped; without one every row is kept, id 0 included. An image without a kept row
+ *     gets status bit 0, num_pos = num_neg = 0 and outputs that are all 0 / -1 (the reference raises there).
+ *   2 IoU of every RoI with every kept row: boxes_overlaps (data.py:151-189) in fp32, every operation rounded on its own, the
+ *     division correctly rounded, no contraction. iou_max[r] = the largest, gt_index[r] = the FIRST kept row that has it
+ *     (torch.max(dim=1) on the CPU takes the first), counted within ALL of the image's rows.
+ *   3 a RoI is positive where iou_max >= pos_iou (0.5), negative where iou_max < pos_iou and its largest IoU over the crowd rows
+ *     is < crowd_iou, otherwise neither.
+ *   4 pos_limit = (int)((double)count * positive_ratio) (Python's int(count * ratio): 100, 0.33 -> 33). The positives with the
+ *     smallest (key, roi index) are kept, at most pos_limit, and written IN THAT ORDER (the reference's
+ *     positive_indices[randperm][:pos_limit] is a random order; the key order stands in for it, as in mrcnn_sample_by_key).
+ *     num_pos = the number kept.
+ *   5 num_pos == 0: nothing is kept at all (the reference's "BugFixed" rule, model.py:516). Otherwise neg_limit =
+ *     (int)(r * num_pos - num_pos) with r = 1.0 / positive_ratio, in fp64, the product and the difference rounded separately,
+ *     truncated (0.33: 0, 2, 4, ... 62, 64, 67 for num_pos = 0 ... 33). The negatives with the smallest (key, roi index), at most
+ *     neg_limit (and at most count - num_pos: memory safety only), follow the positives in that order. num_neg = their number.
+ *   6 outputs, count rows per image; rows past num_pos + num_neg are 0 (indices -1):
+ *       rois_out fp32 [B][count][4]: the chosen RoIs' bits.   target_class_ids int32 [B][count]: the id of row gt_index for a
+ *       positive, 0 for a negative.   target_deltas fp32 [B][count][4]: boxes_deltas (data.py:103-121) in fp32 operation by
+ *       operation — h = y2 - y1, cy = y1 + 0.5f * h for the RoI and the row, dy = (gt_cy - cy) / h, dh = log(gt_h / h) with the
+ *       quotient in fp32 and the logarithm in fp64, narrowed — then each divided by its fp32 std_dev; 0 for a negative.
+ *       roi_index int32 [B][count]: the RoI's position in its image.   gt_index int32 [B][count]: the matched row's position in
+ *       its image for a positive, -1 for a negative.   num_pos, num_neg, status int32 [B].
+ *   7 mask targets (mrcnn_mask_targets_*): target_mask fp32 [B][count][mh][mw]. For a positive slot s it is
+ *     CropFunction(mh, mw, 0) — crop_per_box, crop_cpu.cpp:13-116, the arithmetic of mrcnn_crop_forward_f32 — of mask
+ *     gt_off[b] + gt_index[s] with box rois_out[s], then torch.round (ties to even: 0.5 -> 0, 1.5 -> 2, 2.5 -> 2). Every other
+ *     slot is zeros. The mask is read in place through the index; no [P][H][W] gather exists.
+ * Preconditions for the reference's values: finite boxes with y2 >= y1, x2 >= x1, and no RoI / row pair whose union is 0 (the
+ * reference gives NaN there; here such a pair never wins a maximum). On anything else the calls stay memory-safe: row offsets are
+ * clamped into [0, M] and to 1024 rows per image, every index read from memory (gt_index, num_pos) is checked before it is
+ * followed, mask offsets are computed in 64 bits.
+ * Limits: N in [1, 4096], at most 1024 rows per image (M <= 1024 * B), count in [1, 1024], B in [1, 65535], H, W in [1, 16384],
+ * mh, mw in [1, 64], positive_ratio in (0, 1]. No call synchronises with the host; each call is ONE launch, whatever B is, and
+ * needs no workspace.
+ *
+ * mrcnn_detection_targets — steps 1-6. std_dev: 4 host floats.
+ * mrcnn_mask_targets_u8 / _f32 — step 7 for byte / fp32 masks; rois_out, gt_index, num_pos as mrcnn_detection_targets wrote them.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_detection_targets(const float* rois, const float* gt_boxes, const int32_t* gt_class_ids, const int32_t* gt_off,
+                            const int32_t* keys, int32_t batch, int32_t num_rois, int32_t num_rows, int32_t count,
+                            double positive_ratio, float pos_iou, float crowd_iou, const float std_dev[4], float* rois_out,
+                            int32_t* target_class_ids, float* target_deltas, int32_t* roi_index, int32_t* gt_index,
+                            int32_t* num_pos, int32_t* num_neg, int32_t* status, mrcnn_stream_t stream);
+int mrcnn_mask_targets_u8(const uint8_t* gt_masks, int32_t num_rows, int32_t height, int32_t width, const int32_t* gt_off,
+                          int32_t batch, int32_t count, const float* rois_out, const int32_t* gt_index, const int32_t* num_pos,
+                          int32_t mask_height, int32_t mask_width, float* target_mask, mrcnn_stream_t stream);
+int mrcnn_mask_targets_f32(const float* gt_masks, int32_t num_rows, int32_t height, int32_t width, const int32_t* gt_off,
+                           int32_t batch, int32_t count, const float* rois_out, const int32_t* gt_index, const int32_t* num_pos,
+                           int32_t mask_height, int32_t mask_width, float* target_mask, mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,7 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
            "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
            "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances",
-           "anchor_match", "sample_by_key", "rpn_deltas"]
+           "anchor_match", "sample_by_key", "rpn_deltas", "detection_targets", "mask_targets"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -1900,6 +1900,107 @@ _LIB.define("rpn_deltas(Tensor anchors, Tensor gt_boxes, Tensor gt_off, Tensor m
             "float[] std_dev) -> (Tensor, Tensor)")
 _LIB.impl("rpn_deltas", rpn_deltas, "CUDA")
 _LIB.impl("rpn_deltas", lambda anchors, *a: _need_gpu(anchors), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# Detection training targets: model.mrn_samples for a batch (csrc/detection_targets.hip)
+# --------------------------------------------------------------------------------------------------
+def _target_out(who, name, t, dtype, shape, dev):
+    """A caller's output tensor, checked — or a new one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    _need_gpu(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise RuntimeError(f"{who}: out tensor {name} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got {t.dtype} "
+                           f"{tuple(t.shape)} strides {tuple(t.stride())} on {t.device}")
+    return t
+
+
+@_on_device
+def detection_targets(rois: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: torch.Tensor, gt_off: torch.Tensor,
+                      keys: torch.Tensor, count: int = 100, positive_ratio: float = 0.33, std_dev=(0.1, 0.1, 0.2, 0.2),
+                      pos_iou: float = 0.5, crowd_iou: float = 0.001, out=None):
+    """Steps 1-6 of model.mrn_samples (model.py:396-576; the rule is stated at mrcnn_detection_targets in include/maskrcnn_hip.h)
+    for B images: rois float32 [B,N,4], ground truth packed as gt_boxes float32 [M,4], gt_class_ids int32 [M], gt_off int32 [B+1],
+    keys int32 [B,N] (non-negative: the stand-in for torch.randperm, as in sample_by_key) →
+    (rois_out float32 [B,count,4], target_class_ids int32 [B,count], target_deltas float32 [B,count,4], roi_index int32 [B,count],
+    gt_index int32 [B,count], num_pos int32 [B], num_neg int32 [B], status int32 [B] (bit 0: no kept row in the image)).
+    The positives come first, then the negatives, each by ascending (key, roi index); rows past num_pos + num_neg are 0 / -1.
+    std_dev: four host numbers, narrowed to fp32, as are the thresholds. out: the eight tensors to write into. One launch, no
+    host synchronisation."""
+    who = "detection_targets"
+    _need_gpu(rois, gt_class_ids, keys)
+    if rois.dtype != torch.float32 or rois.dim() != 3 or rois.size(2) != 4 or rois.size(0) < 1 or rois.size(1) < 1:
+        raise RuntimeError(f"{who}: rois must be float32 [B,N,4] with B, N >= 1, got {rois.dtype} {tuple(rois.shape)}")
+    gt_boxes, gt_off = _target_rows(who, gt_boxes, gt_off)
+    b, n, m, dev = rois.size(0), rois.size(1), gt_boxes.size(0), rois.device
+    if gt_off.numel() != b + 1:
+        raise RuntimeError(f"{who}: gt_off must be int32 [{b + 1}] for {b} images of rois, got {tuple(gt_off.shape)}")
+    if gt_class_ids.dtype != torch.int32 or tuple(gt_class_ids.shape) != (m,):
+        raise RuntimeError(f"{who}: gt_class_ids must be int32 [{m}], got {gt_class_ids.dtype} {tuple(gt_class_ids.shape)}")
+    rois, gt_class_ids = rois.contiguous(), gt_class_ids.contiguous()
+    keys = _target_map(who, "keys", keys, torch.int32, b, n)
+    count = int(count)
+    std = [float(v) for v in std_dev]
+    if len(std) != 4:
+        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    c = max(count, 0)
+    spec = (("rois_out", torch.float32, (b, c, 4)), ("target_class_ids", torch.int32, (b, c)), ("target_deltas", torch.float32, (b, c, 4)),
+            ("roi_index", torch.int32, (b, c)), ("gt_index", torch.int32, (b, c)), ("num_pos", torch.int32, (b,)),
+            ("num_neg", torch.int32, (b,)), ("status", torch.int32, (b,)))
+    if out is not None and len(out) != len(spec):
+        raise RuntimeError(f"{who}: out must hold {len(spec)} tensors ({', '.join(s[0] for s in spec)}), got {len(out)}")
+    outs = tuple(_target_out(who, name, None if out is None else out[i], dtype, shape, dev) for i, (name, dtype, shape) in enumerate(spec))
+    _launch(lib.mrcnn_detection_targets,
+            (rois.data_ptr(), _ptr(gt_boxes) if m else None, _ptr(gt_class_ids) if m else None, gt_off.data_ptr(), keys.data_ptr(),
+             b, n, m, count, float(positive_ratio), float(pos_iou), float(crowd_iou), (ctypes.c_float * 4)(*std),
+             *[t.data_ptr() if t.numel() else None for t in outs], _stream()),
+            lambda: (0, (b, n, m), 20 * b * n + 20 * m + 44 * b * c, "detection_targets"))
+    return outs
+
+
+@_on_device
+def mask_targets(gt_masks: torch.Tensor, gt_off: torch.Tensor, rois_out: torch.Tensor, gt_index: torch.Tensor,
+                 num_pos: torch.Tensor, mask_shape=(28, 28), out: torch.Tensor | None = None) -> torch.Tensor:
+    """Step 7 of model.mrn_samples (model.py:491-507): for slot s < num_pos[b] of image b, CropFunction(mh, mw, 0) of mask row
+    gt_off[b] + gt_index[b,s] with box rois_out[b,s], then torch.round; zeros for every other slot → target_mask float32
+    [B,count,mh,mw]. gt_masks [M,H,W] uint8 / bool (the byte's value as a float) or float32, read in place through the index.
+    rois_out float32 [B,count,4], gt_index int32 [B,count], num_pos int32 [B] as detection_targets returns them. One launch, no
+    host synchronisation."""
+    who = "mask_targets"
+    _need_gpu(gt_masks, gt_off, rois_out, gt_index, num_pos)
+    if gt_masks.dtype not in (torch.uint8, torch.bool, torch.float32) or gt_masks.dim() != 3:
+        raise RuntimeError(f"{who}: gt_masks must be uint8, bool or float32 [M,H,W], got {gt_masks.dtype} {tuple(gt_masks.shape)}")
+    if rois_out.dtype != torch.float32 or rois_out.dim() != 3 or rois_out.size(2) != 4 or rois_out.size(0) < 1:
+        raise RuntimeError(f"{who}: rois_out must be float32 [B,count,4], got {rois_out.dtype} {tuple(rois_out.shape)}")
+    b, count, dev = rois_out.size(0), rois_out.size(1), rois_out.device
+    if gt_off.dtype != torch.int32 or tuple(gt_off.shape) != (b + 1,):
+        raise RuntimeError(f"{who}: gt_off must be int32 [{b + 1}], got {gt_off.dtype} {tuple(gt_off.shape)}")
+    gt_index = _target_map(who, "gt_index", gt_index, torch.int32, b, count)
+    if num_pos.dtype != torch.int32 or tuple(num_pos.shape) != (b,):
+        raise RuntimeError(f"{who}: num_pos must be int32 [{b}], got {num_pos.dtype} {tuple(num_pos.shape)}")
+    if len(mask_shape) != 2:
+        raise RuntimeError(f"{who}: mask_shape must be (height, width), got {tuple(mask_shape)}")
+    mh, mw = int(mask_shape[0]), int(mask_shape[1])
+    gt_masks, gt_off, rois_out, num_pos = gt_masks.contiguous(), gt_off.contiguous(), rois_out.contiguous(), num_pos.contiguous()
+    m, h, w = gt_masks.shape
+    out = _target_out(who, "target_mask", out, torch.float32, (b, count, max(mh, 0), max(mw, 0)), dev)
+    fn = lib.mrcnn_mask_targets_f32 if gt_masks.dtype == torch.float32 else lib.mrcnn_mask_targets_u8
+    _launch(fn, (gt_masks.data_ptr() if gt_masks.numel() else None, m, h, w, gt_off.data_ptr(), b, count, _ptr(rois_out) if count else None,
+                 _ptr(gt_index) if count else None, num_pos.data_ptr(), mh, mw, out.data_ptr() if out.numel() else None, _stream()),
+            lambda: (0, (b, count, mh * mw), 4 * b * count * mh * mw, "mask_targets"))
+    return out
+
+
+_LIB.define("detection_targets(Tensor rois, Tensor gt_boxes, Tensor gt_class_ids, Tensor gt_off, Tensor keys, int count=100, "
+            "float positive_ratio=0.33, float[] std_dev=[0.1, 0.1, 0.2, 0.2], float pos_iou=0.5, float crowd_iou=0.001) -> "
+            "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")   # `out` is the Python binding's
+_LIB.impl("detection_targets", lambda *a, **k: detection_targets(*a, **k), "CUDA")
+_LIB.impl("detection_targets", lambda rois, *a, **k: _need_gpu(rois), "CPU")
+_LIB.define("mask_targets(Tensor gt_masks, Tensor gt_off, Tensor rois_out, Tensor gt_index, Tensor num_pos, "
+            "int[] mask_shape=[28, 28]) -> Tensor")
+_LIB.impl("mask_targets", lambda *a, **k: mask_targets(*a, **k), "CUDA")
+_LIB.impl("mask_targets", lambda gt_masks, *a, **k: _need_gpu(gt_masks), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------
