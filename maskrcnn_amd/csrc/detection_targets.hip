@@ -1,9 +1,9 @@
 // Detection training targets: model.mrn_samples (model.py:396-576) for a batch of images, in two entry points. The rule is stated
 // at mrcnn_detection_targets in include/maskrcnn_hip.h.
 //
-//   mrcnn_detection_targets   steps 1-6: crowd rule, fp32 IoU of every RoI against every kept row (boxes_overlaps, data.py:151-189:
-//                             each operation separately rounded, correctly rounded division), first argmax, the classes, the
-//                             positives and negatives with the smallest (key, roi index), boxes_deltas in fp32 with an fp64 log.
+//   mrcnn_detection_targets   steps 1-6: crowd rule, fp32 IoU of every RoI against every kept row, first argmax (target_match.hpp,
+//                             shared with csrc/targets.hip), the classes, the positives and negatives with the smallest
+//                             (key, roi index), boxes_deltas in fp32 with an fp64 log.
 //   mrcnn_mask_targets_*      step 7: crop_and_resize of the matched row's mask with the RoI as the box (the arithmetic of
 //                             csrc/crop.hip: crop_math.hpp), rounded to nearest even.
 //
@@ -28,35 +28,22 @@
 
 #include "common.hpp"
 #include "crop_math.hpp"
+#include "target_match.hpp"
 
 namespace {
 
+using namespace mrcnn_match;
+
 constexpr int kBlock = 1024;               // detection_targets: one workgroup per image
 constexpr int kMaskBlock = 256;
-constexpr int kMaxRows = 1024;             // rows of one image (LDS; 10 bits of the sort key)
 constexpr int kMaxRois = 4096;             // RoIs of one image (LDS sort; 12 bits of the sort key)
 constexpr int kMaxCount = 1024;
-constexpr int kMaxBatch = 65535;           // an image is a grid row
 constexpr int kMaxMaskSide = 64;
 constexpr int kMaxImageSide = 16384;
 constexpr int kRowBits = 10, kRoiBits = 12, kKeyBits = 31;
+static_assert(kMaxRows == 1 << kRowBits && kMaxRois == 1 << kRoiBits, "the sort key's row and RoI fields");
 constexpr int kClassShift = kRowBits + kRoiBits + kKeyBits;
 constexpr unsigned long long kPadding = ~0ull;
-
-struct Rows {
-    int start, n;
-};
-
-// rows of image b, whatever gt_off holds: inside [0, m] and at most kMaxRows of them
-__device__ __forceinline__ Rows image_rows(const int32_t* gt_off, int b, int m) {
-    const int s = min(max(gt_off[b], 0), m);
-    const int e = min(max(gt_off[b + 1], s), m);
-    return Rows{s, min(e - s, kMaxRows)};
-}
-
-// crowd rule, quirk included (model.py:435-442): with a crowd row in the image, rows with id > 0 are kept and id 0 is dropped;
-// without one every row is kept
-__device__ __forceinline__ bool row_kept(int id, bool image_has_crowd) { return image_has_crowd ? id > 0 : true; }
 
 struct TargetParams {
     const float* rois;
@@ -109,36 +96,25 @@ __global__ __launch_bounds__(kBlock) void detection_targets_kernel(TargetParams 
         for (int i = tid; i < sort_n; i += kBlock) {
             unsigned long long key = kPadding;
             if (i < p.n) {
-                const float ay1 = rois[4 * i], ax1 = rois[4 * i + 1], ay2 = rois[4 * i + 2], ax2 = rois[4 * i + 3];
-                const float a_area = (ay2 - ay1) * (ax2 - ax1);
-                float best = -1.f, crowd_max = 0.f;
-                int arg = -1;
+                const float4 roi = make_float4(rois[4 * i], rois[4 * i + 1], rois[4 * i + 2], rois[4 * i + 3]);
+                const float a_area = box_area(roi);
+                Match walk;
                 for (int g = 0; g < r.n; ++g) {
                     const float4 box = s_box[g];
-                    const float y1 = fmaxf(ay1, box.x), x1 = fmaxf(ax1, box.y), y2 = fminf(ay2, box.z), x2 = fminf(ax2, box.w);
-                    const float inter = fmaxf(x2 - x1, 0.f) * fmaxf(y2 - y1, 0.f);
-                    const float g_area = (box.z - box.x) * (box.w - box.y);
-                    const float uni = (a_area + g_area) - inter;
-                    const float iou = inter / uni;
+                    const float iou = box_iou(roi, a_area, box, box_area(box));
                     const int id = s_id[g];
-                    if (row_kept(id, crowd != 0)) {
-                        if (iou > best) {                  // the FIRST largest, as torch.max(dim=1); a NaN never wins
-                            best = iou;
-                            arg = g;
-                        }
-                    } else if (id < 0) {
-                        crowd_max = fmaxf(crowd_max, iou);
-                    }
+                    if (row_kept(id, crowd != 0)) walk.kept_row(g, iou);
+                    else if (id < 0) walk.crowd_row(iou);
                 }
                 unsigned long long cls = 2ull;
-                if (arg >= 0) {
-                    if (best >= p.pos_iou) cls = 0ull;
-                    else if (best < p.pos_iou && crowd_max < p.crowd_iou) cls = 1ull;
+                if (walk.arg >= 0) {
+                    if (walk.best >= p.pos_iou) cls = 0ull;
+                    else if (walk.best < p.pos_iou && walk.crowd_max < p.crowd_iou) cls = 1ull;
                 }
                 my_pos += cls == 0ull;
                 my_neg += cls == 1ull;
                 key = (cls << kClassShift) | ((unsigned long long)((uint32_t)keys[i] & 0x7fffffffu) << (kRowBits + kRoiBits)) |
-                      ((unsigned long long)(uint32_t)i << kRowBits) | (unsigned long long)(uint32_t)max(arg, 0);
+                      ((unsigned long long)(uint32_t)i << kRowBits) | (unsigned long long)(uint32_t)max(walk.arg, 0);
             }
             s_key[i] = key;
         }
@@ -262,10 +238,8 @@ template <typename T>
 int mask_targets(const char* who, const T* gt_masks, int32_t num_rows, int32_t height, int32_t width, const int32_t* gt_off,
                  int32_t batch, int32_t count, const float* rois_out, const int32_t* gt_index, const int32_t* num_pos,
                  int32_t mask_height, int32_t mask_width, float* target_mask, mrcnn_stream_t stream) {
-    MRCNN_REQUIRE(batch >= 1 && batch <= kMaxBatch, "%s: batch=%d must be in [1, %d]", who, batch, kMaxBatch);
+    if (int rc = check_rows(who, num_rows, batch)) return rc;
     MRCNN_REQUIRE(count >= 1 && count <= kMaxCount, "%s: count=%d must be in [1, %d]", who, count, kMaxCount);
-    MRCNN_REQUIRE(num_rows >= 0 && (int64_t)num_rows <= (int64_t)kMaxRows * batch,
-                  "%s: num_rows=%d must be in [0, %d * batch]: at most %d rows per image", who, num_rows, kMaxRows, kMaxRows);
     MRCNN_REQUIRE(height >= 1 && height <= kMaxImageSide && width >= 1 && width <= kMaxImageSide,
                   "%s: masks of %d x %d; height and width must be in [1, %d]", who, height, width, kMaxImageSide);
     MRCNN_REQUIRE(mask_height >= 1 && mask_height <= kMaxMaskSide && mask_width >= 1 && mask_width <= kMaxMaskSide,
@@ -287,11 +261,9 @@ extern "C" int mrcnn_detection_targets(const float* rois, const float* gt_boxes,
                                        int32_t* gt_index, int32_t* num_pos, int32_t* num_neg, int32_t* status,
                                        mrcnn_stream_t stream) {
     const char* who = "detection_targets";
-    MRCNN_REQUIRE(batch >= 1 && batch <= kMaxBatch, "%s: batch=%d must be in [1, %d]", who, batch, kMaxBatch);
+    if (int rc = check_rows(who, num_rows, batch)) return rc;
     MRCNN_REQUIRE(num_rois >= 1 && num_rois <= kMaxRois, "%s: num_rois=%d must be in [1, %d]", who, num_rois, kMaxRois);
     MRCNN_REQUIRE(count >= 1 && count <= kMaxCount, "%s: count=%d must be in [1, %d]", who, count, kMaxCount);
-    MRCNN_REQUIRE(num_rows >= 0 && (int64_t)num_rows <= (int64_t)kMaxRows * batch,
-                  "%s: num_rows=%d must be in [0, %d * batch]: at most %d rows per image", who, num_rows, kMaxRows, kMaxRows);
     MRCNN_REQUIRE(positive_ratio > 0.0 && positive_ratio <= 1.0, "%s: positive_ratio=%g must be in (0, 1]", who, positive_ratio);
     MRCNN_REQUIRE(rois && gt_off && keys && std_dev && rois_out && target_class_ids && target_deltas && roi_index && gt_index &&
                       num_pos && num_neg && status, "%s: null pointer", who);

@@ -1,8 +1,8 @@
 // RPN training targets: data.rpn_samples (data.py:449-591) for a batch of images, in three entry points.
 //
-//   mrcnn_anchor_match   steps 1-6 of the rule in include/maskrcnn_hip.h: fp32 IoU of every anchor against every row of every image
-//                        (boxes_overlaps, data.py:151-189: each operation separately rounded, correctly rounded division), the row
-//                        argmax / max, the crowd rule, the thresholds, and the column argmax (the forced positives).
+//   mrcnn_anchor_match   steps 1-6 of the rule in include/maskrcnn_hip.h: fp32 IoU of every anchor against every row of every image,
+//                        the row argmax / max and the crowd rule (target_match.hpp, shared with csrc/detection_targets.hip), the
+//                        thresholds, and the column argmax (the forced positives).
 //   mrcnn_sample_by_key  steps 7-8: of the positives (negatives) of an image the ones with the smallest (key, anchor index) are kept.
 //   mrcnn_rpn_deltas     step 9: the positives' regression deltas in ascending anchor index, NumPy >= 2 promotion (fp32 box
 //                        centre / size, fp64 anchor side, fp64 division and log, fp64 std-dev, narrowed to fp32 at the end).
@@ -30,33 +30,19 @@
 // Every index is checked where it is used: row offsets are clamped into [0, num_rows] and to 1024 rows an image, iou_argmax is
 // compared with the image's row count, a decoded anchor index with A. Nothing here synchronises with the host.
 #include "common.hpp"
+#include "target_match.hpp"
 
 namespace {
 
+using namespace mrcnn_match;
+
 constexpr int kBlock = 256;
-constexpr int kMaxRows = 1024;             // rows of one image (LDS)
 constexpr int kMaxAnchors = 1 << 24;       // index bits of the packed sampling key
-constexpr int kMaxBatch = 65535;           // an image is a grid row
 constexpr int kPasses = 7;                 // 8-bit digits of the 56-bit (key << 24 | index)
 constexpr int kSampleItems = 8;            // anchors per thread in a sampling pass
 constexpr int kDeltaItems = 16;            // anchors per thread in the delta launches
 constexpr int kDeltaChunk = kBlock * kDeltaItems;
 constexpr unsigned long long kKeptInit = 0xffffffffull;   // (IoU +0, anchor 0); 0 = not a kept row
-
-struct Rows {
-    int start, n;
-};
-
-// rows of image b, whatever gt_off holds: inside [0, m] and at most kMaxRows of them
-__device__ __forceinline__ Rows image_rows(const int32_t* gt_off, int b, int m) {
-    const int s = min(max(gt_off[b], 0), m);
-    const int e = min(max(gt_off[b + 1], s), m);
-    return Rows{s, min(e - s, kMaxRows)};
-}
-
-// crowd rule, quirk included (data.py:496-502): with a crowd row in the image, rows with id > 0 are kept and id 0 is dropped;
-// without one every row is kept
-__device__ __forceinline__ bool row_kept(int id, bool image_has_crowd) { return image_has_crowd ? id > 0 : true; }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // anchor_match
@@ -99,14 +85,12 @@ __global__ __launch_bounds__(kBlock) void anchor_match_kernel(MatchParams p) {
     const int tid = (int)threadIdx.x;
     const int a = (int)blockIdx.x * kBlock + tid;
     const bool live = a < p.a;
-    float ay1 = 0.f, ax1 = 0.f, ay2 = 0.f, ax2 = 0.f;
+    float4 anchor = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live) {   // .float(): round to nearest
-        ay1 = (float)p.anchors[4 * (int64_t)a];
-        ax1 = (float)p.anchors[4 * (int64_t)a + 1];
-        ay2 = (float)p.anchors[4 * (int64_t)a + 2];
-        ax2 = (float)p.anchors[4 * (int64_t)a + 3];
+        const double* an = p.anchors + 4 * (int64_t)a;
+        anchor = make_float4((float)an[0], (float)an[1], (float)an[2], (float)an[3]);
     }
-    const float a_area = (ay2 - ay1) * (ax2 - ax1);
+    const float a_area = box_area(anchor);
     const unsigned long long low = (unsigned long long)(~(uint32_t)a);
     const int lane = tid % mrcnn::kWave;
 
@@ -119,27 +103,19 @@ __global__ __launch_bounds__(kBlock) void anchor_match_kernel(MatchParams p) {
             const float4 box = make_float4(g[0], g[1], g[2], g[3]);
             const int id = p.ids[r.start + i];
             s_box[i] = box;
-            s_area[i] = (box.z - box.x) * (box.w - box.y);
+            s_area[i] = box_area(box);
             s_id[i] = id;
             s_key[i] = 0ull;
             crowd |= id < 0;
         }
         crowd = __syncthreads_or(crowd);
 
-        float best = -1.f, crowd_max = 0.f;
-        int arg = -1;
+        Match walk;
         for (int g = 0; g < r.n; ++g) {
-            const float4 box = s_box[g];
-            const float y1 = fmaxf(ay1, box.x), x1 = fmaxf(ax1, box.y), y2 = fminf(ay2, box.z), x2 = fminf(ax2, box.w);
-            const float inter = fmaxf(x2 - x1, 0.f) * fmaxf(y2 - y1, 0.f);
-            const float uni = (a_area + s_area[g]) - inter;
-            const float iou = inter / uni;
+            const float iou = box_iou(anchor, a_area, s_box[g], s_area[g]);
             const int id = s_id[g];
             if (row_kept(id, crowd != 0)) {
-                if (iou > best) {                          // the FIRST largest, as np.argmax
-                    best = iou;
-                    arg = g;
-                }
+                walk.kept_row(g, iou);
                 // the wave's largest IoU with this row, and its first lane (lanes are in anchor order): ONE LDS atomic per wave
                 // and row, and none where no lane of the wave touches the box
                 const float mine = live && iou > 0.f ? iou : 0.f;
@@ -152,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void anchor_match_kernel(MatchParams p) {
                         atomicMax(&s_key[g], ((unsigned long long)__float_as_uint(mine) << 32) | low);
                 }
             } else if (id < 0) {
-                crowd_max = fmaxf(crowd_max, iou);
+                walk.crowd_row(iou);
             }
         }
         __syncthreads();
@@ -163,13 +139,13 @@ __global__ __launch_bounds__(kBlock) void anchor_match_kernel(MatchParams p) {
         if (live) {
             const int64_t o = (int64_t)b * p.a + a;
             int mt = 0;
-            if (arg >= 0) {
-                if (best >= p.pos) mt = 1;
-                else if (best < p.neg && crowd_max < p.crowd) mt = -1;
+            if (walk.arg >= 0) {
+                if (walk.best >= p.pos) mt = 1;
+                else if (walk.best < p.neg && walk.crowd_max < p.crowd) mt = -1;
             }
             p.match[o] = mt;
-            p.argmax[o] = arg;
-            p.iou_max[o] = arg >= 0 ? best : 0.f;
+            p.argmax[o] = walk.arg;
+            p.iou_max[o] = walk.arg >= 0 ? walk.best : 0.f;
         }
     }
 }
@@ -419,30 +395,13 @@ __global__ __launch_bounds__(kBlock) void rpn_deltas_kernel(DeltaParams p) {
 
 int delta_chunks(int32_t a) { return (a + kDeltaChunk - 1) / kDeltaChunk; }
 
-bool shape_ok(const char* who, int32_t a, int32_t batch) {
-    if (a < 1 || a > kMaxAnchors) {
-        mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: num_anchors=%d must be in [1, %d]", who, a, kMaxAnchors);
-        return false;
-    }
-    if (batch < 1 || batch > kMaxBatch) {
-        mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: batch=%d must be in [1, %d]", who, batch, kMaxBatch);
-        return false;
-    }
-    if ((int64_t)a * batch >= (int64_t)1 << 31) {
-        mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: batch * num_anchors = %lld is too large (must be < 2^31)", who,
-                    (long long)((int64_t)a * batch));
-        return false;
-    }
-    return true;
-}
-
-bool rows_ok(const char* who, int32_t m, int32_t batch) {
-    if (m < 0 || (int64_t)m > (int64_t)kMaxRows * batch) {
-        mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: num_rows=%d must be in [0, %d * batch]: at most %d rows per image", who, m,
-                    kMaxRows, kMaxRows);
-        return false;
-    }
-    return true;
+// the limits of an entry point: A, B, the packed rows (sample_by_key takes none) and A * B
+int check_shape(const char* who, int32_t a, int32_t batch, int32_t num_rows = 0) {
+    MRCNN_REQUIRE(a >= 1 && a <= kMaxAnchors, "%s: num_anchors=%d must be in [1, %d]", who, a, kMaxAnchors);
+    if (int rc = check_rows(who, num_rows, batch)) return rc;
+    MRCNN_REQUIRE((int64_t)a * batch < (int64_t)1 << 31, "%s: batch * num_anchors = %lld is too large (must be < 2^31)", who,
+                  (long long)((int64_t)a * batch));
+    return MRCNN_OK;
 }
 
 }  // namespace
@@ -455,7 +414,7 @@ extern "C" int mrcnn_anchor_match(const double* anchors, int32_t num_anchors, co
                                   const int32_t* gt_off, int32_t num_rows, int32_t batch, float neg_iou, float pos_iou,
                                   float crowd_iou, int32_t* match, int32_t* iou_argmax, float* iou_max, int32_t* gt_argmax,
                                   int32_t* status, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
-    if (!shape_ok("anchor_match", num_anchors, batch) || !rows_ok("anchor_match", num_rows, batch)) return MRCNN_ERR_INVALID_ARGUMENT;
+    if (int rc = check_shape("anchor_match", num_anchors, batch, num_rows)) return rc;
     MRCNN_REQUIRE(anchors && gt_off && match && iou_argmax && iou_max && status, "anchor_match: null pointer");
     MRCNN_REQUIRE(num_rows == 0 || (gt_boxes && gt_class_ids && gt_argmax && workspace), "anchor_match: null pointer");
     MRCNN_REQUIRE(workspace_bytes >= mrcnn_anchor_match_workspace_bytes(num_rows), "anchor_match: workspace of %zu bytes, %zu needed",
@@ -488,7 +447,7 @@ extern "C" size_t mrcnn_sample_by_key_workspace_bytes(int32_t batch) {
 
 extern "C" int mrcnn_sample_by_key(const int32_t* match, const int32_t* keys, int32_t batch, int32_t num_anchors, int32_t count,
                                    int32_t* out, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
-    if (!shape_ok("sample_by_key", num_anchors, batch)) return MRCNN_ERR_INVALID_ARGUMENT;
+    if (int rc = check_shape("sample_by_key", num_anchors, batch)) return rc;
     MRCNN_REQUIRE(count >= 1, "sample_by_key: count=%d must be >= 1", count);
     MRCNN_REQUIRE(match && keys && out && workspace, "sample_by_key: null pointer");
     MRCNN_REQUIRE(workspace_bytes >= mrcnn_sample_by_key_workspace_bytes(batch), "sample_by_key: workspace of %zu bytes, %zu needed",
@@ -519,7 +478,7 @@ extern "C" int mrcnn_rpn_deltas(const double* anchors, int32_t num_anchors, cons
                                 int32_t num_rows, int32_t batch, const int32_t* match, const int32_t* iou_argmax, int32_t count,
                                 const double std_dev[4], float* rpn_bbox, int32_t* num_pos, void* workspace, size_t workspace_bytes,
                                 mrcnn_stream_t stream) {
-    if (!shape_ok("rpn_deltas", num_anchors, batch) || !rows_ok("rpn_deltas", num_rows, batch)) return MRCNN_ERR_INVALID_ARGUMENT;
+    if (int rc = check_shape("rpn_deltas", num_anchors, batch, num_rows)) return rc;
     MRCNN_REQUIRE(count >= 1, "rpn_deltas: count=%d must be >= 1", count);
     MRCNN_REQUIRE((int64_t)count * batch < (int64_t)1 << 29, "rpn_deltas: batch * count = %lld is too large (must be < 2^29)",
                   (long long)((int64_t)count * batch));

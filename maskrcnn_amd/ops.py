@@ -1788,6 +1788,25 @@ def _target_rows(who, gt_boxes, gt_off):
     return gt_boxes.contiguous(), gt_off.contiguous()
 
 
+def _target_ids(who, gt_class_ids, m: int):
+    _need_gpu(gt_class_ids)
+    if gt_class_ids.dtype != torch.int32 or tuple(gt_class_ids.shape) != (m,):
+        raise RuntimeError(f"{who}: gt_class_ids must be int32 [{m}], got {gt_class_ids.dtype} {tuple(gt_class_ids.shape)}")
+    return gt_class_ids.contiguous()
+
+
+def _target_std(who, std_dev):
+    std = [float(v) for v in std_dev]
+    if len(std) != 4:
+        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    return std
+
+
+def _ptr_if(m: int, t):
+    """The pointer of a tensor of the m packed rows: none where there is no row (a null pointer is what the library expects then)."""
+    return t.data_ptr() if m else None
+
+
 def _target_map(who, name, t, dtype, b: int, a: int):
     _need_gpu(t)
     if t.dtype != dtype or tuple(t.shape) != (b, a):
@@ -1810,11 +1829,8 @@ def anchor_match(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: to
     who = "anchor_match"
     anchors = _target_anchors(who, anchors)
     gt_boxes, gt_off = _target_rows(who, gt_boxes, gt_off)
-    _need_gpu(gt_class_ids)
     m, a, b, dev = gt_boxes.size(0), anchors.size(0), gt_off.numel() - 1, anchors.device
-    if gt_class_ids.dtype != torch.int32 or tuple(gt_class_ids.shape) != (m,):
-        raise RuntimeError(f"{who}: gt_class_ids must be int32 [{m}], got {gt_class_ids.dtype} {tuple(gt_class_ids.shape)}")
-    gt_class_ids = gt_class_ids.contiguous()
+    gt_class_ids = _target_ids(who, gt_class_ids, m)
     match = torch.empty(b, a, dtype=torch.int32, device=dev)
     iou_argmax = torch.empty(b, a, dtype=torch.int32, device=dev)
     iou_max = torch.empty(b, a, dtype=torch.float32, device=dev)
@@ -1823,9 +1839,9 @@ def anchor_match(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: to
     nbytes = int(lib.mrcnn_anchor_match_workspace_bytes(m))
     ws = _workspace(nbytes, dev)
     _launch(lib.mrcnn_anchor_match,
-            (anchors.data_ptr(), a, _ptr(gt_boxes) if m else None, _ptr(gt_class_ids) if m else None, gt_off.data_ptr(), m, b,
+            (anchors.data_ptr(), a, _ptr_if(m, gt_boxes), _ptr_if(m, gt_class_ids), gt_off.data_ptr(), m, b,
              float(neg_iou), float(pos_iou), float(crowd_iou), match.data_ptr(), iou_argmax.data_ptr(), iou_max.data_ptr(),
-             _ptr(gt_argmax) if m else None, status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+             _ptr_if(m, gt_argmax), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
             lambda: (0, (b, a, m), 32 * a + 12 * b * a, "anchor_match"))
     return match, iou_argmax, iou_max, gt_argmax, status
 
@@ -1874,15 +1890,13 @@ def rpn_deltas(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_off: torch.Tens
     match = _target_map(who, "match", match, torch.int32, b, a)
     iou_argmax = _target_map(who, "iou_argmax", iou_argmax, torch.int32, b, a)
     count = int(count)
-    std = [float(v) for v in std_dev]
-    if len(std) != 4:
-        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    std = _target_std(who, std_dev)
     rpn_bbox = torch.empty(b, max(count, 0), 4, dtype=torch.float32, device=dev)
     num_pos = torch.empty(b, dtype=torch.int32, device=dev)
     nbytes = int(lib.mrcnn_rpn_deltas_workspace_bytes(b, a))
     ws = _workspace(nbytes, dev)
     _launch(lib.mrcnn_rpn_deltas,
-            (anchors.data_ptr(), a, _ptr(gt_boxes) if m else None, gt_off.data_ptr(), m, b, match.data_ptr(), iou_argmax.data_ptr(),
+            (anchors.data_ptr(), a, _ptr_if(m, gt_boxes), gt_off.data_ptr(), m, b, match.data_ptr(), iou_argmax.data_ptr(),
              count, (ctypes.c_double * 4)(*std), rpn_bbox.data_ptr() if count > 0 else None, num_pos.data_ptr(), ws.data_ptr(),
              nbytes, _stream()),
             lambda: (0, (b, a, count), 2 * 4 * b * a + 16 * b * count, "rpn_deltas"))
@@ -1936,14 +1950,10 @@ def detection_targets(rois: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: 
     b, n, m, dev = rois.size(0), rois.size(1), gt_boxes.size(0), rois.device
     if gt_off.numel() != b + 1:
         raise RuntimeError(f"{who}: gt_off must be int32 [{b + 1}] for {b} images of rois, got {tuple(gt_off.shape)}")
-    if gt_class_ids.dtype != torch.int32 or tuple(gt_class_ids.shape) != (m,):
-        raise RuntimeError(f"{who}: gt_class_ids must be int32 [{m}], got {gt_class_ids.dtype} {tuple(gt_class_ids.shape)}")
-    rois, gt_class_ids = rois.contiguous(), gt_class_ids.contiguous()
+    rois, gt_class_ids = rois.contiguous(), _target_ids(who, gt_class_ids, m)
     keys = _target_map(who, "keys", keys, torch.int32, b, n)
     count = int(count)
-    std = [float(v) for v in std_dev]
-    if len(std) != 4:
-        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    std = _target_std(who, std_dev)
     c = max(count, 0)
     spec = (("rois_out", torch.float32, (b, c, 4)), ("target_class_ids", torch.int32, (b, c)), ("target_deltas", torch.float32, (b, c, 4)),
             ("roi_index", torch.int32, (b, c)), ("gt_index", torch.int32, (b, c)), ("num_pos", torch.int32, (b,)),
@@ -1952,7 +1962,7 @@ def detection_targets(rois: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: 
         raise RuntimeError(f"{who}: out must hold {len(spec)} tensors ({', '.join(s[0] for s in spec)}), got {len(out)}")
     outs = tuple(_target_out(who, name, None if out is None else out[i], dtype, shape, dev) for i, (name, dtype, shape) in enumerate(spec))
     _launch(lib.mrcnn_detection_targets,
-            (rois.data_ptr(), _ptr(gt_boxes) if m else None, _ptr(gt_class_ids) if m else None, gt_off.data_ptr(), keys.data_ptr(),
+            (rois.data_ptr(), _ptr_if(m, gt_boxes), _ptr_if(m, gt_class_ids), gt_off.data_ptr(), keys.data_ptr(),
              b, n, m, count, float(positive_ratio), float(pos_iou), float(crowd_iou), (ctypes.c_float * 4)(*std),
              *[t.data_ptr() if t.numel() else None for t in outs], _stream()),
             lambda: (0, (b, n, m), 20 * b * n + 20 * m + 44 * b * c, "detection_targets"))

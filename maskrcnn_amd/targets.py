@@ -53,6 +53,13 @@ def _overlaps(a32: np.ndarray, g32: np.ndarray) -> np.ndarray:
         return (inter / ((a_area + g_area) - inter)).astype(np.float32)
 
 
+def _crowd_and_kept(ids: np.ndarray):
+    """The crowd rule, quirk included (data.py:496-502, model.py:435-442) → (crowd rows, kept rows): with a crowd row (id < 0) in
+    the image the rows with id > 0 are kept and id 0 is dropped; without one every row is kept."""
+    crowd = np.where(ids < 0)[0]
+    return crowd, np.where(ids > 0)[0] if crowd.size else np.arange(ids.size)
+
+
 def match_numpy(anchors, gt_boxes, gt_class_ids, neg_iou=NEG_IOU, pos_iou=POS_IOU, crowd_iou=CROWD_IOU):
     """Steps 1-6 for one image → (match int32 [A], iou_argmax int32 [A], iou_max float32 [A], gt_argmax int32 [G], status int).
     Row indices count all of the image's rows; status bit 0: no kept row (match 0, iou_argmax -1, iou_max 0)."""
@@ -60,8 +67,7 @@ def match_numpy(anchors, gt_boxes, gt_class_ids, neg_iou=NEG_IOU, pos_iou=POS_IO
     boxes = np.asarray(gt_boxes, np.float32).reshape(-1, 4)
     ids = np.asarray(gt_class_ids, np.int32).reshape(-1)
     n = a32.shape[0]
-    crowd = np.where(ids < 0)[0]
-    kept = np.where(ids > 0)[0] if crowd.size else np.arange(ids.size)
+    crowd, kept = _crowd_and_kept(ids)
     match = np.zeros(n, np.int32)
     gt_argmax = np.full(ids.size, -1, np.int32)
     if kept.size == 0:
@@ -137,8 +143,7 @@ def _check_image(i: int, boxes: np.ndarray, ids: np.ndarray, who: str = "rpn_tar
         raise ValueError(f"{who}: image {i} has {boxes.shape[0]} rows; at most {MAX_ROWS_PER_IMAGE} per image")
     if not np.isfinite(boxes).all() or (boxes[:, 2] < boxes[:, 0]).any() or (boxes[:, 3] < boxes[:, 1]).any():
         raise ValueError(f"{who}: image {i}: boxes must be finite with y2 >= y1 and x2 >= x1")
-    kept = (ids > 0) if (ids < 0).any() else np.ones(ids.shape, bool)
-    if not kept.any():
+    if _crowd_and_kept(ids)[1].size == 0:
         raise ValueError(f"{who}: image {i} has no usable ground truth (no row, or crowd and class-0 rows only)")
 
 
@@ -156,6 +161,33 @@ def _unpack(gt_boxes, gt_class_ids, gt_off, who: str = "rpn_targets"):
     return [(boxes[s:e], ids[s:e]) for s, e in zip(off[:-1], off[1:])]
 
 
+def _ground_truth(who: str, gt_boxes, gt_class_ids, gt_off, dev):
+    """→ (images, boxes_d, ids_d, off_d, batch). images: the checked host copies per image — None for packed DEVICE tensors bound
+    for the device, which are not read back. boxes_d float32 [M,4] / ids_d int32 [M] / off_d int32 [B+1]: the packed form on `dev`
+    — None on the cpu route."""
+    on_device = gt_off is not None and _on_gpu(gt_boxes) and _on_gpu(gt_class_ids) and _on_gpu(gt_off)
+    if on_device and dev.type != "cpu":
+        return None, gt_boxes.to(dev), gt_class_ids.to(dev), gt_off.to(dev), gt_off.numel() - 1
+    images = _unpack(gt_boxes, gt_class_ids, gt_off, who)
+    for i, (b, c) in enumerate(images):
+        _check_image(i, b, c, who)
+    if dev.type == "cpu":
+        return images, None, None, None, len(images)
+    off = np.concatenate([[0], np.cumsum([len(c) for _, c in images])]).astype(np.int32)
+    boxes_d = torch.from_numpy(np.concatenate([b for b, _ in images]).astype(np.float32)).to(dev)
+    ids_d = torch.from_numpy(np.concatenate([c for _, c in images]).astype(np.int32)).to(dev)
+    return images, boxes_d, ids_d, torch.from_numpy(off).to(dev), len(images)
+
+
+def _keys(keys, batch: int, n: int, dev, generator) -> torch.Tensor:
+    """int32 [batch,n] on `dev`: the caller's keys, or uniform ones drawn there from `generator`."""
+    if keys is None:
+        return torch.randint(0, 2 ** 31 - 1, (batch, n), dtype=torch.int32, device=dev, generator=generator)
+    if not isinstance(keys, torch.Tensor):
+        keys = torch.from_numpy(np.array(keys, np.int32))
+    return keys.to(dev, torch.int32).reshape(batch, n)
+
+
 def rpn_targets(anchors, gt_boxes, gt_class_ids, count: int = 128, std_dev=(0.1, 0.1, 0.2, 0.2), keys=None, generator=None,
                 device="cuda:0", gt_off=None):
     """data.rpn_samples for a batch → (rpn_match int32 [B,A,1], rpn_bbox float32 [B,count,4]), the shapes the reference's
@@ -171,22 +203,15 @@ def rpn_targets(anchors, gt_boxes, gt_class_ids, count: int = 128, std_dev=(0.1,
     if count < 1:
         raise ValueError(f"rpn_targets: count={count} must be >= 1")
     dev = torch.device(device)
-    on_device = gt_off is not None and _on_gpu(gt_boxes) and _on_gpu(gt_class_ids) and _on_gpu(gt_off)
     if not _on_gpu(anchors):
         _check_anchors(np.asarray(_host(anchors), np.float64))
-    images = None
-    if not on_device or dev.type == "cpu":
-        images = _unpack(gt_boxes, gt_class_ids, gt_off)
-        for i, (b, c) in enumerate(images):
-            _check_image(i, b, c)
-    batch = len(images) if images is not None else gt_off.numel() - 1
+    images, boxes_d, ids_d, off_d, batch = _ground_truth("rpn_targets", gt_boxes, gt_class_ids, gt_off, dev)
     n_anchors = anchors.shape[0]
+    keys = _keys(keys, batch, n_anchors, dev, generator)
 
     if dev.type == "cpu":
         a = np.asarray(_host(anchors), np.float64)
-        if keys is None:
-            keys = torch.randint(0, 2 ** 31 - 1, (batch, n_anchors), dtype=torch.int32, generator=generator)
-        keys = np.asarray(_host(keys)).reshape(batch, n_anchors)
+        keys = keys.numpy()
         rpn_match, rpn_bbox = np.zeros((batch, n_anchors, 1), np.int32), np.zeros((batch, count, 4), np.float32)
         for i, (b, c) in enumerate(images):
             match, arg, _, _, _ = match_numpy(a, b, c)
@@ -197,20 +222,8 @@ def rpn_targets(anchors, gt_boxes, gt_class_ids, count: int = 128, std_dev=(0.1,
 
     from . import ops
     anchors_d = (anchors if isinstance(anchors, torch.Tensor) else torch.from_numpy(np.array(anchors, np.float64))).to(dev, torch.float64)
-    if on_device:
-        boxes_d, ids_d, off_d = gt_boxes.to(dev), gt_class_ids.to(dev), gt_off.to(dev)
-    else:
-        off = np.concatenate([[0], np.cumsum([len(c) for _, c in images])]).astype(np.int32)
-        boxes_d = torch.from_numpy(np.concatenate([b for b, _ in images]).astype(np.float32)).to(dev)
-        ids_d = torch.from_numpy(np.concatenate([c for _, c in images]).astype(np.int32)).to(dev)
-        off_d = torch.from_numpy(off).to(dev)
-    if keys is None:
-        keys_d = torch.randint(0, 2 ** 31 - 1, (batch, n_anchors), dtype=torch.int32, device=dev, generator=generator)
-    else:
-        keys_d = (keys if isinstance(keys, torch.Tensor) else torch.from_numpy(np.array(keys, np.int32))).to(dev, torch.int32)
-        keys_d = keys_d.reshape(batch, n_anchors)
     match, arg, _, _, _ = ops.anchor_match(anchors_d, boxes_d, ids_d, off_d, NEG_IOU, POS_IOU, CROWD_IOU)
-    ops.sample_by_key(match, keys_d, count, out=match)
+    ops.sample_by_key(match, keys, count, out=match)
     rpn_bbox, _ = ops.rpn_deltas(anchors_d, boxes_d, off_d, match, arg, count, std_dev)
     return match.unsqueeze(-1), rpn_bbox
 
@@ -225,8 +238,7 @@ def roi_match_numpy(rois, gt_boxes, gt_class_ids, pos_iou=ROI_POS_IOU, crowd_iou
     boxes = np.asarray(gt_boxes, np.float32).reshape(-1, 4)
     ids = np.asarray(gt_class_ids, np.int32).reshape(-1)
     n = r32.shape[0]
-    crowd = np.where(ids < 0)[0]
-    kept = np.where(ids > 0)[0] if crowd.size else np.arange(ids.size)
+    crowd, kept = _crowd_and_kept(ids)
     cls = np.full(n, 2, np.int32)
     if kept.size == 0:
         return cls, np.full(n, -1, np.int32), np.zeros(n, np.float32), 1
@@ -391,19 +403,11 @@ def detection_targets(rois, gt_boxes, gt_class_ids, gt_masks, count: int = 100, 
     batch, n = int(rois.shape[0]), int(rois.shape[1])
     if n > MAX_ROIS_PER_IMAGE:
         raise ValueError(f"{who}: N={n} rois per image; at most {MAX_ROIS_PER_IMAGE}")
-    packed = gt_off is not None
-    on_device = packed and _on_gpu(gt_boxes) and _on_gpu(gt_class_ids) and _on_gpu(gt_off)
-    images = None
-    if not on_device or dev.type == "cpu":
-        images = _unpack(gt_boxes, gt_class_ids, gt_off, who)
-        if len(images) != batch:
-            raise ValueError(f"{who}: rois of {batch} images, ground truth of {len(images)}")
-        for i, (b, c) in enumerate(images):
-            _check_image(i, b, c, who)
-    elif gt_off.numel() != batch + 1:
-        raise ValueError(f"{who}: rois of {batch} images, gt_off of {gt_off.numel() - 1}")
+    images, boxes_d, ids_d, off_d, gt_batch = _ground_truth(who, gt_boxes, gt_class_ids, gt_off, dev)
+    if gt_batch != batch:
+        raise ValueError(f"{who}: rois of {batch} images, {'gt_off' if images is None else 'ground truth'} of {gt_batch}")
     # masks: [M,H,W] in one piece, rows as the boxes'
-    if packed:
+    if gt_off is not None:
         masks = gt_masks
         rows = int(gt_boxes.shape[0])
         if len(masks.shape) != 3 or int(masks.shape[0]) != rows:
@@ -426,11 +430,10 @@ def detection_targets(rois, gt_boxes, gt_class_ids, gt_masks, count: int = 100, 
         for i in range(batch):
             _check_rois(who, i, r_host[i])
 
+    keys = _keys(keys, batch, n, dev, generator)
     if dev.type == "cpu":
         r_host, m_host = np.asarray(_host(rois), np.float32), _host(masks)
-        if keys is None:
-            keys = torch.randint(0, 2 ** 31 - 1, (batch, n), dtype=torch.int32, generator=generator)
-        keys = np.asarray(_host(keys)).reshape(batch, n)
+        keys = keys.numpy()
         out = DetectionTargets(np.zeros((batch, count, 4), np.float32), np.zeros((batch, count), np.int32),
                                np.zeros((batch, count, 4), np.float32), np.zeros((batch, count, mh, mw), np.float32),
                                np.full((batch, count), -1, np.int32), np.full((batch, count), -1, np.int32),
@@ -456,20 +459,8 @@ def detection_targets(rois, gt_boxes, gt_class_ids, gt_masks, count: int = 100, 
             x = torch.from_numpy(x if x.flags.writeable else x.copy())
         return x.to(dev, dtype)
 
-    rois_d = as_dev(rois, torch.float32)
-    if on_device:
-        boxes_d, ids_d, off_d = gt_boxes.to(dev), gt_class_ids.to(dev), gt_off.to(dev)
-    else:
-        off = np.concatenate([[0], np.cumsum([len(c) for _, c in images])]).astype(np.int32)
-        boxes_d = torch.from_numpy(np.concatenate([b for b, _ in images]).astype(np.float32)).to(dev)
-        ids_d = torch.from_numpy(np.concatenate([c for _, c in images]).astype(np.int32)).to(dev)
-        off_d = torch.from_numpy(off).to(dev)
-    masks_d = as_dev(masks)
-    if keys is None:
-        keys_d = torch.randint(0, 2 ** 31 - 1, (batch, n), dtype=torch.int32, device=dev, generator=generator)
-    else:
-        keys_d = as_dev(keys, torch.int32).reshape(batch, n)
+    rois_d, masks_d = as_dev(rois, torch.float32), as_dev(masks)
     rois_out, class_ids, deltas, roi_index, gt_index, num_pos, num_neg, status = ops.detection_targets(
-        rois_d, boxes_d, ids_d, off_d, keys_d, count, positive_ratio, std_dev, pos_iou, CROWD_IOU)
+        rois_d, boxes_d, ids_d, off_d, keys, count, positive_ratio, std_dev, pos_iou, CROWD_IOU)
     target_mask = ops.mask_targets(masks_d, off_d, rois_out, gt_index, num_pos, (mh, mw))
     return DetectionTargets(rois_out, class_ids, deltas, target_mask, roi_index, gt_index, num_pos, num_neg, status)

@@ -95,3 +95,25 @@ def ulp_distance(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     ia, ib = a.astype(np.float32).view(np.int32).astype(np.int64), b.astype(np.float32).view(np.int32).astype(np.int64)
     ia, ib = np.where(ia < 0, -(ia & 0x7fffffff), ia), np.where(ib < 0, -(ib & 0x7fffffff), ib)
     return np.abs(ia - ib)
+
+
+@functools.lru_cache(maxsize=None)
+def shared_geometry():
+    """One geometry for BOTH matchers (csrc/target_match.hpp is their common rule): 100 boxes, every coordinate a multiple of 1/8
+    in [0, 64], so the float64 anchors narrow exactly to the float32 RoIs; 2 images. Image 0: five rows — an ordinary one, a crowd,
+    an id-0 row (dropped beside the crowd), another ordinary one and a duplicate of row 0 (an exact IoU tie for every box: row 0
+    wins). Image 1: one row. Box 0 overlaps no row, boxes 1-6 are the rows themselves (IoU 1), box 7 overlaps rows 0 and 3 alike (IoU
+    0.2 with each), the others are rows moved and resized by up to 2.5, or anywhere. → dict(boxes float64 [100,4], gt float32 [6,4], ids, off, keys)."""
+    gt = np.array([[8, 8, 24, 24], [32, 32, 56, 56], [8, 40, 24, 56], [40, 8, 56, 24], [8, 8, 24, 24], [16, 16, 48, 48]], np.float32)
+    ids = np.array([3, -1, 0, 5, 7, 2], np.int32)
+    rng = np.random.default_rng(20261019)
+    near = gt[rng.integers(0, 6, 62)] + rng.integers(-20, 21, (62, 4)) / 8.0
+    y1, x1 = rng.integers(0, 8 * 48, 30) / 8.0, rng.integers(0, 8 * 48, 30) / 8.0
+    far = np.stack([y1, x1, y1 + rng.integers(8, 8 * 16, 30) / 8.0, x1 + rng.integers(8, 8 * 16, 30) / 8.0], 1)
+    boxes = np.concatenate([[[60, 60, 64, 64]], gt, [[16, 8, 48, 24]], near, far]).astype(np.float64)
+    assert boxes.shape == (100, 4) and (boxes >= 0).all() and (boxes <= 64).all() and np.array_equal(boxes * 8, np.round(boxes * 8))
+    assert (boxes[:, 2] > boxes[:, 0]).all() and (boxes[:, 3] > boxes[:, 1]).all()
+    out = dict(boxes=boxes, gt=gt, ids=ids, off=np.array([0, 5, 6], np.int32), keys=np.stack([hash_keys(11, b, 100, 0) for b in range(2)]))
+    for v in out.values():
+        v.setflags(write=False)
+    return out

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from targets_cases import case, images, names, ulp_distance
+from targets_cases import case, images, names, shared_geometry, ulp_distance
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -154,6 +154,26 @@ def test_rpn_targets_refuses_an_image_without_usable_ground_truth_and_draws_keys
 
 def bits_t(t):
     return t.view(torch.int32)
+
+
+def test_anchor_match_and_detection_targets_match_one_geometry_alike():
+    """The two kernels share their matching rule (csrc/target_match.hpp): on the same 100 boxes (a partial wave) the RoIs
+    detection_targets keeps as positives — pos_iou 0.7, positive_ratio 1 and count 100: every one that reaches the threshold, no
+    negatives — are the anchors whose iou_max reaches it, each matched to the same row. test_targets_host.py holds the numpy
+    routes to the same on this input."""
+    from maskrcnn_amd import ops
+    g = shared_geometry()
+    boxes, ids, off = dev(g["gt"]), dev(g["ids"]), dev(g["off"])
+    _, arg, iou, _, status = ops.anchor_match(dev(g["boxes"]), boxes, ids, off)
+    rois = dev(np.stack([g["boxes"]] * 2), np.float32)
+    _, _, _, roi_index, gt_index, num_pos, num_neg, roi_status = ops.detection_targets(rois, boxes, ids, off, dev(g["keys"]), 100, 1.0,
+                                                                                         pos_iou=0.7)
+    arg, iou, roi_index, gt_index = arg.cpu().numpy(), iou.cpu().numpy(), roi_index.cpu().numpy(), gt_index.cpu().numpy()
+    assert status.tolist() == roi_status.tolist() == [0, 0] and num_neg.tolist() == [0, 0]
+    for i, p in enumerate(num_pos.tolist()):
+        want = np.where((arg[i] >= 0) & (iou[i] >= np.float32(0.7)))[0]
+        assert len(want) >= 1 and sorted(roi_index[i, :p].tolist()) == want.tolist(), i
+        assert np.array_equal(gt_index[i, :p], arg[i][roi_index[i, :p]]), i
 
 
 @pytest.mark.parametrize("name", ["pyr128_b3_count8_mod4_keys", "full_b2"])

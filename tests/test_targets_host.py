@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import ROOT, load_golden
-from targets_cases import case, cases, images, pyramid_config, usable
+from targets_cases import case, cases, images, pyramid_config, shared_geometry, usable
 
 ENTRY_POINTS = ("mrcnn_anchor_match", "mrcnn_sample_by_key", "mrcnn_rpn_deltas", "mrcnn_anchor_match_workspace_bytes",
                 "mrcnn_sample_by_key_workspace_bytes", "mrcnn_rpn_deltas_workspace_bytes")
@@ -82,6 +82,32 @@ def test_numpy_route_equals_every_array_of_the_fixture():
                 assert np.array_equal(m.numpy()[..., 0], c["match"]) and np.array_equal(b.numpy(), c["bbox"]), c["name"]
 
 
+def test_both_matchers_agree_on_one_geometry():
+    """match_numpy and roi_match_numpy restate one rule: on the same boxes the RoIs that reach pos_iou are the anchors whose
+    iou_max does, matched to the same row. (test_gpu_targets.py asserts the same of the two kernels on this input.)"""
+    from maskrcnn_amd import targets
+    g = shared_geometry()
+    assert np.array_equal(g["boxes"].astype(np.float32).astype(np.float64), g["boxes"])
+    positives = []
+    for i, (s, e) in enumerate(zip(g["off"][:-1], g["off"][1:])):
+        boxes, ids = g["gt"][s:e], g["ids"][s:e]
+        _, arg, iou, _, status = targets.match_numpy(g["boxes"], boxes, ids)
+        cls, gt_index, roi_iou, roi_status = targets.roi_match_numpy(g["boxes"].astype(np.float32), boxes, ids, pos_iou=0.7)
+        want = np.where((arg >= 0) & (iou >= np.float32(0.7)))[0]
+        idx, p, q = targets.roi_sample_numpy(cls, g["keys"][i], 100, 1.0)
+        assert status == roi_status == 0 and q == 0 and (idx[p:] == -1).all()
+        assert sorted(idx[:p].tolist()) == want.tolist() and np.array_equal(gt_index[idx[:p]], arg[idx[:p]])
+        assert np.array_equal(roi_iou.view(np.int32), iou.view(np.int32)) and np.array_equal(gt_index, arg)
+        assert iou[0] == 0 and cls[0] == 1                                    # box 0 touches no row
+        positives.append(len(want))
+    assert positives[0] >= 1 and positives[1] >= 1
+    # image 0: the rows themselves — the crowd and the id-0 row are never matched, the duplicate loses to row 0
+    arg = targets.match_numpy(g["boxes"], g["gt"][:5], g["ids"][:5])[1]
+    assert arg[1] == 0 and arg[5] == 0 and arg[4] == 3 and not np.isin(arg, [1, 2, 4]).any()
+    ov = targets._overlaps(g["boxes"][7:8].astype(np.float32), g["gt"][[0, 3]])
+    assert ov[0, 0] == ov[0, 1] == np.float32(0.2) and arg[7] == 0            # an exact tie between two rows: the first wins
+
+
 def test_front_end_refuses_bad_ground_truth_on_the_host():
     from maskrcnn_amd import targets
     c = case("pyr64_all_crowd")
@@ -147,12 +173,15 @@ def test_source_is_built_without_fma_contraction_or_fast_math():
     spec = importlib.util.spec_from_file_location("mrcnn_build", f"{ROOT}/maskrcnn_amd/build.py")
     build = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build)
-    assert "-ffp-contract=off" in build.SOURCES["targets.hip"]
-    flags = build.COMMON + build.SOURCES["targets.hip"]
-    assert "-fno-fast-math" in flags
-    # nothing that lets the compiler approximate the IoU's division
-    assert not [f for f in flags if re.search(r"fast-math|unsafe-math|reciprocal|approx|no-hip-fp32-correctly-rounded|finite-math", f)
-                and f != "-fno-fast-math"]
+    for src in ("targets.hip", "detection_targets.hip"):       # both include the shared matching rule (csrc/target_match.hpp)
+        assert "-ffp-contract=off" in build.SOURCES[src], src
+        flags = build.COMMON + build.SOURCES[src]
+        assert "-fno-fast-math" in flags, src
+        # nothing that lets the compiler approximate the IoU's division
+        assert not [f for f in flags if re.search(r"fast-math|unsafe-math|reciprocal|approx|no-hip-fp32-correctly-rounded|finite-math", f)
+                    and f != "-fno-fast-math"], src
+        assert '#include "target_match.hpp"' in open(f"{ROOT}/maskrcnn_amd/csrc/{src}").read(), src
+    assert "built with FP contraction off" in open(f"{ROOT}/maskrcnn_amd/csrc/target_match.hpp").read()
 
 
 def test_entry_points_refuse_the_limits_before_touching_a_pointer():
