@@ -10,12 +10,14 @@
 //   2 rle_iou_kernel   a wave per (detection, ground truth) pair: the detection's on runs are spread over the lanes; a run
 //                      [s, e) overlaps the ground truth in F(e) - F(s) pixels, F(x) = on pixels of the ground truth before
 //                      position x, found by binary search in its end positions. union = area_d + area_g - intersection.
+// The wave scan and the wave reduction are csrc/workgroup.hpp's.
 // The reference's bounding-box pre-test (rleIou calls bbIou on rleToBbox first and keeps its 0) changes no bit: boxes that
 // do not overlap hold masks that do not overlap, and an empty intersection is (double)0 / (double)1 = +0.0 too.
 //
 // Built with -ffp-contract=off: bbIou's da+ga-i with i=w*h must stay separately rounded (the reference codec is plain -O2
 // x86-64 C: no FMA).
 #include "common.hpp"
+#include "workgroup.hpp"
 
 #include <climits>
 
@@ -70,15 +72,6 @@ struct Table {
     uint32_t* area;     // [n] workspace
 };
 
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < mrcnn::kWave; d <<= 1) {
-        const uint32_t up = __shfl_up(v, d);
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void rle_ends_kernel(const Table a, const Table b) {
     const int lane = threadIdx.x & (mrcnn::kWave - 1);
     int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / mrcnn::kWave;
@@ -95,8 +88,8 @@ __global__ __launch_bounds__(kBlock) void rle_ends_kernel(const Table a, const T
     for (int base = 0; base < nr; base += mrcnn::kWave) {
         const int j = base + lane;
         const uint32_t c = j < nr ? t.counts[row + j] : 0u;
-        const uint32_t e = end + wave_inclusive_scan(c, lane);
-        const uint32_t o = on + wave_inclusive_scan((j & 1) ? c : 0u, lane);
+        const uint32_t e = end + mrcnn::wave_inclusive_scan(c, lane);
+        const uint32_t o = on + mrcnn::wave_inclusive_scan((j & 1) ? c : 0u, lane);
         if (j < nr) {
             t.ends[row + j] = e;
             t.on_upto[row + j] = o;
@@ -148,8 +141,7 @@ __global__ __launch_bounds__(kBlock) void rle_iou_kernel(const IouParams p) {
         const uint32_t s = de[j - 1], t = de[j];
         if (t > s) inter += on_before(ge, go, ng, t) - on_before(ge, go, ng, s);
     }
-#pragma unroll
-    for (int d = mrcnn::kWave / 2; d > 0; d >>= 1) inter += __shfl_xor(inter, d);
+    inter = mrcnn::wave_reduce(inter, [](uint32_t a, uint32_t b) { return a + b; });
     if (lane == 0) {
         const uint32_t area_d = p.dt.area[pr.di], area_g = p.gt.area[pr.gi];
         const bool crowd = p.iscrowd != nullptr && p.iscrowd[pr.gi] != 0;

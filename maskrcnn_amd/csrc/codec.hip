@@ -10,13 +10,14 @@
 //   even m from 2, cnts[0] alone — so two wave scans per step, one per parity, each with a carry across the steps.
 //   The string is swept twice: once to validate and count (a row with more runs than capacity is never written), once to write.
 // mrcnn_rle_area_bbox, a wave per row: one scan of the counts gives cc; t, y, x and the min / max follow per lane.
-// mrcnn_rle_to_string: pass 1 (a wave per row) sums the characters per row, one workgroup scans them into str_off, pass 2 (a wave
-//   per row) scans the characters per run within the row and writes them.
+// mrcnn_rle_to_string: pass 1 (a wave per row) sums the characters per row, one workgroup scans them into str_off
+//   (chunked_exclusive_scan, workgroup.hpp), pass 2 (a wave per row) scans the characters per run within the row and writes them.
 // mrcnn_rle_decode_u8: the encoder's transposition in reverse. A wave per row scans the counts to end positions (clipped at
 //   H*W). Then a lane owns FOUR adjacent columns of a 32-row segment: one binary search per column finds the run its first pixel
 //   lies in, then it walks down the rows and stores one 32-bit word per row — the lanes of a wave write 256 contiguous bytes of
 //   each row, so the stores are contiguous along x without a trip through LDS.
 #include "common.hpp"
+#include "workgroup.hpp"
 
 #include <climits>
 
@@ -37,22 +38,9 @@ enum : int32_t {
     kBadByte = 1, kLongToken = 2, kOpenToken = 4, kBadSize = 8, kEmptyRun = 16, kPixelSum = 32, kBadOffsets = 64,
 };
 
-template <class T>
-__device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
-#pragma unroll
-    for (int d = 1; d < mrcnn::kWave; d <<= 1) {
-        const T up = __shfl_up(v, d);
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-template <class T, class Op>
-__device__ __forceinline__ T wave_reduce(T v, Op op) {
-#pragma unroll
-    for (int d = mrcnn::kWave / 2; d > 0; d >>= 1) v = op(v, __shfl_xor(v, d));
-    return v;
-}
+using mrcnn::rle_put_value;
+using mrcnn::wave_inclusive_scan;
+using mrcnn::wave_reduce;
 
 __device__ __forceinline__ bool row_ok(int nr, int capacity) { return nr >= 0 && nr <= capacity; }
 
@@ -240,21 +228,6 @@ struct ToStringParams {
     int64_t row_stride;   // 0: packed at str_off; > 0: row i at bytes + i*row_stride (rows longer than the stride are not written)
 };
 
-// rleToString's group loop for one value (a long there); returns the characters, written when dst is given
-__device__ __forceinline__ int put_value(uint8_t* dst, long long x) {
-    int k = 0;
-    bool more;
-    do {
-        int c = (int)(x & 31);
-        x >>= 5;   // arithmetic
-        more = (c & 16) ? x != -1 : x != 0;
-        if (more) c |= 32;
-        if (dst) dst[k] = (uint8_t)(c + 48);
-        ++k;
-    } while (more);
-    return k;
-}
-
 __device__ __forceinline__ long long string_value(const uint32_t* row, int j) {
     long long x = (long long)row[j];
     if (j > 2) x -= (long long)row[j - 2];
@@ -269,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void rle_string_bytes_kernel(const ToString
     long long total = 0;
     if (row_ok(nr, p.capacity)) {
         const uint32_t* row = p.counts + (int64_t)i * p.capacity;
-        for (int j = lane; j < nr; j += mrcnn::kWave) total += put_value(nullptr, string_value(row, j));
+        for (int j = lane; j < nr; j += mrcnn::kWave) total += rle_put_value<false>(nullptr, string_value(row, j));
         total = wave_reduce(total, [](long long a, long long b) { return a + b; });
     }
     if (lane == 0) p.row_bytes[i] = total;
@@ -277,28 +250,10 @@ __global__ __launch_bounds__(kBlock) void rle_string_bytes_kernel(const ToString
 
 // exclusive scan of row_bytes into str_off[0..n], one workgroup
 __global__ __launch_bounds__(kScanThreads) void rle_string_scan_kernel(const ToStringParams p) {
-    __shared__ long long lds[2 * kScanThreads];
-    const int t = threadIdx.x;
-    const int64_t count = p.n, chunk = (count + kScanThreads - 1) / kScanThreads;
-    const int64_t lo = min((int64_t)t * chunk, count), hi = min(lo + chunk, count);
-    long long acc = 0;
-    for (int64_t i = lo; i < hi; ++i) acc += p.row_bytes[i];
-    int cur = 0;
-    lds[t] = acc;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        long long v = lds[cur * kScanThreads + t];
-        if (t >= d) v += lds[cur * kScanThreads + t - d];
-        lds[(cur ^ 1) * kScanThreads + t] = v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    long long r = t > 0 ? lds[cur * kScanThreads + t - 1] : 0;
-    for (int64_t i = lo; i < hi; ++i) {
-        p.str_off[i] = r;
-        r += p.row_bytes[i];
-    }
-    if (t == kScanThreads - 1) p.str_off[count] = lds[cur * kScanThreads + t];
+    __shared__ int64_t lds[2 * kScanThreads];
+    const int64_t total = mrcnn::chunked_exclusive_scan<kScanThreads>(p.row_bytes, p.str_off, (int64_t)p.n, (int64_t)0, lds,
+                                                                      [](int64_t a, int64_t b) { return a + b; });
+    if (threadIdx.x == kScanThreads - 1) p.str_off[p.n] = total;   // the last thread: its chunk is the short one
 }
 
 __global__ __launch_bounds__(kBlock) void rle_string_write_kernel(const ToStringParams p) {
@@ -319,9 +274,9 @@ __global__ __launch_bounds__(kBlock) void rle_string_write_kernel(const ToString
     for (int base = 0; base < nr; base += mrcnn::kWave) {
         const int j = base + lane;
         const long long x = j < nr ? string_value(row, j) : 0;
-        const int k = j < nr ? put_value(nullptr, x) : 0;
+        const int k = j < nr ? rle_put_value<false>(nullptr, x) : 0;
         const int incl = wave_inclusive_scan(k, lane);
-        if (j < nr) put_value(p.bytes + at + (incl - k), x);   // ends at most at b1 <= bytes_capacity
+        if (j < nr) rle_put_value<true>(p.bytes + at + (incl - k), x);   // ends at most at b1 <= bytes_capacity
         at += __shfl(incl, mrcnn::kWave - 1);
     }
 }

@@ -12,7 +12,7 @@
 // argmax / crowd max, and forms ONE 64-bit sort key per RoI:
 //     class (0 positive, 1 negative, 2 neither) << 53 | key (31 bits) << 22 | roi index (12 bits) << 10 | matched row (10 bits)
 // The RoI index is unique, so the row bits never decide an order: they ride along and spare a second table. One LDS bitonic sort
-// of the next power of two >= N keys (32 KB at 4096; the padding is all ones and sorts last) yields the positives and then the
+// (workgroup.hpp) of the next power of two >= N keys (32 KB at 4096; the padding is all ones and sorts last) yields the positives and then the
 // negatives, each in (key, roi index) order; the class counts P and Q come from LDS atomics. Slot s < num_pos reads sorted entry
 // s, slot num_pos <= s < num_pos + num_neg reads entry P + (s - num_pos), every other slot is written as zeros / -1: the kernel
 // writes every byte of its outputs, so there is no memset. neg_limit is evaluated on the device in fp64 (the file is built with
@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "crop_math.hpp"
 #include "target_match.hpp"
+#include "workgroup.hpp"
 
 namespace {
 
@@ -120,22 +121,7 @@ __global__ __launch_bounds__(kBlock) void detection_targets_kernel(TargetParams 
         }
         if (my_pos) atomicAdd(&s_count[0], my_pos);
         if (my_neg) atomicAdd(&s_count[1], my_neg);
-        __syncthreads();
-        // bitonic sort, ascending: sort_n / 2 compare-exchanges per step
-        for (int k = 2; k <= sort_n; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < sort_n / 2; t += kBlock) {
-                    const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                    const unsigned long long a = s_key[lo], c = s_key[hi];
-                    const bool ascending = (lo & k) == 0;
-                    if ((a > c) == ascending) {
-                        s_key[lo] = c;
-                        s_key[hi] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        mrcnn::bitonic_sort<kBlock, false>(s_key, sort_n);   // its barriers publish s_count too (one barrier when sort_n == 1)
         n_pos = min(s_count[0], p.n);
         n_neg = min(s_count[1], p.n - n_pos);
     }

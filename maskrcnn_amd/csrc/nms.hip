@@ -6,19 +6,20 @@
 // copies it to the host with a blocking hipMemcpy and scans it there):
 //   * one workgroup per segment (image, or image x class set), everything LDS-resident, no global
 //     scratch, no host round trip, graph-capturable;
-//   * score order by an in-LDS bitonic sort of 64-bit keys (~score | index) — ties resolve to the
+//   * score order by an in-LDS bitonic sort (workgroup.hpp) of 64-bit keys (~score | index) — ties resolve to the
 //     lower input index, NaN scores first (ATen's convention);
 //   * suppression in 64-box chunks of the sorted order, wave64-shaped:
 //       A. every wave ballots one row of the chunk's 64x64 IoU>=thr matrix per step (lane = column),
 //       B. wave 0 resolves the chunk serially over the *alive* boxes only (readlane + scalar ops),
 //       C. all threads test their own (register-resident) later boxes against the chunk's survivors,
 //          broadcasting survivor boxes from LDS;
-//   * ascending-index compaction with wave ballots + a workgroup prefix sum.
+//   * ascending-index compaction with a workgroup prefix sum (block_inclusive_scan, workgroup.hpp).
 // IoU arithmetic is the reference's, op for op, compiled with FP contraction off: separately rounded
 // (x2-x1+1)*(y2-y1+1), std::max/min NaN semantics via ternaries, correctly rounded IEEE division.
 #pragma clang fp contract(off)
 
 #include "common.hpp"
+#include "workgroup.hpp"
 
 namespace {
 
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(T) void nms_kernel(const float* __restrict__ dets, 
     int* bcl = reinterpret_cast<int*>(bar + CAP);         // [CAP]
     u64* colmask = reinterpret_cast<u64*>(bcl + CAP);     // [64]
     u64* misc = colmask + 64;                             // [0] = chunk survivors
-    int* wsum = reinterpret_cast<int*>(misc + 2);         // [NW + 1]
+    int* wsum = reinterpret_cast<int*>(misc + 2);         // [NW] block_inclusive_scan's scratch
     unsigned char* sup = reinterpret_cast<unsigned char*>(wsum + 32);  // [CAP] sorted order
     unsigned char* keepf = sup + CAP;                                  // [CAP] input order
 
@@ -101,23 +102,9 @@ __global__ __launch_bounds__(T) void nms_kernel(const float* __restrict__ dets, 
         keepf[i] = 0;
     }
     for (int i = np2 + tid; i < CAP; i += T) keepf[i] = 0;
-    __syncthreads();
 
-    // ---- 2. bitonic sort (ascending key == descending score, stable by index) -------------------
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (np2 >> 1); t += T) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const u64 a = keys[i], b = keys[i + j];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) {
-                    keys[i] = b;
-                    keys[i + j] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // ---- 2. bitonic sort (ascending key == descending score, stable by index); its barriers publish keepf too ----
+    mrcnn::bitonic_sort<T, false>(keys, np2);
 
     // ---- 3. gather boxes into sorted order; areas as nms_cpu.cpp:26 -----------------------------
     Box mine[PER];
@@ -224,26 +211,8 @@ __global__ __launch_bounds__(T) void nms_kernel(const float* __restrict__ dets, 
     int local = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) local += keepf[tid * PER + k];
-    int incl = local;  // wave inclusive scan
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int w = 0; w < NW; ++w) {
-            const int v = wsum[w];
-            wsum[w] = acc;
-            acc += v;
-        }
-        wsum[NW] = acc;
-    }
-    __syncthreads();
-    const int total = wsum[NW];
-    int pos = wsum[wave] + incl - local;
+    int total;
+    int pos = mrcnn::block_inclusive_scan<T>(local, wsum, total) - local;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int i = tid * PER + k;
@@ -297,21 +266,7 @@ __global__ __launch_bounds__(T) void nms_sort_kernel(const float* __restrict__ d
     while (np2 < n) np2 <<= 1;
     for (int i = tid; i < np2; i += T)
         keys[i] = (i < n) ? make_key(d[i * row_stride + 4 * col_stride], static_cast<u32>(i)) : ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (np2 >> 1); t += T) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const u64 a = keys[i], b = keys[i + j];
-                const bool up = (i & k) == 0;
-                if ((a > b) == up) {
-                    keys[i] = b;
-                    keys[i + j] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    mrcnn::bitonic_sort<T, false>(keys, np2);
     const int64_t base = static_cast<int64_t>(seg) * ws.np;
     for (int p = tid; p < ws.np; p += T) {
         float4 b = make_float4(0.f, 0.f, 0.f, 0.f);

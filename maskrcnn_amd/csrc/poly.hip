@@ -1,6 +1,7 @@
 // COCO polygon ground truth to run lengths on the GPU (gfx950): rleFrPoly (and with it rleFrBbox) and rleMerge of
 // cocoapi/common/maskApi.c:162-202, :49-70 — what COCO.annToRLE does per annotation in serial C — for every part and every
-// annotation of a data set in one call each. No host synchronisation, the same bits from run to run.
+// annotation of a data set in one call each. No host synchronisation, the same bits from run to run. The workgroup scans and
+// the bitonic sort are csrc/workgroup.hpp's.
 //
 // mrcnn_rle_from_poly_f64, one workgroup per polygon part:
 //   1 vertices -> the 5x grid ((int)(5*x + .5)), per-edge boundary-point counts max(|dX|, |dY|) + 1, scanned by the workgroup
@@ -27,6 +28,7 @@
 // Built with -ffp-contract=off: 5*x + .5 and ys + s*t + .5 are separately rounded in the reference (plain -O2 x86-64 C), and a
 // fused multiply-add moves boundary points across pixel centres (tests/golden/poly.npz flags cases on which it does).
 #include "common.hpp"
+#include "workgroup.hpp"
 
 #include <climits>
 
@@ -43,41 +45,7 @@ constexpr int kMaxVerts = 1 << 28;
 constexpr size_t kAlign = 256;
 size_t aligned(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
-// ------------------------------------------------------------------------------------------------ workgroup primitives
-template <class T>
-__device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
-#pragma unroll
-    for (int d = 1; d < mrcnn::kWave; d <<= 1) {
-        const T up = __shfl_up(v, d);
-        if (lane >= d) v += up;
-    }
-    return v;
-}
-
-// Inclusive scan of one value per thread over the workgroup; `total` is the sum (to every thread). red: LDS [kWaves].
-template <class T>
-__device__ __forceinline__ T block_inclusive_scan(T v, T* red, T& total) {
-    const int lane = threadIdx.x & (mrcnn::kWave - 1), wave = threadIdx.x / mrcnn::kWave;
-    v = wave_inclusive_scan(v, lane);
-    if (lane == mrcnn::kWave - 1) red[wave] = v;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < kWaves; ++i) {
-        const T r = red[i];
-        if (i < wave) before += r;
-        all += r;
-    }
-    __syncthreads();   // red may be reused
-    total = all;
-    return v + before;
-}
-
-__device__ __forceinline__ int block_sum(int v, int* red) {
-    int total;
-    block_inclusive_scan(v, red, total);
-    return total;
-}
+using mrcnn::wave_inclusive_scan;
 
 // ------------------------------------------------------------------------------------------------ rleFrPoly
 struct PolyParams {
@@ -193,8 +161,8 @@ __device__ int count_range(const Part& a, uint32_t lo, uint32_t hi, PolyShared& 
             in += key >= lo && key < hi;
         }
     }
-    in = block_sum(in, sh.red);
-    if (all) *all = block_sum(any, sh.red);
+    in = mrcnn::block_sum<kBlock>(in, sh.red);
+    if (all) *all = mrcnn::block_sum<kBlock>(any, sh.red);
     return in;
 }
 
@@ -219,23 +187,9 @@ __device__ int sort_range(const Part& a, uint32_t lo, uint32_t hi, int m, PolySh
     }
     int n2 = 1;
     while (n2 < m) n2 <<= 1;
-    __syncthreads();
-    for (int e = m + tid; e < n2; e += kBlock) sh.keys[e] = 0xffffffffu;
-    __syncthreads();
-    for (int kk = 2; kk <= n2; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (n2 >> 1); t += kBlock) {
-                const int low = t & (j - 1);
-                const int i1 = ((t - low) << 1) + low, i2 = i1 + j;
-                const uint32_t x = sh.keys[i1], y = sh.keys[i2];
-                if ((x > y) == ((i1 & kk) == 0)) {
-                    sh.keys[i1] = y;
-                    sh.keys[i2] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    __syncthreads();   // not for the padding (its slots are nobody's): the waves enter the sort together, measured 2 % faster with it
+    for (int e = m + tid; e < n2; e += kBlock) sh.keys[e] = 0xffffffffu;   // slots m.. : no key was emitted there
+    mrcnn::bitonic_sort<kBlock, false>(sh.keys, n2);
     // a thread owns `chunk` (<= 32) consecutive sorted keys; bit b of mask: key e0 + b ends an equal run of odd length
     const int chunk = (m + kBlock - 1) / kBlock;
     const int e0 = min(tid * chunk, m), e1 = min(e0 + chunk, m);
@@ -257,7 +211,7 @@ __device__ int sort_range(const Part& a, uint32_t lo, uint32_t hi, int m, PolySh
     sh.cnt[tid] = mine;
     sh.lastv[tid] = last;
     int total;
-    const int before = block_inclusive_scan(mine, sh.red, total) - mine;   // its barriers publish cnt / lastv too
+    const int before = mrcnn::block_inclusive_scan<kBlock>(mine, sh.red, total) - mine;   // its barriers publish cnt / lastv too
     const bool write = mode == kWrite || (mode == kWriteIfFits && nb + total + 1 <= capacity);
     if (write && mine) {
         uint32_t pv = prev;
@@ -374,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void rle_from_poly_kernel(const PolyParams 
             c = (dx > dy ? dx : dy) + 1;
         }
         long long total;
-        const long long incl = block_inclusive_scan(c, sh.redll, total);
+        const long long incl = mrcnn::block_inclusive_scan<kBlock>(c, sh.redll, total);
         if (j < a.k) eo[j] = (int)min(carry + incl - c, (long long)kMaxPartPoints + 1);
         carry = min(carry + total, (long long)kMaxPartPoints + 1);
     }
@@ -400,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void rle_from_poly_kernel(const PolyParams 
             }
         }
     }
-    const int all = block_sum(any, sh.red);   // its barriers publish sh.count and sh.keys
+    const int all = mrcnn::block_sum<kBlock>(any, sh.red);   // its barriers publish sh.count and sh.keys
     const int in_range = sh.count;
     __syncthreads();   // everyone has read sh.count before a sweep resets it
     uint32_t prev = 0;

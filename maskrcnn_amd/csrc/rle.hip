@@ -17,6 +17,7 @@
 // read once in full and twice more only where it has edges. A mask with more runs than `capacity` is left out of
 // passes 3 - 5 altogether: its counts / strings rows are never touched.
 #include "common.hpp"
+#include "workgroup.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -68,7 +69,6 @@ __device__ __forceinline__ int4 join(const int4 a, const int4 b) {   // a earlie
     }
     return r;
 }
-__device__ __forceinline__ int join(const int a, const int b) { return a + b; }
 
 struct RleParams {
     const uint8_t* masks;
@@ -200,54 +200,14 @@ __global__ __launch_bounds__(kBlock) void rle_count_kernel(const RleParams p) {
     }
 }
 
-// Exclusive scan of one mask's cells by one workgroup: every lane folds a contiguous chunk, the chunk sums are scanned
-// through LDS, and a second walk over the chunk writes the prefixes. Returns the total (to every lane).
-template <class T>
-__device__ T block_exclusive_scan(const T* in, T* out, int64_t count, T identity, T* lds /* [2][kScanThreads] */) {
-    const int t = threadIdx.x;
-    const int64_t chunk = (count + kScanThreads - 1) / kScanThreads;
-    const int64_t lo = min((int64_t)t * chunk, count), hi = min(lo + chunk, count);
-    T acc = identity;
-    for (int64_t i = lo; i < hi; ++i) acc = join(acc, in[i]);
-    int cur = 0;
-    lds[t] = acc;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        T v = lds[cur * kScanThreads + t];
-        if (t >= d) v = join(lds[cur * kScanThreads + t - d], v);
-        lds[(cur ^ 1) * kScanThreads + t] = v;
-        cur ^= 1;
-        __syncthreads();
-    }
-    T r = t > 0 ? lds[cur * kScanThreads + t - 1] : identity;
-    const T total = lds[cur * kScanThreads + kScanThreads - 1];
-    for (int64_t i = lo; i < hi; ++i) {
-        const T v = in[i];
-        out[i] = r;
-        r = join(r, v);
-    }
-    __syncthreads();   // the LDS buffers may be reused by the caller
-    return total;
-}
-
-template <class Op>
-__device__ int block_reduce(int v, int* lds /* [kScanThreads / kWave] */, Op op) {
-#pragma unroll
-    for (int d = mrcnn::kWave / 2; d > 0; d >>= 1) v = op(v, __shfl_xor(v, d));
-    if ((threadIdx.x & (mrcnn::kWave - 1)) == 0) lds[threadIdx.x / mrcnn::kWave] = v;
-    __syncthreads();
-    int r = lds[0];
-    for (int i = 1; i < kScanThreads / mrcnn::kWave; ++i) r = op(r, lds[i]);
-    __syncthreads();
-    return r;
-}
-
+// One workgroup scans one mask's cells (chunked_exclusive_scan, workgroup.hpp); the extents and the area are reduced beside it.
 __global__ __launch_bounds__(kScanThreads) void rle_scan_kernel(const RleParams p) {
     __shared__ int4 lds[2 * kScanThreads];
     __shared__ int red[kScanThreads / mrcnn::kWave];
     const int m = blockIdx.x;
     const int64_t base = (int64_t)m * p.plan.cells;
-    const int4 total = block_exclusive_scan(p.run + base, p.pre + base, p.plan.cells, make_int4(0, 0, 0, 0), lds);
+    const int4 total = mrcnn::chunked_exclusive_scan<kScanThreads>(p.run + base, p.pre + base, p.plan.cells, make_int4(0, 0, 0, 0),
+                                                                   lds, [](const int4 a, const int4 b) { return join(a, b); });
 
     const int t = threadIdx.x;
     const int64_t chunk = (p.plan.cells + kScanThreads - 1) / kScanThreads;
@@ -266,11 +226,11 @@ __global__ __launch_bounds__(kScanThreads) void rle_scan_kernel(const RleParams 
     }
     auto fmin = [](int a, int b) { return min(a, b); };
     auto fmax = [](int a, int b) { return max(a, b); };
-    area = block_reduce(area, red, [](int a, int b) { return a + b; });
-    xmin = block_reduce(xmin, red, fmin);
-    xmax = block_reduce(xmax, red, fmax);
-    ymin = block_reduce(ymin, red, fmin);
-    ymax = block_reduce(ymax, red, fmax);
+    area = mrcnn::block_reduce<kScanThreads>(area, red, [](int a, int b) { return a + b; });
+    xmin = mrcnn::block_reduce<kScanThreads>(xmin, red, fmin);
+    xmax = mrcnn::block_reduce<kScanThreads>(xmax, red, fmax);
+    ymin = mrcnn::block_reduce<kScanThreads>(ymin, red, fmin);
+    ymax = mrcnn::block_reduce<kScanThreads>(ymax, red, fmax);
     if (t == 0) {
         p.num_runs[m] = total.x + 1;
         p.areas[m] = area;
@@ -290,24 +250,9 @@ __global__ __launch_bounds__(kScanThreads) void rle_bytes_scan_kernel(const RleP
         return;
     }
     const int64_t base = (int64_t)m * p.plan.cells;
-    const int total = block_exclusive_scan(p.cbytes + base, p.boff + base, p.plan.cells, 0, lds);
+    const int total = mrcnn::chunked_exclusive_scan<kScanThreads>(p.cbytes + base, p.boff + base, p.plan.cells, 0, lds,
+                                                                  [](int a, int b) { return a + b; });
     if (threadIdx.x == 0) p.string_bytes[m] = total;
-}
-
-// rleToString's group loop for one value: up to 6 characters (|x| <= 2^28); returns how many.
-template <bool WRITE>
-__device__ __forceinline__ int put_value(uint8_t* dst, int x) {
-    int k = 0;
-    bool more;
-    do {
-        int c = x & 31;
-        x >>= 5;   // arithmetic
-        more = (c & 16) ? x != -1 : x != 0;
-        if (more) c |= 32;
-        if (WRITE) dst[k] = (uint8_t)(c + 48);
-        ++k;
-    } while (more);
-    return k;
 }
 
 template <bool WRITE>
@@ -346,10 +291,10 @@ __global__ __launch_bounds__(kBlock) void rle_emit_kernel(const RleParams p) {
         if (WRITE) {
             if (i < p.capacity) {   // always: num_runs <= capacity here
                 if (counts) counts[i] = (uint32_t)cnt;
-                if (str) b += put_value<true>(str + b, x);
+                if (str) b += mrcnn::rle_put_value<true>(str + b, x);   // up to 6 characters: |x| <= 2^28
             }
         } else {
-            b += put_value<false>(nullptr, x);
+            b += mrcnn::rle_put_value<false>(nullptr, x);
         }
         a3 = a2; a2 = a1; a1 = pos;
         ++i;

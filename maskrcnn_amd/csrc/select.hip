@@ -5,9 +5,10 @@
 //   detection_select   mrn_refine's tail: keep ∩ per-class NMS keep, top detection_max_instances by score, gathers
 //                      (model.py:1475-1487), plus the normalised boxes the mask head pools (model.py:1188)
 // All three are latency-bound integer/compare work on tiny outputs (top-k: two chip-wide passes over the scores,
-// the other two one workgroup per image). Ordering is total and
+// the other two one workgroup per image; the LDS bitonic sort is workgroup.hpp's). Ordering is total and
 // deterministic: descending score, ties by ascending index (the reference's ATen sort leaves ties unspecified).
 #include "common.hpp"
+#include "workgroup.hpp"
 
 namespace {
 
@@ -24,28 +25,6 @@ __device__ __forceinline__ uint32_t order_key(float f) {
     uint32_t u = __float_as_uint(f);
     if (f != f) u = 0x7FC00000u;  // any NaN → +qNaN (largest)
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone float → uint
-}
-
-// Descending bitonic sort of n (a power of two) keys in LDS by all threads of the workgroup.
-template <typename T>
-__device__ __forceinline__ void bitonic_sort_desc(T* keys, int n, int tid, int nthreads) {
-    for (int k = 2; k <= n; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int i = tid; i < n; i += nthreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const T a = keys[i], b = keys[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? a < b : a > b) {
-                        keys[i] = b;
-                        keys[l] = a;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
 }
 
 // Descending sort of one 64-bit key per thread across a 1024-thread workgroup: thread t ends up with the t-th
@@ -197,13 +176,14 @@ __device__ __forceinline__ void radix_select(TopkShared& sh, int tid, uint32_t w
     need_eq = sh.remaining;
 }
 
-// Sort the `count` (>= k) composites in sh.keys (descending key, ascending index) and write the first k.
+// Sort the `count` (>= k) composites in sh.keys (descending key, ascending index) and write the first k. The composites may
+// have been written by any thread right before the call: the sort's first barrier publishes them.
 __device__ __forceinline__ void emit_topk(TopkShared& sh, int tid, int count, int k, const float* __restrict__ s,
                                           float* __restrict__ top, int64_t* __restrict__ order) {
     int cp = 1;
     while (cp < count) cp <<= 1;
     for (int i = count + tid; i < cp; i += TOPK_THREADS) sh.keys[i] = 0;  // padding sorts last
-    bitonic_sort_desc(sh.keys, cp, tid, TOPK_THREADS);
+    mrcnn::bitonic_sort<TOPK_THREADS, true>(sh.keys, cp);
     for (int i = tid; i < k; i += TOPK_THREADS) {
         const uint32_t idx = 0xFFFFFFFFu - static_cast<uint32_t>(sh.keys[i]);
         top[i] = s[idx];
@@ -273,7 +253,6 @@ __device__ __forceinline__ void exact_topk_row(TopkShared& sh, int tid, const fl
             }
         }
     }
-    __syncthreads();
     emit_topk(sh, tid, k, k, s, top, order);
 }
 
@@ -369,7 +348,6 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_finish_kernel(const float* 
     const uint64_t* cand = ws.cand + static_cast<int64_t>(b) * SORT_CAP;
     if (k > TOPK_THREADS) {  // more results than threads: sort all candidates in LDS
         for (uint32_t i = tid; i < ncand; i += TOPK_THREADS) sh.keys[i] = cand[i];
-        __syncthreads();
         emit_topk(sh, tid, static_cast<int>(ncand), k, s, top_b, order_b);
         return;
     }
@@ -406,7 +384,6 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_finish_kernel(const float* 
                 const uint32_t i = u * TOPK_THREADS + tid;
                 if (i < ncand) sh.keys[i] = c[u];
             }
-            __syncthreads();
             emit_topk(sh, tid, static_cast<int>(ncand), k, s, top_b, order_b);
             return;
         }
@@ -502,7 +479,7 @@ __global__ __launch_bounds__(1024) void detection_select_kernel(
         if (tid < d) cnt += emit(tid, v);
     } else {
         for (int i = tid; i < pp; i += 1024) sh.keys[i] = key_of(i);
-        bitonic_sort_desc(sh.keys, pp, tid, 1024);
+        mrcnn::bitonic_sort<1024, true>(sh.keys, pp);
         for (int i = tid; i < d; i += 1024) cnt += emit(i, sh.keys[i]);
     }
     // count of valid slots (they are a prefix of the sorted order)

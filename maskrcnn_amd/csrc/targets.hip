@@ -20,7 +20,7 @@
 // sample_by_key. The (key, anchor index) pairs of an image are distinct 55-bit numbers (31 key bits, 24 index bits), so "the k
 // smallest" is "those <= the k-th smallest", and that one is found by a radix select: seven histogram passes of 8 bits from the
 // top, positives and negatives in the same pass. A pass's workgroups first work out, each for itself and all alike, which digit
-// the pass before has settled (a 256-bin scan of that pass's histogram), then count the next digit of the elements that still
+// the pass before has settled (a 256-bin scan of that pass's histogram: block_inclusive_scan, workgroup.hpp), then count the next digit of the elements that still
 // carry the prefix: LDS histogram, then one integer atomic add per non-empty bin. Equal keys are told apart by the index bits, so
 // any number of ties costs nothing extra. 1 memset + 7 passes + 1 marking launch, whatever B is (an image is a grid row).
 //
@@ -31,6 +31,7 @@
 // compared with the image's row count, a decoded anchor index with A. Nothing here synchronises with the host.
 #include "common.hpp"
 #include "target_match.hpp"
+#include "workgroup.hpp"
 
 namespace {
 
@@ -192,21 +193,6 @@ __device__ __forceinline__ unsigned long long packed_key(int32_t key, int a) {
     return ((unsigned long long)((uint32_t)key & 0x7fffffffu) << 24) | (unsigned long long)(uint32_t)a;
 }
 
-// inclusive scan of one value per thread over the workgroup; s[255] holds the total afterwards
-__device__ uint32_t block_scan256(uint32_t v, uint32_t* s) {
-    const int tid = (int)threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const uint32_t t = tid >= off ? s[tid - off] : 0u;
-        __syncthreads();
-        s[tid] += t;
-        __syncthreads();
-    }
-    return s[tid];
-}
-
 // The states pass p (1..kPasses) filters with, from pass p-1's state and histogram: class 0 the positives, class 1 the negatives.
 // Every workgroup of image b computes the same values.
 __device__ void resolve_states(const SampleParams& q, int b, int p, SelState (&st)[2], uint32_t* s_scan, int* s_pick) {
@@ -215,8 +201,8 @@ __device__ void resolve_states(const SampleParams& q, int b, int p, SelState (&s
     for (int c = 0; c < 2; ++c) {
         const uint32_t* h = q.hist + (((int64_t)(p - 1) * q.batch + b) * 2 + c) * 256;
         const uint32_t v = h[tid];
-        const uint32_t incl = block_scan256(v, s_scan);
-        const uint32_t total = s_scan[kBlock - 1];
+        uint32_t total;
+        const uint32_t incl = mrcnn::block_inclusive_scan<kBlock>(v, s_scan, total);
         SelState prev;
         if (p == 1) {
             int k;
@@ -254,7 +240,7 @@ __device__ void resolve_states(const SampleParams& q, int b, int p, SelState (&s
 
 __global__ __launch_bounds__(kBlock) void sample_hist_kernel(SampleParams q, int p) {
     __shared__ uint32_t s_hist[2][256];
-    __shared__ uint32_t s_scan[kBlock];
+    __shared__ uint32_t s_scan[kBlock / mrcnn::kWave];
     __shared__ int s_pick[2];
     const int tid = (int)threadIdx.x, b = (int)blockIdx.y;
     SelState st[2];
@@ -291,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void sample_hist_kernel(SampleParams q, int
 }
 
 __global__ __launch_bounds__(kBlock) void sample_mark_kernel(SampleParams q) {
-    __shared__ uint32_t s_scan[kBlock];
+    __shared__ uint32_t s_scan[kBlock / mrcnn::kWave];
     __shared__ int s_pick[2];
     const int tid = (int)threadIdx.x, b = (int)blockIdx.y;
     SelState st[2];

@@ -233,6 +233,14 @@ def test_to_string_equals_the_golden_strings_and_round_trips(ops, cases):
     assert torch.equal(nr, num_runs)
     live = torch.arange(cap, device=DEV)[None, :] < nr[:, None]
     assert torch.equal(torch.where(live, cnt, torch.zeros_like(cnt)), counts)
+    # the row counts round the 1024-thread scan of the row bytes: one row, a row a thread, and the first with two for some
+    short = [c for c in cases if c["counts"].size <= 70]
+    for n in (1, 1024, 1025):
+        picks = [short[(5 * i + 3) % len(short)] for i in range(n)]
+        data, off = ops.rle_to_string(*table([c["counts"] for c in picks], 70, fill=9))
+        data, off = data.cpu().numpy(), off.cpu().numpy()
+        assert np.array_equal(off, np.concatenate([[0], np.cumsum([len(c["string"]) for c in picks])])), n
+        assert data.tobytes() == b"".join(c["string"] for c in picks), n
 
 
 def test_to_string_with_a_buffer_one_byte_short_reports_the_true_total_and_stays_inside(cases):

@@ -189,9 +189,25 @@ def test_a_part_over_capacity_reports_its_runs_and_nothing_is_written_outside(fx
 
 def test_a_part_with_more_vertices_than_the_on_chip_vertex_cache(fx):
     """3 000 and 2 049 vertices: the scanned edge counts of such a part live in the workspace, not in LDS. Against the numpy
-    restatement, which tests/test_poly_host.py pins to the reference; 2 048 vertices, the last size that stays on chip, too."""
-    from test_poly_host import fr_poly_ref
+    restatement, which tests/test_poly_host.py pins to the reference; 2 048 vertices, the last size that stays on chip, too.
+    And the sizes of the on-chip sort: rectangles with exactly 257 keys below h*w (one more than the workgroup has threads),
+    with rle_from_poly_onchip_keys() of them (the sort's capacity, no padding) and with one more (range by range)."""
+    from maskrcnn_amd import ops
+    from test_poly_host import fr_poly_ref, poly_keys_ref
     g = fx.g
+    onchip = ops.rle_from_poly_onchip_keys()
+    # a rectangle over c pixel columns has 2c crossings; with its lower edge on y == h of the LAST column one of them is the
+    # alias key h*w, which is not sorted
+    rect = lambda x0, y0, x1, y1: np.array([[x0, y0], [x0, y1], [x1, y1], [x1, y0]], dtype=np.float64)
+    sized = [(rect(11, 1, 140, 4), 4, 140, 257), (rect(2, .5, 2 + onchip // 2, 1.5), 2, onchip // 2 + 4, onchip),
+             (rect(0, 1, onchip // 2 + 1, 2), 2, onchip // 2 + 1, onchip + 1)]
+    for xy, h, w, m in sized:
+        assert int((poly_keys_ref(xy, h, w) < h * w).sum()) == m
+    nr, cnt, nk = raw_from_poly(poly_args([s[0] for s in sized], [s[1] for s in sized], [s[2] for s in sized]), onchip + 8)
+    for j, (xy, h, w, m) in enumerate(sized):
+        want = fr_poly_ref(xy, h, w)
+        assert nr[j] == want.size and np.array_equal(cnt[j, :nr[j]], want) and (cnt[j, nr[j]:] == POISON).all(), m
+        assert nk[j] == poly_keys_ref(xy, h, w).size and want.size >= m
     rng = np.random.default_rng(11)
     def ring(k, h, w):
         a = np.sort(rng.uniform(0, 2 * np.pi, k))

@@ -312,7 +312,9 @@ def test_topk_desc_sorted_equal_full_and_misaligned_rows(dev):
         if k == 2000:
             assert ncand[0] > 4096
         _run_topk_case(asc.flip(1).contiguous(), k, dev, ("descending", k))
-    for n, k in ((3000, 1000), (N_ANCHORS, 1000), (N_ANCHORS, 4096), (5000, 5)):
+    # 5000 equal scores are more candidates than the LDS sort holds: exact_topk_row sorts exactly k composites, k = 1 among them
+    # (no sort step at all) and k = 65 (one past a wave)
+    for n, k in ((3000, 1000), (N_ANCHORS, 1000), (N_ANCHORS, 4096), (5000, 5), (5000, 1), (5000, 65)):
         s = torch.full((2, n), 0.25)
         top, order, ncand = _topk(s.to(dev), k, dev)
         assert torch.equal(order, torch.arange(k).expand(2, k)) and bool((top == 0.25).all()), (n, k)
@@ -717,9 +719,10 @@ def test_detection_select_sizes_counts_nan_and_ties(dev, p):
     """rois_per_image P in {1, 2, 1023, 1024, 1025, 4095, 4096} (the register sort and the LDS sort meet at 1024); max_instances
     of 1, of P (more than there are candidates) and in between; keep_counts of 0 and P; an all-background image; scores
     quantised to eight values so that equal scores straddle the cut; NaN scores of both signs, which rank first in index order
-    (torch.sort(stable=True, descending=True)). Bit for bit."""
+    (torch.sort(stable=True, descending=True)). Images 5 and 6: exactly one candidate and exactly min(65, P) candidates, all
+    foreground (the LDS sort of P > 1024 with a single real key, and with one more than a wave of them). Bit for bit."""
     g = torch.Generator().manual_seed(5200 + p)
-    b = 5
+    b = 7
     dets = torch.rand(b, p, 5, generator=g)
     dets[..., :4] = (dets[..., :4] * 900).round()
     dets[0, :, 4] = torch.randint(0, 8, (p,), generator=g).float() / 8            # ties across every cut
@@ -731,8 +734,9 @@ def test_detection_select_sizes_counts_nan_and_ties(dev, p):
     class_ids = torch.randint(0, 81, (b, p), generator=g)
     class_ids[2] = 0                                                               # all background
     class_ids[0] = class_ids[0].clamp_min(1)                                       # all foreground
+    class_ids[5:] = class_ids[5:].clamp_min(1)
     nms_cls = torch.where(class_ids > 0, class_ids, -torch.arange(1, p + 1).expand(b, p)).to(I32)
-    counts = [p, 0, p, p, int(torch.randint(0, p + 1, (1,), generator=g))]
+    counts = [p, 0, p, p, int(torch.randint(0, p + 1, (1,), generator=g)), 1, min(65, p)]
     keep = _keep_rows(g, b, p, counts)
     for d in sorted({1, p, min(p, 100), max(1, p // 2)}):
         ids, scores, boxes, rois, cnt = _detection_select(dets, nms_cls, class_ids, keep, torch.tensor(counts, dtype=I32), d, dev)

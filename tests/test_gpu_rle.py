@@ -180,6 +180,7 @@ def test_random_shapes_and_batches_vs_restatement(ops):
     rng = np.random.default_rng(7)
     shapes = [(37, 53), (1, 1), (2, 3), (64, 64), (100, 31), (31, 100), (257, 129), (40, 1), (1, 40), (513, 66), (90, 2049)]
     shapes += [tuple(int(v) for v in rng.integers(1, 70, 2)) for _ in range(20)]
+    shapes += [(5, 1024), (5, 1025)]      # one segment of rows: 1024 and 1025 cells, a cell a thread of the scan and one more
     for h, w in shapes:
         n = int(rng.integers(1, 6))
         masks = rng.random((n, h, w)) < rng.choice([0.03, 0.3, 0.5, 0.9])

@@ -86,6 +86,16 @@ def check_case(c, anchor_match, sample_by_key, rpn_deltas):
     sampled = sample_by_key(match_u, keys, c["count"])
     assert sampled.data_ptr() != match_u.data_ptr() and np.array_equal(match_u.cpu().numpy(), c["match_u"])   # the input is not touched
     assert np.array_equal(sampled.cpu().numpy(), c["match"]), name
+    # the ends of the 256-bin scan of the radix select, which takes the digits (key << 24 | anchor) >> 48, >> 40, ... & 255: every
+    # key in bin 0 of the first pass (key >> 24 == 0), then every key in bin 255 of the second ((key >> 16) & 255 == 255; the
+    # first pass's digit is a 31-bit key's top 7 bits and never passes 127), where only the scan's last thread holds a count.
+    # Against the numpy route, which test_targets_host.py holds to the fixture
+    from maskrcnn_amd import targets
+    for what, ends in (("bin 0", c["keys"] >> 8), ("bin 255", (c["keys"] & 0xffff) | 0x00ff0000)):
+        ends = np.ascontiguousarray(ends.astype(np.int32))
+        assert (ends >> 24 == 0).all() and (what == "bin 0" or ((ends >> 16) & 255 == 255).all())
+        want = np.stack([targets.sample_numpy(c["match_u"][i], ends[i], c["count"]) for i in range(c["batch"])])
+        assert np.array_equal(sample_by_key(match_u, dev(ends), c["count"]).cpu().numpy(), want), (name, what)
 
     differ = 0
     bbox, num_pos = rpn_deltas(a, boxes, off, sampled, arg, c["count"])
