@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 25
+#define MRCNN_ABI_VERSION 26
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -908,6 +908,82 @@ int mrcnn_mask_targets_u8(const uint8_t* gt_masks, int32_t num_rows, int32_t hei
 int mrcnn_mask_targets_f32(const float* gt_masks, int32_t num_rows, int32_t height, int32_t width, const int32_t* gt_off,
                            int32_t batch, int32_t count, const float* rois_out, const int32_t* gt_index, const int32_t* num_pos,
                            int32_t mask_height, int32_t mask_width, float* target_mask, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training losses — replace  RPN.class_loss / RPN.boxes_loss  (model.py:652-718),  Classifier.class_loss / Classifier.boxes_loss
+ * (model.py:802-845) and  Mask.mask_loss  (model.py:922-953), the five losses train_epoch adds up (model.py:1622-1629), forward and
+ * backward for a batch of B images (csrc/losses.hip). They read the padded [B][count][...] outputs of the target calls above in
+ * place: no torch.nonzero, no gather, no host read.
+ *
+ * The rule. Every contributing element's term and derivative is evaluated in fp64 from the fp32 inputs. The terms of an image are
+ * summed in fp64 in a FIXED order by store-and-sum: a workgroup writes its partial sum with plain stores, a later launch adds the
+ * partials in index order (each thread a run of consecutive partials, the runs in thread order); no floating-point atomic, no
+ * ticket or last-block protocol — two calls on the same inputs return the same bits. Quotients and gradients are narrowed to fp32
+ * last. The per-element definitions are those of the stock torch functions the reference calls:
+ *   cross entropy (RPN class loss over 2 logits, head class loss over C): term log(sum_j exp(x_j - max)) - (x_c - max);
+ *     derivative softmax(x)_j - [j == c].
+ *   smooth L1, beta 1, d = pred - target: term 0.5 d^2 if |d| < 1, else |d| - 0.5; derivative d if |d| < 1, else sign(d).
+ *   binary cross entropy on a probability p with target y (y need not be 0 or 1):
+ *     term -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)), log(1 - p) taken as log1p(-p) as torch takes it;
+ *     derivative (p - y) / max(p (1 - p), 1e-12).
+ * Which elements contribute, for image b:
+ *   RPN class loss: anchors with match != 0, class 1 if match == 1, else 0. count: n_cls[b].
+ *   RPN box loss: anchors with match == 1 in ascending anchor index, the k-th paired with target_bbox[b][k][:] (mrcnn_rpn_deltas
+ *     writes them in that order); 4 elements each, count 4 P[b]. A positive whose rank is >= count has no target row: it is left
+ *     out and bit 0 of status[b] is set.
+ *   head class loss: slots s < num_rois[b] (the caller passes num_pos + num_neg; clamped into [0, count]), class
+ *     target_class_ids[b][s]; padding slots never contribute, whatever their logits hold. A class id outside 0 .. C-1 sets status
+ *     bit 1 and the slot is skipped in all three losses.
+ *   head box loss: those slots with target_class_ids > 0: pred_bbox[b][s][class][:] against target_deltas[b][s][:].
+ *   mask loss: the same slots: pred_masks[b][s][class][:][:] against target_mask[b][s][:][:], mh * mw elements per slot.
+ * An element that does not contribute is never read into the arithmetic (a select, not a multiply by zero): a NaN or Inf in a
+ * neutral anchor's logits, in a padding slot or in another class's plane changes nothing.
+ * Reductions are the caller's: the calls return per loss the per-image fp64 sums and int32 counts. loss = sum / count over the
+ * batch ("mean": the reference's functions on the concatenation of the images, the reference itself at B = 1) or per image.
+ * DEVIATION: a loss without a contributing element is 0 with all-zero gradients. The reference's head losses say so themselves
+ * for an empty input, but F.cross_entropy / F.smooth_l1_loss / F.binary_cross_entropy over nothing — its RPN losses on an image
+ * without a sampled anchor, its head box and mask losses on negatives only — return NaN, the mean of nothing.
+ * The backward calls write EVERY element of the dense gradients (a non-contributing element is +0) with full-width stores, and
+ * scale by the upstream gradient and the forward's counts, both read from device memory: grad_out fp32 [kLosses] and the counts
+ * summed over the batch (per_image == 0), or grad_out fp32 [B][kLosses] and the image's own counts (per_image != 0).
+ * Limits: A in [1, 2^24], B in [1, 65535], B * A < 2^31, count in [1, 1024], C in [2, 4096], mh, mw in [1, 64]; offsets are 64-bit.
+ * No call synchronises with the host or allocates; two launches forward and one backward per family, whatever B is.
+ * Alignment: float4 rows (pred_bbox, target_bbox, target_deltas, grad_bbox) 16 bytes, RPN logits and their gradient 8, workspaces 8.
+ *
+ * mrcnn_rpn_loss_forward: match int32 [B][A], logits fp32 [B][A][2], pred_bbox fp32 [B][A][4], target_bbox fp32 [B][count][4] →
+ *   sums fp64 [B][2] (class, box), counts int32 [B][2] (n_cls, 4 min(P, count)), status int32 [B], and chunk_pos int32
+ *   [B][mrcnn_rpn_loss_chunks(A)]: the positives of each chunk of 1024 anchors, from which the backward call ranks the positives
+ *   in its single launch (the scan over match == 1 across workgroups, as mrcnn_rpn_deltas does it). Only the contributing anchors'
+ *   logits and deltas are loaded; the pass over the rest reads match alone.
+ * mrcnn_rpn_loss_backward → grad_logits fp32 [B][A][2], grad_bbox fp32 [B][A][4]; chunk_pos and counts as the forward wrote them.
+ * mrcnn_head_loss_forward: target_class_ids int32 [B][count], num_rois int32 [B], target_deltas fp32 [B][count][4], target_mask
+ *   fp32 [B][count][mh][mw], logits fp32 [B][count][C], pred_bbox fp32 [B][count][C][4], pred_masks fp32 [B][count][C][mh][mw]
+ *   (the reference's [R, C, ...] with R = B * count) → sums fp64 [B][3] (class, box, mask), counts int32 [B][3] (slots, 4 positives,
+ *   mh mw positives), status int32 [B]. One workgroup per slot stores the slot's three partial sums; a second launch adds the
+ *   slots of each image in slot order.
+ * mrcnn_head_loss_backward → grad_logits, grad_bbox, grad_masks in the predictions' shapes: zeros but the slot's logits row, the
+ *   class's row of pred_bbox and the class's plane of pred_masks; the mask gradient is written with 16-byte stores.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t mrcnn_rpn_loss_chunks(int32_t num_anchors);
+size_t mrcnn_rpn_loss_workspace_bytes(int32_t batch, int32_t num_anchors, int32_t count);
+int mrcnn_rpn_loss_forward(const int32_t* match, const float* logits, const float* pred_bbox, const float* target_bbox,
+                           int32_t batch, int32_t num_anchors, int32_t count, double* sums, int32_t* counts, int32_t* status,
+                           int32_t* chunk_pos, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+int mrcnn_rpn_loss_backward(const int32_t* match, const float* logits, const float* pred_bbox, const float* target_bbox,
+                            const int32_t* chunk_pos, const int32_t* counts, const float* grad_out, int32_t per_image,
+                            int32_t batch, int32_t num_anchors, int32_t count, float* grad_logits, float* grad_bbox,
+                            mrcnn_stream_t stream);
+size_t mrcnn_head_loss_workspace_bytes(int32_t batch, int32_t count);
+int mrcnn_head_loss_forward(const int32_t* target_class_ids, const int32_t* num_rois, const float* target_deltas,
+                            const float* target_mask, const float* logits, const float* pred_bbox, const float* pred_masks,
+                            int32_t batch, int32_t count, int32_t num_classes, int32_t mask_height, int32_t mask_width,
+                            double* sums, int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                            mrcnn_stream_t stream);
+int mrcnn_head_loss_backward(const int32_t* target_class_ids, const int32_t* num_rois, const float* target_deltas,
+                             const float* target_mask, const float* logits, const float* pred_bbox, const float* pred_masks,
+                             const int32_t* counts, const float* grad_out, int32_t per_image, int32_t batch, int32_t count,
+                             int32_t num_classes, int32_t mask_height, int32_t mask_width, float* grad_logits, float* grad_bbox,
+                             float* grad_masks, mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

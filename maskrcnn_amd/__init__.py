@@ -5,7 +5,7 @@ PyTorch fallback for the ops (a missing library is an ImportError).
 """
 from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import ops  # noqa: F401  (registers torch.ops.maskrcnn.*)
-
+from . import losses  # noqa: F401  (the training losses on the targets' padded outputs)
 
 
 def roi_align(inputs, pool_size, image_shape):
@@ -29,4 +29,4 @@ def roi_align(inputs, pool_size, image_shape):
     return ops.nhwc_to_nchw(pooled)
 
 
-__all__ = ["ops", "roi_align"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)
+__all__ = ["ops", "roi_align", "losses"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)

@@ -34,7 +34,8 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
            "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
            "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances",
-           "anchor_match", "sample_by_key", "rpn_deltas", "detection_targets", "mask_targets"]
+           "anchor_match", "sample_by_key", "rpn_deltas", "detection_targets", "mask_targets",
+           "rpn_loss", "rpn_loss_backward", "head_loss", "head_loss_backward"]
 
 _LIB = torch.library.Library("maskrcnn", "DEF")
 
@@ -2011,6 +2012,169 @@ _LIB.define("mask_targets(Tensor gt_masks, Tensor gt_off, Tensor rois_out, Tenso
             "int[] mask_shape=[28, 28]) -> Tensor")
 _LIB.impl("mask_targets", lambda *a, **k: mask_targets(*a, **k), "CUDA")
 _LIB.impl("mask_targets", lambda gt_masks, *a, **k: _need_gpu(gt_masks), "CPU")
+
+
+# --------------------------------------------------------------------------------------------------
+# Training losses: the reference's five loss functions for a batch, forward and backward (csrc/losses.hip)
+# --------------------------------------------------------------------------------------------------
+def _loss_input(who, name, t, dtype, shape):
+    """A contiguous tensor of this dtype and shape whose first byte is 16-byte aligned (the kernels read float4 rows)."""
+    _need_gpu(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{who}: {name} must be {dtype} {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox):
+    _need_gpu(match, logits, pred_bbox, target_bbox)
+    if match.dtype != torch.int32 or match.dim() != 2 or match.size(0) < 1 or match.size(1) < 1:
+        raise RuntimeError(f"{who}: match must be int32 [B,A] with B, A >= 1, got {match.dtype} {tuple(match.shape)}")
+    b, a = match.shape
+    if target_bbox.dim() != 3 or target_bbox.size(1) < 1:
+        raise RuntimeError(f"{who}: target_bbox must be float32 [{b},count,4] with count >= 1, got {tuple(target_bbox.shape)}")
+    count = target_bbox.size(1)
+    return (_loss_input(who, "match", match, torch.int32, (b, a)), _loss_input(who, "logits", logits, torch.float32, (b, a, 2)),
+            _loss_input(who, "pred_bbox", pred_bbox, torch.float32, (b, a, 4)),
+            _loss_input(who, "target_bbox", target_bbox, torch.float32, (b, count, 4)), b, a, count)
+
+
+def _loss_grad_out(who, grad_out, counts, losses: int):
+    """grad_out float32 [losses] (the batch's mean) or [B,losses] (per image) → (grad_out, counts, per_image)."""
+    b = counts.size(0)
+    _need_gpu(grad_out, counts)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (b, losses):
+        raise RuntimeError(f"{who}: counts must be int32 [B,{losses}] as the forward returned them, got {counts.dtype} {tuple(counts.shape)}")
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) not in ((losses,), (b, losses)):
+        raise RuntimeError(f"{who}: grad_out must be float32 [{losses}] or [{b},{losses}], got {grad_out.dtype} {tuple(grad_out.shape)}")
+    return grad_out.contiguous(), counts.contiguous(), grad_out.dim() == 2
+
+
+@_on_device
+def rpn_loss(match: torch.Tensor, logits: torch.Tensor, pred_bbox: torch.Tensor, target_bbox: torch.Tensor):
+    """RPN.class_loss and RPN.boxes_loss (model.py:652-718) for B images; the rule is stated at mrcnn_rpn_loss_forward in
+    include/maskrcnn_hip.h. match int32 [B,A] of -1 / 0 / 1, logits float32 [B,A,2], pred_bbox float32 [B,A,4], target_bbox float32
+    [B,count,4] as rpn_deltas wrote it → (sums float64 [B,2]: the class and box terms of each image, counts int32 [B,2]: the
+    anchors with match != 0 and 4 x the positives that have a target row, status int32 [B]: bit 0 = more than count positives,
+    chunk_pos int32 [B,chunks]: what rpn_loss_backward ranks the positives by). A loss is sums / counts, over the batch or per
+    image. Two launches, no host synchronisation."""
+    who = "rpn_loss"
+    match, logits, pred_bbox, target_bbox, b, a, count = _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox)
+    dev = match.device
+    sums = torch.empty(b, 2, dtype=torch.float64, device=dev)
+    counts = torch.empty(b, 2, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    chunk_pos = torch.empty(b, max(int(lib.mrcnn_rpn_loss_chunks(a)), 1), dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rpn_loss_workspace_bytes(b, a, count))
+    ws = _workspace(nbytes, dev)
+    _launch(lib.mrcnn_rpn_loss_forward,
+            (match.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(), target_bbox.data_ptr(), b, a, count, sums.data_ptr(),
+             counts.data_ptr(), status.data_ptr(), chunk_pos.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, count), 4 * b * a + 56 * b * count, "rpn_loss"))
+    return sums, counts, status, chunk_pos
+
+
+@_on_device
+def rpn_loss_backward(match: torch.Tensor, logits: torch.Tensor, pred_bbox: torch.Tensor, target_bbox: torch.Tensor,
+                      chunk_pos: torch.Tensor, counts: torch.Tensor, grad_out: torch.Tensor):
+    """The gradients of rpn_loss's two losses → (grad_logits float32 [B,A,2], grad_bbox float32 [B,A,4]), every element written,
+    +0 where an anchor does not contribute. counts and chunk_pos as rpn_loss returned them; grad_out float32 [2]: the upstream
+    gradients of (class loss, box loss) = batch sums / batch counts, or [B,2]: of each image's own sums / counts. One launch, no
+    host synchronisation."""
+    who = "rpn_loss_backward"
+    match, logits, pred_bbox, target_bbox, b, a, count = _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox)
+    chunk_pos = _loss_input(who, "chunk_pos", chunk_pos, torch.int32, (b, max(int(lib.mrcnn_rpn_loss_chunks(a)), 1)))
+    grad_out, counts, per_image = _loss_grad_out(who, grad_out, counts, 2)
+    grad_logits, grad_bbox = torch.empty_like(logits), torch.empty_like(pred_bbox)
+    _launch(lib.mrcnn_rpn_loss_backward,
+            (match.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(), target_bbox.data_ptr(), chunk_pos.data_ptr(),
+             counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, a, count, grad_logits.data_ptr(), grad_bbox.data_ptr(),
+             _stream()),
+            lambda: (0, (b, a, count), 28 * b * a, "rpn_loss_backward"))
+    return grad_logits, grad_bbox
+
+
+def _head_loss_inputs(who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks):
+    _need_gpu(target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
+    if target_class_ids.dtype != torch.int32 or target_class_ids.dim() != 2 or target_class_ids.size(0) < 1 or target_class_ids.size(1) < 1:
+        raise RuntimeError(f"{who}: target_class_ids must be int32 [B,count] with B, count >= 1, got {target_class_ids.dtype} "
+                           f"{tuple(target_class_ids.shape)}")
+    b, count = target_class_ids.shape
+    if target_mask.dim() != 4 or logits.dim() != 3 or logits.size(2) < 1:
+        raise RuntimeError(f"{who}: target_mask must be float32 [{b},{count},mh,mw] and logits float32 [{b},{count},C], got "
+                           f"{tuple(target_mask.shape)} and {tuple(logits.shape)}")
+    c, mh, mw = logits.size(2), target_mask.size(2), target_mask.size(3)
+    return (_loss_input(who, "target_class_ids", target_class_ids, torch.int32, (b, count)),
+            _loss_input(who, "num_rois", num_rois, torch.int32, (b,)),
+            _loss_input(who, "target_deltas", target_deltas, torch.float32, (b, count, 4)),
+            _loss_input(who, "target_mask", target_mask, torch.float32, (b, count, mh, mw)),
+            _loss_input(who, "logits", logits, torch.float32, (b, count, c)),
+            _loss_input(who, "pred_bbox", pred_bbox, torch.float32, (b, count, c, 4)),
+            _loss_input(who, "pred_masks", pred_masks, torch.float32, (b, count, c, mh, mw)), b, count, c, mh, mw)
+
+
+@_on_device
+def head_loss(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_deltas: torch.Tensor, target_mask: torch.Tensor,
+              logits: torch.Tensor, pred_bbox: torch.Tensor, pred_masks: torch.Tensor):
+    """Classifier.class_loss, Classifier.boxes_loss and Mask.mask_loss (model.py:802-845, 922-953) for B images on the padded outputs
+    of detection_targets; the rule is stated at mrcnn_rpn_loss_forward in include/maskrcnn_hip.h. target_class_ids int32 [B,count],
+    num_rois int32 [B] (num_pos + num_neg: the slots past it never contribute), target_deltas float32 [B,count,4], target_mask
+    float32 [B,count,mh,mw], logits float32 [B,count,C], pred_bbox float32 [B,count,C,4], pred_masks float32 [B,count,C,mh,mw] →
+    (sums float64 [B,3]: class, box, mask; counts int32 [B,3]: the slots, 4 x the positive slots, mh x mw x the positive slots;
+    status int32 [B]: bit 1 = a class id outside 0 .. C-1, whose slot is skipped). Two launches, no host synchronisation."""
+    who = "head_loss"
+    ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
+        who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
+    dev = ids.device
+    sums = torch.empty(b, 3, dtype=torch.float64, device=dev)
+    counts = torch.empty(b, 3, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_head_loss_workspace_bytes(b, count))
+    ws = _workspace(nbytes, dev)
+    _launch(lib.mrcnn_head_loss_forward,
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
+             pred_masks.data_ptr(), b, count, c, mh, mw, sums.data_ptr(), counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+             _stream()),
+            lambda: (0, (b, count, c), 4 * b * count * (c + 2 * mh * mw + 10), "head_loss"))
+    return sums, counts, status
+
+
+@_on_device
+def head_loss_backward(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_deltas: torch.Tensor, target_mask: torch.Tensor,
+                       logits: torch.Tensor, pred_bbox: torch.Tensor, pred_masks: torch.Tensor, counts: torch.Tensor,
+                       grad_out: torch.Tensor):
+    """The gradients of head_loss's three losses → (grad_logits, grad_bbox, grad_masks) in the predictions' shapes, every element
+    written: zeros but the contributing slots' logits rows, their class's box row and their class's mask plane. counts as
+    head_loss returned them; grad_out float32 [3] (batch mean) or [B,3] (per image), as for rpn_loss_backward. One launch, no host
+    synchronisation."""
+    who = "head_loss_backward"
+    ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
+        who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
+    grad_out, counts, per_image = _loss_grad_out(who, grad_out, counts, 3)
+    grad_logits, grad_bbox, grad_masks = torch.empty_like(logits), torch.empty_like(pred_bbox), torch.empty_like(pred_masks)
+    _launch(lib.mrcnn_head_loss_backward,
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
+             pred_masks.data_ptr(), counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, count, c, mh, mw,
+             grad_logits.data_ptr(), grad_bbox.data_ptr(), grad_masks.data_ptr(), _stream()),
+            lambda: (0, (b, count, c), 4 * b * count * c * (mh * mw + 5), "head_loss_backward"))
+    return grad_logits, grad_bbox, grad_masks
+
+
+_LIB.define("rpn_loss(Tensor match, Tensor logits, Tensor pred_bbox, Tensor target_bbox) -> (Tensor, Tensor, Tensor, Tensor)")
+_LIB.impl("rpn_loss", rpn_loss, "CUDA")
+_LIB.impl("rpn_loss", lambda match, *a: _need_gpu(match), "CPU")
+_LIB.define("rpn_loss_backward(Tensor match, Tensor logits, Tensor pred_bbox, Tensor target_bbox, Tensor chunk_pos, Tensor counts, "
+            "Tensor grad_out) -> (Tensor, Tensor)")
+_LIB.impl("rpn_loss_backward", rpn_loss_backward, "CUDA")
+_LIB.impl("rpn_loss_backward", lambda match, *a: _need_gpu(match), "CPU")
+_LIB.define("head_loss(Tensor target_class_ids, Tensor num_rois, Tensor target_deltas, Tensor target_mask, Tensor logits, "
+            "Tensor pred_bbox, Tensor pred_masks) -> (Tensor, Tensor, Tensor)")
+_LIB.impl("head_loss", head_loss, "CUDA")
+_LIB.impl("head_loss", lambda ids, *a: _need_gpu(ids), "CPU")
+_LIB.define("head_loss_backward(Tensor target_class_ids, Tensor num_rois, Tensor target_deltas, Tensor target_mask, Tensor logits, "
+            "Tensor pred_bbox, Tensor pred_masks, Tensor counts, Tensor grad_out) -> (Tensor, Tensor, Tensor)")
+_LIB.impl("head_loss_backward", head_loss_backward, "CUDA")
+_LIB.impl("head_loss_backward", lambda ids, *a: _need_gpu(ids), "CPU")
 
 
 # --------------------------------------------------------------------------------------------------
