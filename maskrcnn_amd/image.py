@@ -206,7 +206,7 @@ def rle_masks_from_table(size, num_runs: torch.Tensor, counts: torch.Tensor) -> 
     most 6 per run for masks of up to 2^28 pixels) straight into the [N, 6*capacity] layout (ops.rle_to_string_rows). A row that
     was refused or is over its capacity keeps its num_runs and has string_bytes 0, area -1 and bbox -1; to_coco() raises on it."""
     h, w = int(size[0]), int(size[1])
-    num_runs, counts = ops._rle_table((num_runs, counts), "rle_masks_from_table")
+    num_runs, counts = ops.rle_table((num_runs, counts), "rle_masks_from_table")
     n, cap, dev = num_runs.size(0), counts.size(1), num_runs.device
     sizes = torch.tensor([h, w], dtype=torch.int32, device=dev)
     areas, bboxes = ops.rle_area_bbox(num_runs, counts, sizes[0].expand(n).contiguous(), sizes[1].expand(n).contiguous())

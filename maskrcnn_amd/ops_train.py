@@ -1,0 +1,315 @@
+"""Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip) and the five
+losses, forward and backward (csrc/losses.hip). ops.py re-exports every name here; argument checks and registration are
+_binding.py's."""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from ._binding import _launch, _on_device, _ptr0, _stream, checked, checked_out, register, workspace
+from ._lib import lib
+
+_I32, _F32 = torch.int32, torch.float32
+_ANCHORS_HINT = " (anchors.pyramid_anchors(cfg, dtype=torch.float64))"
+
+
+# --------------------------------------------------------------------------------------------------
+# RPN training targets: data.rpn_samples for a batch (csrc/targets.hip)
+# --------------------------------------------------------------------------------------------------
+def _target_std(who, std_dev):
+    std = [float(v) for v in std_dev]
+    if len(std) != 4:
+        raise RuntimeError(f"{who}: std_dev must hold 4 numbers, got {len(std)}")
+    return std
+
+
+@_on_device
+def anchor_match(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: torch.Tensor, gt_off: torch.Tensor,
+                 neg_iou: float = 0.3, pos_iou: float = 0.7, crowd_iou: float = 0.001):
+    """Steps 1-6 of data.rpn_samples (data.py:485-540; the rule is stated at mrcnn_anchor_match in include/maskrcnn_hip.h) for B
+    images: anchors float64 [A,4], ground truth packed as gt_boxes float32 [M,4], gt_class_ids int32 [M], gt_off int32 [B+1] →
+    (match int32 [B,A] of -1 / 0 / 1, iou_argmax int32 [B,A] (row position within the image), iou_max float32 [B,A], gt_argmax
+    int32 [M] (-1: crowd or dropped row), status int32 [B] (bit 0: no kept row in the image)). The thresholds are narrowed to
+    fp32. No host synchronisation."""
+    who = "anchor_match"
+    anchors = checked(who, "anchors", anchors, torch.float64, (("A", 1), 4), hint=_ANCHORS_HINT)
+    gt_boxes = checked(who, "gt_boxes", gt_boxes, _F32, ("M", 4))
+    gt_off = checked(who, "gt_off", gt_off, _I32, (("B+1", 2),))
+    m, a, b, dev = gt_boxes.size(0), anchors.size(0), gt_off.numel() - 1, anchors.device
+    gt_class_ids = checked(who, "gt_class_ids", gt_class_ids, _I32, (m,))
+    match = torch.empty(b, a, dtype=torch.int32, device=dev)
+    iou_argmax = torch.empty(b, a, dtype=torch.int32, device=dev)
+    iou_max = torch.empty(b, a, dtype=torch.float32, device=dev)
+    gt_argmax = torch.empty(m, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_anchor_match_workspace_bytes(m))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_anchor_match,
+            (anchors.data_ptr(), a, _ptr0(gt_boxes), _ptr0(gt_class_ids), gt_off.data_ptr(), m, b,
+             float(neg_iou), float(pos_iou), float(crowd_iou), match.data_ptr(), iou_argmax.data_ptr(), iou_max.data_ptr(),
+             _ptr0(gt_argmax), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, m), 32 * a + 12 * b * a, "anchor_match"))
+    return match, iou_argmax, iou_max, gt_argmax, status
+
+
+@_on_device
+def sample_by_key(match: torch.Tensor, keys: torch.Tensor, count: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Steps 7-8 of data.rpn_samples (data.py:542-557) for match int32 [B,A]: of an image's positives the count // 2 with the
+    smallest (key, anchor index) stay positive, then of its negatives the count - (positives left) with the smallest stay
+    negative; the others become 0. keys int32 [B,A], non-negative (the caller's stand-in for np.random.choice: independent
+    uniform keys draw from the same distribution). → out int32 [B,A] (a new tensor when none is given; `out is match` works in
+    place). No host synchronisation."""
+    who = "sample_by_key"
+    match = checked(who, "match", match, _I32, (("B", 1), ("A", 1)))    # `out is match`: contiguous then, and passed on as it is
+    b, a = match.shape
+    keys = checked(who, "keys", keys, _I32, (b, a))
+    out = checked_out(who, "out", out, _I32, (b, a), match.device)
+    nbytes = int(lib.mrcnn_sample_by_key_workspace_bytes(b))
+    ws = workspace(nbytes, match.device)
+    _launch(lib.mrcnn_sample_by_key,
+            (match.data_ptr(), keys.data_ptr(), b, a, int(count), out.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, int(count)), 8 * 8 * b * a, "sample_by_key"))
+    return out
+
+
+@_on_device
+def rpn_deltas(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_off: torch.Tensor, match: torch.Tensor, iou_argmax: torch.Tensor,
+               count: int, std_dev=(0.1, 0.1, 0.2, 0.2)):
+    """Step 9 of data.rpn_samples (data.py:559-589): the regression deltas of an image's positives (match == 1) in ascending
+    anchor index against row iou_argmax of the image, divided by std_dev (four host numbers, used as fp64) and narrowed to fp32,
+    with the reference's NumPy >= 2 promotion (mrcnn_rpn_deltas in include/maskrcnn_hip.h) → (rpn_bbox float32 [B,count,4], rows
+    past the positives 0; num_pos int32 [B]). Positives beyond `count` are counted, not written. No host synchronisation."""
+    who = "rpn_deltas"
+    anchors = checked(who, "anchors", anchors, torch.float64, (("A", 1), 4), hint=_ANCHORS_HINT)
+    gt_boxes = checked(who, "gt_boxes", gt_boxes, _F32, ("M", 4))
+    gt_off = checked(who, "gt_off", gt_off, _I32, (("B+1", 2),))
+    m, a, b, dev = gt_boxes.size(0), anchors.size(0), gt_off.numel() - 1, anchors.device
+    match = checked(who, "match", match, _I32, (b, a))
+    iou_argmax = checked(who, "iou_argmax", iou_argmax, _I32, (b, a))
+    count = int(count)
+    std = _target_std(who, std_dev)
+    rpn_bbox = torch.empty(b, max(count, 0), 4, dtype=torch.float32, device=dev)
+    num_pos = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rpn_deltas_workspace_bytes(b, a))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_rpn_deltas,
+            (anchors.data_ptr(), a, _ptr0(gt_boxes), gt_off.data_ptr(), m, b, match.data_ptr(), iou_argmax.data_ptr(),
+             count, (ctypes.c_double * 4)(*std), _ptr0(rpn_bbox), num_pos.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, count), 2 * 4 * b * a + 16 * b * count, "rpn_deltas"))
+    return rpn_bbox, num_pos
+
+
+register("anchor_match(Tensor anchors, Tensor gt_boxes, Tensor gt_class_ids, Tensor gt_off, float neg_iou=0.3, float pos_iou=0.7, "
+         "float crowd_iou=0.001) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", anchor_match)
+register("sample_by_key(Tensor match, Tensor keys, int count) -> Tensor", sample_by_key)   # `out` is the Python binding's
+register("rpn_deltas(Tensor anchors, Tensor gt_boxes, Tensor gt_off, Tensor match, Tensor iou_argmax, int count, "
+         "float[] std_dev) -> (Tensor, Tensor)", rpn_deltas)
+
+
+# --------------------------------------------------------------------------------------------------
+# Detection training targets: model.mrn_samples for a batch (csrc/detection_targets.hip)
+# --------------------------------------------------------------------------------------------------
+@_on_device
+def detection_targets(rois: torch.Tensor, gt_boxes: torch.Tensor, gt_class_ids: torch.Tensor, gt_off: torch.Tensor,
+                      keys: torch.Tensor, count: int = 100, positive_ratio: float = 0.33, std_dev=(0.1, 0.1, 0.2, 0.2),
+                      pos_iou: float = 0.5, crowd_iou: float = 0.001, out=None):
+    """Steps 1-6 of model.mrn_samples (model.py:396-576; the rule is stated at mrcnn_detection_targets in include/maskrcnn_hip.h)
+    for B images: rois float32 [B,N,4], ground truth packed as gt_boxes float32 [M,4], gt_class_ids int32 [M], gt_off int32 [B+1],
+    keys int32 [B,N] (non-negative: the stand-in for torch.randperm, as in sample_by_key) →
+    (rois_out float32 [B,count,4], target_class_ids int32 [B,count], target_deltas float32 [B,count,4], roi_index int32 [B,count],
+    gt_index int32 [B,count], num_pos int32 [B], num_neg int32 [B], status int32 [B] (bit 0: no kept row in the image)).
+    The positives come first, then the negatives, each by ascending (key, roi index); rows past num_pos + num_neg are 0 / -1.
+    std_dev: four host numbers, narrowed to fp32, as are the thresholds. out: the eight tensors to write into. One launch, no
+    host synchronisation."""
+    who = "detection_targets"
+    rois = checked(who, "rois", rois, _F32, (("B", 1), ("N", 1), 4))
+    b, n, dev = rois.size(0), rois.size(1), rois.device
+    gt_boxes = checked(who, "gt_boxes", gt_boxes, _F32, ("M", 4))
+    gt_off = checked(who, "gt_off", gt_off, _I32, (b + 1,), hint=f" for {b} images of rois")
+    m = gt_boxes.size(0)
+    gt_class_ids = checked(who, "gt_class_ids", gt_class_ids, _I32, (m,))
+    keys = checked(who, "keys", keys, _I32, (b, n))
+    count = int(count)
+    std = _target_std(who, std_dev)
+    c = max(count, 0)
+    spec = (("rois_out", _F32, (b, c, 4)), ("target_class_ids", _I32, (b, c)), ("target_deltas", _F32, (b, c, 4)),
+            ("roi_index", _I32, (b, c)), ("gt_index", _I32, (b, c)), ("num_pos", _I32, (b,)), ("num_neg", _I32, (b,)),
+            ("status", _I32, (b,)))
+    if out is not None and len(out) != len(spec):
+        raise RuntimeError(f"{who}: out must hold {len(spec)} tensors ({', '.join(s[0] for s in spec)}), got {len(out)}")
+    outs = tuple(checked_out(who, name, None if out is None else o, dtype, shape, dev) for (name, dtype, shape), o in zip(spec, out or spec))
+    _launch(lib.mrcnn_detection_targets,
+            (rois.data_ptr(), _ptr0(gt_boxes), _ptr0(gt_class_ids), gt_off.data_ptr(), keys.data_ptr(),
+             b, n, m, count, float(positive_ratio), float(pos_iou), float(crowd_iou), (ctypes.c_float * 4)(*std),
+             *[_ptr0(t) for t in outs], _stream()),
+            lambda: (0, (b, n, m), 20 * b * n + 20 * m + 44 * b * c, "detection_targets"))
+    return outs
+
+
+@_on_device
+def mask_targets(gt_masks: torch.Tensor, gt_off: torch.Tensor, rois_out: torch.Tensor, gt_index: torch.Tensor,
+                 num_pos: torch.Tensor, mask_shape=(28, 28), out: torch.Tensor | None = None) -> torch.Tensor:
+    """Step 7 of model.mrn_samples (model.py:491-507): for slot s < num_pos[b] of image b, CropFunction(mh, mw, 0) of mask row
+    gt_off[b] + gt_index[b,s] with box rois_out[b,s], then torch.round; zeros for every other slot → target_mask float32
+    [B,count,mh,mw]. gt_masks [M,H,W] uint8 / bool (the byte's value as a float) or float32, read in place through the index.
+    rois_out float32 [B,count,4], gt_index int32 [B,count], num_pos int32 [B] as detection_targets returns them. One launch, no
+    host synchronisation."""
+    who = "mask_targets"
+    gt_masks = checked(who, "gt_masks", gt_masks, (torch.uint8, torch.bool, _F32), ("M", "H", "W"))
+    rois_out = checked(who, "rois_out", rois_out, _F32, (("B", 1), "count", 4))
+    b, count, dev = rois_out.size(0), rois_out.size(1), rois_out.device
+    gt_off = checked(who, "gt_off", gt_off, _I32, (b + 1,))
+    gt_index = checked(who, "gt_index", gt_index, _I32, (b, count))
+    num_pos = checked(who, "num_pos", num_pos, _I32, (b,))
+    if len(mask_shape) != 2:
+        raise RuntimeError(f"{who}: mask_shape must be (height, width), got {tuple(mask_shape)}")
+    mh, mw = int(mask_shape[0]), int(mask_shape[1])
+    m, h, w = gt_masks.shape
+    out = checked_out(who, "target_mask", out, _F32, (b, count, max(mh, 0), max(mw, 0)), dev)
+    fn = lib.mrcnn_mask_targets_f32 if gt_masks.dtype == _F32 else lib.mrcnn_mask_targets_u8
+    _launch(fn, (_ptr0(gt_masks), m, h, w, gt_off.data_ptr(), b, count, _ptr0(rois_out), _ptr0(gt_index), num_pos.data_ptr(), mh, mw,
+                 _ptr0(out), _stream()),
+            lambda: (0, (b, count, mh * mw), 4 * b * count * mh * mw, "mask_targets"))
+    return out
+
+
+register("detection_targets(Tensor rois, Tensor gt_boxes, Tensor gt_class_ids, Tensor gt_off, Tensor keys, int count=100, "
+         "float positive_ratio=0.33, float[] std_dev=[0.1, 0.1, 0.2, 0.2], float pos_iou=0.5, float crowd_iou=0.001) -> "
+         "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)", detection_targets)   # `out` is the Python binding's
+register("mask_targets(Tensor gt_masks, Tensor gt_off, Tensor rois_out, Tensor gt_index, Tensor num_pos, "
+         "int[] mask_shape=[28, 28]) -> Tensor", mask_targets)
+
+
+# --------------------------------------------------------------------------------------------------
+# Training losses: the reference's five loss functions for a batch, forward and backward (csrc/losses.hip)
+# --------------------------------------------------------------------------------------------------
+def _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox):
+    """The four tensors both RPN loss ops read, on 16-byte boundaries (the kernels read float4 rows), and B, A, count."""
+    match = checked(who, "match", match, _I32, (("B", 1), ("A", 1)), align16=True)
+    b, a = match.shape
+    target_bbox = checked(who, "target_bbox", target_bbox, _F32, (b, ("count", 1), 4), align16=True)
+    return (match, checked(who, "logits", logits, _F32, (b, a, 2), align16=True),
+            checked(who, "pred_bbox", pred_bbox, _F32, (b, a, 4), align16=True), target_bbox, b, a, target_bbox.size(1))
+
+
+def _loss_grad_out(who, grad_out, counts, losses: int):
+    """grad_out float32 [losses] (the batch's mean) or [B,losses] (per image) → (grad_out, counts, per_image)."""
+    counts = checked(who, "counts", counts, _I32, ("B", losses), hint=" as the forward returned them")
+    per_image = isinstance(grad_out, torch.Tensor) and grad_out.dim() == 2
+    shape = (counts.size(0), losses) if per_image else (losses,)
+    return checked(who, "grad_out", grad_out, _F32, shape, hint=f" (or [{losses}]: the batch's mean)"), counts, per_image
+
+
+@_on_device
+def rpn_loss(match: torch.Tensor, logits: torch.Tensor, pred_bbox: torch.Tensor, target_bbox: torch.Tensor):
+    """RPN.class_loss and RPN.boxes_loss (model.py:652-718) for B images; the rule is stated at mrcnn_rpn_loss_forward in
+    include/maskrcnn_hip.h. match int32 [B,A] of -1 / 0 / 1, logits float32 [B,A,2], pred_bbox float32 [B,A,4], target_bbox float32
+    [B,count,4] as rpn_deltas wrote it → (sums float64 [B,2]: the class and box terms of each image, counts int32 [B,2]: the
+    anchors with match != 0 and 4 x the positives that have a target row, status int32 [B]: bit 0 = more than count positives,
+    chunk_pos int32 [B,chunks]: what rpn_loss_backward ranks the positives by). A loss is sums / counts, over the batch or per
+    image. Two launches, no host synchronisation."""
+    who = "rpn_loss"
+    match, logits, pred_bbox, target_bbox, b, a, count = _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox)
+    dev = match.device
+    sums = torch.empty(b, 2, dtype=torch.float64, device=dev)
+    counts = torch.empty(b, 2, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    chunk_pos = torch.empty(b, max(int(lib.mrcnn_rpn_loss_chunks(a)), 1), dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_rpn_loss_workspace_bytes(b, a, count))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_rpn_loss_forward,
+            (match.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(), target_bbox.data_ptr(), b, a, count, sums.data_ptr(),
+             counts.data_ptr(), status.data_ptr(), chunk_pos.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, a, count), 4 * b * a + 56 * b * count, "rpn_loss"))
+    return sums, counts, status, chunk_pos
+
+
+@_on_device
+def rpn_loss_backward(match: torch.Tensor, logits: torch.Tensor, pred_bbox: torch.Tensor, target_bbox: torch.Tensor,
+                      chunk_pos: torch.Tensor, counts: torch.Tensor, grad_out: torch.Tensor):
+    """The gradients of rpn_loss's two losses → (grad_logits float32 [B,A,2], grad_bbox float32 [B,A,4]), every element written,
+    +0 where an anchor does not contribute. counts and chunk_pos as rpn_loss returned them; grad_out float32 [2]: the upstream
+    gradients of (class loss, box loss) = batch sums / batch counts, or [B,2]: of each image's own sums / counts. One launch, no
+    host synchronisation."""
+    who = "rpn_loss_backward"
+    match, logits, pred_bbox, target_bbox, b, a, count = _rpn_loss_inputs(who, match, logits, pred_bbox, target_bbox)
+    chunk_pos = checked(who, "chunk_pos", chunk_pos, _I32, (b, max(int(lib.mrcnn_rpn_loss_chunks(a)), 1)), align16=True)
+    grad_out, counts, per_image = _loss_grad_out(who, grad_out, counts, 2)
+    grad_logits, grad_bbox = torch.empty_like(logits), torch.empty_like(pred_bbox)
+    _launch(lib.mrcnn_rpn_loss_backward,
+            (match.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(), target_bbox.data_ptr(), chunk_pos.data_ptr(),
+             counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, a, count, grad_logits.data_ptr(), grad_bbox.data_ptr(),
+             _stream()),
+            lambda: (0, (b, a, count), 28 * b * a, "rpn_loss_backward"))
+    return grad_logits, grad_bbox
+
+
+def _head_loss_inputs(who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks):
+    """The seven tensors both head loss ops read, on 16-byte boundaries, and B, count, C, mh, mw."""
+    ids = checked(who, "target_class_ids", target_class_ids, _I32, (("B", 1), ("count", 1)), align16=True)
+    b, count = ids.shape
+    target_mask = checked(who, "target_mask", target_mask, _F32, (b, count, "mh", "mw"), align16=True)
+    logits = checked(who, "logits", logits, _F32, (b, count, ("C", 1)), align16=True)
+    c, mh, mw = logits.size(2), target_mask.size(2), target_mask.size(3)
+    return (ids, checked(who, "num_rois", num_rois, _I32, (b,), align16=True),
+            checked(who, "target_deltas", target_deltas, _F32, (b, count, 4), align16=True), target_mask, logits,
+            checked(who, "pred_bbox", pred_bbox, _F32, (b, count, c, 4), align16=True),
+            checked(who, "pred_masks", pred_masks, _F32, (b, count, c, mh, mw), align16=True), b, count, c, mh, mw)
+
+
+@_on_device
+def head_loss(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_deltas: torch.Tensor, target_mask: torch.Tensor,
+              logits: torch.Tensor, pred_bbox: torch.Tensor, pred_masks: torch.Tensor):
+    """Classifier.class_loss, Classifier.boxes_loss and Mask.mask_loss (model.py:802-845, 922-953) for B images on the padded outputs
+    of detection_targets; the rule is stated at mrcnn_rpn_loss_forward in include/maskrcnn_hip.h. target_class_ids int32 [B,count],
+    num_rois int32 [B] (num_pos + num_neg: the slots past it never contribute), target_deltas float32 [B,count,4], target_mask
+    float32 [B,count,mh,mw], logits float32 [B,count,C], pred_bbox float32 [B,count,C,4], pred_masks float32 [B,count,C,mh,mw] →
+    (sums float64 [B,3]: class, box, mask; counts int32 [B,3]: the slots, 4 x the positive slots, mh x mw x the positive slots;
+    status int32 [B]: bit 1 = a class id outside 0 .. C-1, whose slot is skipped). Two launches, no host synchronisation."""
+    who = "head_loss"
+    ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
+        who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
+    dev = ids.device
+    sums = torch.empty(b, 3, dtype=torch.float64, device=dev)
+    counts = torch.empty(b, 3, dtype=torch.int32, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    nbytes = int(lib.mrcnn_head_loss_workspace_bytes(b, count))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_head_loss_forward,
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
+             pred_masks.data_ptr(), b, count, c, mh, mw, sums.data_ptr(), counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+             _stream()),
+            lambda: (0, (b, count, c), 4 * b * count * (c + 2 * mh * mw + 10), "head_loss"))
+    return sums, counts, status
+
+
+@_on_device
+def head_loss_backward(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_deltas: torch.Tensor, target_mask: torch.Tensor,
+                       logits: torch.Tensor, pred_bbox: torch.Tensor, pred_masks: torch.Tensor, counts: torch.Tensor,
+                       grad_out: torch.Tensor):
+    """The gradients of head_loss's three losses → (grad_logits, grad_bbox, grad_masks) in the predictions' shapes, every element
+    written: zeros but the contributing slots' logits rows, their class's box row and their class's mask plane. counts as
+    head_loss returned them; grad_out float32 [3] (batch mean) or [B,3] (per image), as for rpn_loss_backward. One launch, no host
+    synchronisation."""
+    who = "head_loss_backward"
+    ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
+        who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
+    grad_out, counts, per_image = _loss_grad_out(who, grad_out, counts, 3)
+    grad_logits, grad_bbox, grad_masks = torch.empty_like(logits), torch.empty_like(pred_bbox), torch.empty_like(pred_masks)
+    _launch(lib.mrcnn_head_loss_backward,
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
+             pred_masks.data_ptr(), counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, count, c, mh, mw,
+             grad_logits.data_ptr(), grad_bbox.data_ptr(), grad_masks.data_ptr(), _stream()),
+            lambda: (0, (b, count, c), 4 * b * count * c * (mh * mw + 5), "head_loss_backward"))
+    return grad_logits, grad_bbox, grad_masks
+
+
+register("rpn_loss(Tensor match, Tensor logits, Tensor pred_bbox, Tensor target_bbox) -> (Tensor, Tensor, Tensor, Tensor)", rpn_loss)
+register("rpn_loss_backward(Tensor match, Tensor logits, Tensor pred_bbox, Tensor target_bbox, Tensor chunk_pos, Tensor counts, "
+         "Tensor grad_out) -> (Tensor, Tensor)", rpn_loss_backward)
+register("head_loss(Tensor target_class_ids, Tensor num_rois, Tensor target_deltas, Tensor target_mask, Tensor logits, "
+         "Tensor pred_bbox, Tensor pred_masks) -> (Tensor, Tensor, Tensor)", head_loss)
+register("head_loss_backward(Tensor target_class_ids, Tensor num_rois, Tensor target_deltas, Tensor target_mask, Tensor logits, "
+         "Tensor pred_bbox, Tensor pred_masks, Tensor counts, Tensor grad_out) -> (Tensor, Tensor, Tensor)", head_loss_backward)
+

@@ -2,7 +2,7 @@
 the cocoeval route through them. Every comparison is exact (integer / byte work). References: tests/golden/codec.npz and rle.npz
 (the reference's own codec) and the numpy readers image.rle_counts / image.rle_decode / cocoeval._rle_area_bbox, which
 tests/test_codec_host.py pins to the same fixture. Outputs are pre-filled with a poison value where the test owns the buffers
-(the entry points are then called through the ctypes binding, as ops.py calls them)."""
+(the entry points are then called through the ctypes binding, as ops_coco.py calls them)."""
 import json
 
 import numpy as np
