@@ -53,7 +53,10 @@ inline const char* tuning_env(const char* name) {
 // ordered by its barriers and counted waits computes the same bits at any skew; one that is protected only by "the other
 // waves cannot be that far ahead" (round 5's conv3x3_wino4_f32: ten MFMA slots stood in for a barrier) goes wrong on every
 // launch instead of one in 5 000. tests/test_gpu_sync_fuzz.py runs the kernels' parity tests on such a build.
-// MRCNN_SYNC_FUZZ_POINT() follows the hand-written barriers (asm / __builtin_amdgcn_s_barrier); __syncthreads() is wrapped.
+// The fuzz points: __syncthreads(), __syncthreads_or(), __syncthreads_and() and __syncthreads_count() are wrapped by the macros
+// below; MRCNN_SYNC_FUZZ_POINT() follows every hand-written barrier (asm s_barrier / __builtin_amdgcn_s_barrier), in the same
+// statement, macro or body. A barrier of any other form is not fuzzed: tests/test_host.py reads the sources and refuses one,
+// and takes the set of wrapped names from the #define lines of this block.
 #ifdef MRCNN_SYNC_FUZZ
 namespace mrcnn {
 __device__ __forceinline__ void sync_fuzz_point() {
@@ -85,9 +88,29 @@ __device__ __forceinline__ void fuzzed_syncthreads() {
     __syncthreads();
     sync_fuzz_point();
 }
+// The voting barriers (HIP's __device__ inline functions, reached here under their own names: the macros come below). The
+// sleep follows the whole vote, so the waves leave it skewed as they leave a plain barrier.
+__device__ __forceinline__ int fuzzed_syncthreads_or(int predicate) {
+    const int r = __syncthreads_or(predicate);
+    sync_fuzz_point();
+    return r;
+}
+__device__ __forceinline__ int fuzzed_syncthreads_and(int predicate) {
+    const int r = __syncthreads_and(predicate);
+    sync_fuzz_point();
+    return r;
+}
+__device__ __forceinline__ int fuzzed_syncthreads_count(int predicate) {
+    const int r = __syncthreads_count(predicate);
+    sync_fuzz_point();
+    return r;
+}
 }  // namespace mrcnn
 #define MRCNN_SYNC_FUZZ_POINT() ::mrcnn::sync_fuzz_point()
 #define __syncthreads() ::mrcnn::fuzzed_syncthreads()
+#define __syncthreads_or(predicate) ::mrcnn::fuzzed_syncthreads_or(predicate)
+#define __syncthreads_and(predicate) ::mrcnn::fuzzed_syncthreads_and(predicate)
+#define __syncthreads_count(predicate) ::mrcnn::fuzzed_syncthreads_count(predicate)
 #else
 #define MRCNN_SYNC_FUZZ_POINT() ((void)0)
 #endif

@@ -40,6 +40,33 @@ def test_full_size_and_pipeline_tests_pass_under_schedule_fuzzing():
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1500:]
 
 
+# The barrier-heavy non-conv kernels (rle, codec, overlay, targets, detection_targets, losses, and select's edge paths) and the
+# scans, sorts and reductions of csrc/workgroup.hpp under them: group -> (files, tests left out, the child's time limit in s).
+# Left out: the multi-gigabyte offset tests and the tests that start further processes or load the whole model; the small
+# cases that stay reach the same kernels. The time limits are four times the wall time measured on the fuzzed library, rounded
+# up to 30 s: masks 8.1 s (7.3 s on the product library), training 6.4 s (5.9 s), refine 6.0 s (5.4 s), mostly start-up.
+FUZZED_FAMILIES = {
+    "masks": (("test_gpu_rle.py", "test_gpu_codec.py", "test_gpu_blend.py"),
+              ("cli", "detect_rle", "largest_mask", "schedule_fuzzing"), 60),
+    "training": (("test_gpu_targets.py", "test_gpu_detection_targets.py", "test_gpu_losses.py"),
+                 ("offsets_above_2_to_31", "schedule_fuzzing"), 30),
+    "refine": (("test_gpu_refine_edges.py",), ("row_longer_than_2_to_31", "schedule_fuzzing"), 30),
+}
+
+
+@pytest.mark.skipif(os.environ.get("MRCNN_SYNC_FUZZ_CHILD") == "1", reason="this IS the fuzzed child run")
+@pytest.mark.parametrize("group", list(FUZZED_FAMILIES))
+def test_mask_training_and_refine_kernel_tests_pass_under_schedule_fuzzing(group):
+    """One child pytest per group of files on the fuzzed library: every __syncthreads / __syncthreads_or of these kernels and of
+    the workgroup.hpp routines they call is followed by the random sleep, so a hand-off that a barrier does not order (two uses
+    of one `red` array, a write to the LDS that chunked_exclusive_scan was still reading) fails its golden comparison here."""
+    files, left_out, limit = FUZZED_FAMILIES[group]
+    r = subprocess.run([sys.executable, "-m", "pytest", *("tests/" + f for f in files), "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider",
+                        "-k", " and ".join("not " + k for k in left_out)], cwd=ROOT, env=_env(), capture_output=True, text=True,
+                       timeout=limit)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1500:]
+
+
 @pytest.mark.skipif(os.environ.get("MRCNN_SYNC_FUZZ_CHILD") == "1", reason="this IS the fuzzed child run")
 def test_fuzzing_finds_round5_kernel():
     """The detector detects: the same build with the barrier behind the prologue's operand reads left out (MRCNN_W4_DEBUG=8192,

@@ -465,3 +465,255 @@ def test_w4_forensics_decomposition_identifies_synthesised_causes(tmp_path):
     assert all(cb["A_operand_fit"]["k_tile"] == 40 and cb["V_used"]["best_other_k_tile"]["k_tile"] == 38 for cb in b["components"])
     assert c["positions"] == [8, 9, 10, 11] and c["rounds"] == [1] and c["single_component_fit"]["component"] == [1, 1]
     assert "M_replaced" in c["components"][0]
+
+
+# ------------------------------------------------------------------------------------------------ barriers and schedule fuzzing
+CSRC = os.path.join(ROOT, "maskrcnn_amd", "csrc")
+_COMMON = "common.hpp"
+
+
+def _strip_comments(text):
+    """C++ source with comments, character literals and the escapes inside string literals blanked (an asm string's
+    "\\n\\ts_barrier" reads "    s_barrier"); every newline stays, so an offset still gives the line."""
+    out, i, n, state = [], 0, len(text), "code"
+    while i < n:
+        c, two = text[i], text[i:i + 2]
+        if state == "code":
+            if two == "//":
+                state = "line"
+            elif two == "/*":
+                state, c = "block", "  "
+                i += 1
+            elif c == '"':
+                state = "string"
+            elif c == "'":
+                state = "char"
+            out.append(c if state in ("code", "string", "char") else " " * len(c))
+        elif state == "line":
+            if c == "\n":
+                state = "code"
+            out.append("\n" if c == "\n" else " ")
+        elif state == "block":
+            if two == "*/":
+                state, c = "code", "  "
+                i += 1
+            out.append(c if c == "\n" else " " * len(c))
+        else:   # string / char
+            if c == "\\" and i + 1 < n and text[i + 1] != "\n":
+                out.append("  ")
+                i += 2
+                continue
+            if (c == '"' and state == "string") or (c == "'" and state == "char") or c == "\n":
+                state = "code"
+                out.append(c)
+            else:
+                out.append(c if state == "string" else " ")
+        i += 1
+    return "".join(out)
+
+
+def _line(text, pos):
+    return text.count("\n", 0, pos) + 1
+
+
+def _body(text, open_brace):
+    """(start, end) of the text between the brace at `open_brace` and its partner."""
+    depth = 0
+    for i in range(open_brace, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            return open_brace + 1, i
+    return open_brace + 1, len(text)
+
+
+def _fuzz_wrappers(common):
+    """What common.hpp's MRCNN_SYNC_FUZZ block wraps: ({wrapped barrier name: span of its wrapper function's body}, the spans
+    of the wrapping #define lines, end of the block, problems). A wrapper counts when its `#define __syncthreads...(args)`
+    expands to a function of that block which calls the barrier of that name and then sync_fuzz_point()."""
+    import re
+    problems = []
+    m = re.search(r"^[ \t]*#[ \t]*ifdef[ \t]+MRCNN_SYNC_FUZZ[ \t]*$", common, re.M)
+    if not m:
+        return {}, [], 0, [f"{_COMMON}: no `#ifdef MRCNN_SYNC_FUZZ` block"]
+    e = re.compile(r"^[ \t]*#[ \t]*(else|endif|if|ifdef|ifndef|elif)\b", re.M).search(common, m.end())
+    if not e or e.group(1) != "else":
+        return {}, [], m.end(), [f"{_COMMON}:{_line(common, m.end())}: the MRCNN_SYNC_FUZZ block must run straight to its #else"]
+    lo, hi = m.end(), e.start()
+    block = common[lo:hi]
+    point = re.search(r"^[ \t]*#[ \t]*define[ \t]+MRCNN_SYNC_FUZZ_POINT\(\)[ \t]+(.*)$", block, re.M)
+    if not point or not re.search(r"\bsync_fuzz_point\(\)", point.group(1)):
+        problems.append(f"{_COMMON}: the fuzz build's MRCNN_SYNC_FUZZ_POINT() does not expand to sync_fuzz_point()")
+    wrapped, defines = {}, []
+    for d in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(__syncthreads\w*)\(([^)]*)\)[ \t]+(.*)$", block, re.M):
+        name, where = d.group(1), f"{_COMMON}:{_line(common, lo + d.start())}"
+        defines.append((lo + d.start(), lo + d.end()))
+        fn = re.fullmatch(r"::mrcnn::(\w+)\(([^)]*)\)\s*", d.group(3))
+        if not fn or fn.group(2).strip() != d.group(2).strip():
+            problems.append(f"{where}: `#define {name}` does not expand to one ::mrcnn:: wrapper call with the same arguments")
+            continue
+        f = re.search(r"\b%s[ \t]*\([^)]*\)\s*\{" % re.escape(fn.group(1)), block[:d.start()])
+        if not f:
+            problems.append(f"{where}: {fn.group(1)}() is not defined in the block in front of `#define {name}`")
+            continue
+        b0, b1 = _body(block, f.end() - 1)
+        call = re.search(r"\b%s[ \t]*\(" % re.escape(name), block[b0:b1])
+        if not call or not re.search(r"\bsync_fuzz_point\(\)", block[b0 + call.end():b1]):
+            problems.append(f"{where}: {fn.group(1)}() does not call {name}() and then sync_fuzz_point()")
+            continue
+        wrapped[name] = (lo + b0, lo + b1)
+    return wrapped, defines, hi, problems
+
+
+def _fuzz_point_follows(text, pos):
+    """MRCNN_SYNC_FUZZ_POINT() behind the barrier at `pos`: in the same macro body when the barrier stands in a #define, else
+    up to the end of the third line after it; never past the closing brace of the body the barrier stands in."""
+    start = text.rfind("\n", 0, pos) + 1
+    while start > 0 and text[:start - 1].rstrip(" \t").endswith("\\"):
+        start = text.rfind("\n", 0, start - 1) + 1
+    if text[start:pos].lstrip().startswith("#"):
+        end = start
+        while True:   # the logical line of the macro
+            nl = text.find("\n", end)
+            end = len(text) if nl < 0 else nl
+            if nl < 0 or not text[start:end].rstrip(" \t").endswith("\\"):
+                break
+            end += 1
+    else:
+        end = pos
+        for _ in range(4):
+            nl = text.find("\n", end)
+            end = len(text) if nl < 0 else nl + 1
+    in_string = text.count('"', text.rfind("\n", 0, pos) + 1, pos) % 2 == 1
+    depth, i = 0, pos
+    while i < end:
+        c = text[i]
+        if c == '"':
+            in_string = not in_string
+        elif not in_string:
+            depth += {"{": 1, "}": -1}.get(c, 0)
+            if depth < 0:
+                return False
+            if text.startswith("MRCNN_SYNC_FUZZ_POINT()", i):
+                return True
+        i += 1
+    return False
+
+
+def _barrier_audit(csrc):
+    """Every workgroup barrier of csrc/*.hip and *.hpp must be a point at which the -DMRCNN_SYNC_FUZZ build sleeps. Returns the
+    problems as 'file:line: ...' strings (none when all is well) and the number of barriers seen."""
+    import re
+    texts = {f: _strip_comments(open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))
+             if f.endswith((".hip", ".hpp"))}
+    if _COMMON not in texts:
+        return [f"{_COMMON} is missing"], 0
+    wrapped, defines, block_end, problems = _fuzz_wrappers(texts[_COMMON])
+    names = ", ".join(sorted(wrapped)) or "nothing"
+    token = re.compile(r"(?<!\w)(__syncthreads\w*|__builtin_amdgcn_s_barrier\w*|s_barrier\w*"
+                       r"|__barrier|__work_group_barrier|work_group_barrier|__ockl_wgred_\w+|cooperative_groups)(?!\w)")
+    includes = {f: [(m.group(1), m.start()) for m in re.finditer(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', t, re.M)]
+                for f, t in texts.items()}
+
+    def reaches_common(f, seen):
+        if f == _COMMON:
+            return True
+        seen.add(f)
+        return any(g in texts and g not in seen and reaches_common(g, seen) for g, _ in includes[f])
+
+    seen_barriers = 0
+    for f, t in texts.items():
+        first = None
+        for m in token.finditer(t):
+            name, where = m.group(1), f"{f}:{_line(t, m.start())}"
+            if f == _COMMON and m.start() < block_end:
+                inside = name in wrapped and wrapped[name][0] <= m.start() < wrapped[name][1]
+                if not inside and not any(a <= m.start() < b for a, b in defines):
+                    problems.append(f"{where}: {name} is defined or used in front of the fuzz wrappers")
+                continue
+            if re.match(r"[ \t]*#[ \t]*(define|undef)[ \t]+$", t[t.rfind("\n", 0, m.start()) + 1:m.start()]):
+                problems.append(f"{where}: {name} is redefined outside {_COMMON}'s MRCNN_SYNC_FUZZ block")
+                continue
+            seen_barriers += 1
+            first = m.start() if first is None else first
+            if name.startswith("__syncthreads"):
+                if name not in wrapped:
+                    problems.append(f"{where}: {name}( is a workgroup barrier that {_COMMON}'s MRCNN_SYNC_FUZZ block does not "
+                                    f"wrap (it wraps {names}): no fuzz point follows it")
+            elif name in ("__builtin_amdgcn_s_barrier", "s_barrier"):
+                if not _fuzz_point_follows(t, m.start()):
+                    problems.append(f"{where}: hand-written {name} without MRCNN_SYNC_FUZZ_POINT() in the same statement, "
+                                    "macro body or the next three lines of its body")
+            else:
+                problems.append(f"{where}: {name} is a barrier form that the fuzz build does not know")
+        if first is not None and f != _COMMON:
+            if not reaches_common(f, set()):
+                problems.append(f'{f}:{_line(t, first)}: a barrier, but the file does not reach {_COMMON} through its #include "..." lines')
+            elif not any(pos < first and g in texts and reaches_common(g, set()) for g, pos in includes[f]):
+                problems.append(f"{f}:{_line(t, first)}: a barrier in front of the #include that leads to {_COMMON}")
+    return problems, seen_barriers
+
+
+def test_every_workgroup_barrier_is_a_schedule_fuzz_point():
+    """The -DMRCNN_SYNC_FUZZ build (csrc/common.hpp, tests/test_gpu_sync_fuzz.py) finds a missing barrier only where the existing
+    ones are fuzz points. Read off the sources, comments stripped: (a) every file with a barrier reaches common.hpp through its
+    quoted includes, in front of its first barrier; (b) every barrier is of a fuzzed form — a `__syncthreads...(` that common.hpp's
+    MRCNN_SYNC_FUZZ block wraps (the set is parsed from that block's #define lines, each checked to call the barrier and then
+    sync_fuzz_point()), or a hand-written s_barrier / __builtin_amdgcn_s_barrier with MRCNN_SYNC_FUZZ_POINT() behind it; (c) nothing
+    in common.hpp names a barrier in front of the wrappers, and no file redefines one."""
+    problems, seen = _barrier_audit(CSRC)
+    assert not problems, "%d barrier(s) that the schedule-fuzzing build does not fuzz:\n%s" % (len(problems), "\n".join(problems))
+    assert seen > 100, f"only {seen} barriers found under {CSRC}: the audit no longer reads the kernels"
+
+
+def test_barrier_audit_names_an_unwrapped_form_a_bare_barrier_and_a_missing_include(tmp_path):
+    """The audit above on a small tree with one defect of each kind, and on common.hpp with a wrapper taken out."""
+    import re
+    import shutil
+    common = open(os.path.join(CSRC, _COMMON)).read()
+    good = ('#include "mid.hpp"\n__global__ void k(int* p) {\n    __shared__ int s;\n    __syncthreads();\n'
+            '    asm volatile("s_waitcnt lgkmcnt(0)\\n\\ts_barrier" ::: "memory");\n    MRCNN_SYNC_FUZZ_POINT();\n'
+            '    // __syncthreads_xor(1); s_barrier in a comment\n}\n'
+            '#define B() do { __builtin_amdgcn_s_barrier(); MRCNN_SYNC_FUZZ_POINT(); } while (0)\n')
+
+    def audit(files, common_text=common):
+        d = tmp_path / str(len(os.listdir(tmp_path)))
+        d.mkdir()
+        (d / _COMMON).write_text(common_text)
+        (d / "mid.hpp").write_text('#pragma once\n#include "common.hpp"\n')
+        for name, text in files.items():
+            (d / name).write_text(text)
+        return _barrier_audit(str(d))[0]
+
+    assert audit({"a.hip": good}) == []
+    got = audit({"a.hip": good.replace("__syncthreads();", "__syncthreads_xor(1);")})
+    assert len(got) == 1 and got[0].startswith("a.hip:4: __syncthreads_xor( is a workgroup barrier"), got
+    got = audit({"a.hip": good.replace("    MRCNN_SYNC_FUZZ_POINT();\n", "")})
+    assert len(got) == 1 and got[0].startswith("a.hip:5: hand-written s_barrier without"), got
+    # the fuzz point of the NEXT function does not count
+    got = audit({"a.hip": good.replace('"memory");\n', '"memory");\n}\nvoid g() {\n')})
+    assert len(got) == 1 and got[0].startswith("a.hip:5: hand-written s_barrier without"), got
+    got = audit({"a.hip": good.replace("MRCNN_SYNC_FUZZ_POINT(); } while", "} while")})
+    assert len(got) == 1 and got[0].startswith("a.hip:9: hand-written __builtin_amdgcn_s_barrier without"), got
+    got = audit({"a.hip": good.replace('#include "mid.hpp"\n', "\n")})
+    assert len(got) == 1 and "does not reach common.hpp" in got[0], got
+    got = audit({"a.hip": good + "#undef __syncthreads\n"})
+    assert len(got) == 1 and got[0].startswith("a.hip:10: __syncthreads is redefined"), got
+    got = audit({"a.hip": good}, common.replace("#ifdef MRCNN_SYNC_FUZZ\n", "inline void f() { __syncthreads(); }\n#ifdef MRCNN_SYNC_FUZZ\n", 1))
+    assert len(got) == 1 and "in front of the fuzz wrappers" in got[0], got
+    # a wrapper that no longer sleeps is no wrapper
+    got = audit({"a.hip": good}, re.sub(r"(__syncthreads\(\);\n)\s*sync_fuzz_point\(\);\n", r"\1", common, count=1))
+    assert any("does not call __syncthreads() and then sync_fuzz_point()" in g for g in got) and any(g.startswith("a.hip:4:") for g in got), got
+    # the real tree with each wrapper's #define taken out in turn: every site of that form is named, and beside them only the
+    # wrapper function that common.hpp is left with
+    wrappers = re.findall(r"^#define (__syncthreads\w*)\(", common, re.M)
+    assert "__syncthreads" in wrappers
+    for name in wrappers:
+        d = tmp_path / ("without" + name)
+        shutil.copytree(CSRC, d, ignore=shutil.ignore_patterns("build"))
+        (d / _COMMON).write_text(re.sub(r"^#define %s\(.*\n" % re.escape(name), "", common, count=1, flags=re.M))
+        got = _barrier_audit(str(d))[0]
+        sites = sum(len(re.findall(r"(?<!\w)%s\(" % re.escape(name), _strip_comments(open(os.path.join(CSRC, f)).read())))
+                    for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp")))
+        own = len(re.findall(r"(?<!\w)%s\(" % re.escape(name), _strip_comments(common)))
+        named = [g for g in got if f": {name}( is a workgroup barrier" in g]
+        assert got and len(named) == sites - own and all(g in named or g.startswith(_COMMON + ":") for g in got), (name, sites, own, got)
