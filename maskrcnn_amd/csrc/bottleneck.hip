@@ -504,13 +504,6 @@ extern "C" int mrcnn_bottleneck_fused_f32(const float* x, int32_t batch, int32_t
     p.w1_bytes = static_cast<unsigned>(4LL * P * cin);
     p.u2_bytes = static_cast<unsigned>(4LL * 16 * P * P);
     p.w3_bytes = static_cast<unsigned>(4LL * CO * P);
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck_fused_f32), FUSED_LDS, "bottleneck_fused"))
-        return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "bottleneck_fused: cannot query the device");
-    const int ncu = cus >= 8 ? (cus / 8) * 8 : 8;
-    const int virt = 8 * ((p.total + 7) / 8);
-    const int grid = virt < ncu ? virt : ncu;
-    hipLaunchKernelGGL(bottleneck_fused_f32, dim3(grid), dim3(512), FUSED_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("bottleneck_fused_f32");
+    return mrcnn::launch_one_per_cu(bottleneck_fused_f32, 8 * ((p.total + 7) / 8), 512, FUSED_LDS, mrcnn::as_stream(stream),
+                                    "bottleneck_fused", "bottleneck_fused_f32", p);
 }

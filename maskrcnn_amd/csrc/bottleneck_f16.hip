@@ -450,16 +450,9 @@ extern "C" int mrcnn_bottleneck_c2_f16(const void* x_f16, int32_t batch, int32_t
     p.tiles = batch * p.tiles_x * p.tiles_y;
     p.x_bytes = static_cast<unsigned>(static_cast<long long>(batch) * height * width * cin * 2);
     p.y_bytes = static_cast<unsigned>(static_cast<long long>(batch) * height * width * 256 * 2);
-    const int cus = mrcnn::device_cu_count() > 0 ? mrcnn::device_cu_count() : 256;
+    int cus;
+    if (int rc = mrcnn::query_cus("bottleneck_c2_f16", cus)) return rc;
     const int per_xcd = std::max(1, std::min(cus / 8, (p.tiles + 7) / 8));
-    const dim3 grid(8 * per_xcd);
-    hipStream_t s = mrcnn::as_stream(stream);
-    if (wd_frags) {
-        if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck_c2_f16<true>), LDS_BYTES, "bottleneck_c2_f16")) return rc;
-        hipLaunchKernelGGL((bottleneck_c2_f16<true>), grid, dim3(512), LDS_BYTES, s, p);
-    } else {
-        if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck_c2_f16<false>), LDS_BYTES, "bottleneck_c2_f16")) return rc;
-        hipLaunchKernelGGL((bottleneck_c2_f16<false>), grid, dim3(512), LDS_BYTES, s, p);
-    }
-    return mrcnn::check_launch("bottleneck_c2_f16");
+    return mrcnn::launch_kernel(wd_frags ? bottleneck_c2_f16<true> : bottleneck_c2_f16<false>, 8 * per_xcd, 512, LDS_BYTES,
+                                mrcnn::as_stream(stream), "bottleneck_c2_f16", "bottleneck_c2_f16", p);
 }

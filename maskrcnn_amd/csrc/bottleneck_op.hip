@@ -9,7 +9,7 @@
 // i.e. two launches for the ResNet C2 blocks (three with a downsample branch), three (four) elsewhere. The plan is a function
 // of the block's shape PER IMAGE and of which conv2 transforms the caller supplies — never of the batch: image i of a batch equals
 // image i alone bit for bit. Every intermediate lives in the caller's workspace; nothing is allocated or synchronised here.
-#include "common.hpp"
+#include "conv_common.hpp"
 
 namespace {
 
@@ -23,9 +23,6 @@ struct Plan {
     size_t res_off, h_off, h2_off, total;
 };
 
-// tiles of 16 x 32 output pixels per image: the F(4x4) kernel's M tiles (the rule modules.py applies to every F(4x4) layer)
-inline int wino4_tiles_per_image(int h, int w) { return ((h / 4 + 3) / 4) * ((w / 4 + 7) / 8); }
-
 Plan make_plan(int batch, int height, int width, int cin, int planes, int stride, bool has_ds, bool have_u2, bool have_u4,
                int min_tiles4, bool fuse_conv3) {
     Plan p{};
@@ -34,7 +31,7 @@ Plan make_plan(int batch, int height, int width, int cin, int planes, int stride
     p.m = 1LL * batch * p.oh * p.ow;
     const bool even = p.oh % 2 == 0 && p.ow % 2 == 0 && planes % 8 == 0;
     p.use4 = have_u4 && have_u2 && even && mrcnn_conv3x3_winograd4_supported(batch, p.oh, p.ow, planes, planes) &&
-             wino4_tiles_per_image(p.oh, p.ow) >= min_tiles4;
+             mrcnn_conv::wino4_tiles_per_image(p.oh, p.ow) >= min_tiles4;   // the F(4x4) kernel's M tiles per image
     p.use2 = !p.use4 && have_u2 && even;
     p.fused3 = p.use4 && fuse_conv3 && planes == 64;
     size_t off = 0;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -33,6 +34,41 @@ constexpr int kWave = 64;  // gfx950 wavefront
 //   device_cu_count:    multiProcessorCount of the current device (persistent-grid sizing), 0 on failure.
 int ensure_dynamic_lds(const void* kernel, size_t lds_bytes, const char* who);
 int device_cu_count();
+
+// The launch tail every persistent launcher shares. Each launcher keeps its own grid rule (they differ for measured reasons,
+// stated at each site); what they share is the device query, the XCD rounding and the grant / launch / check sequence.
+//   query_cus:     the CU count of the current device, or THE answer to a failed query: MRCNN_ERR_LAUNCH,
+//                  "<who>: cannot query the device";
+//   whole_xcds:    CUs rounded down to whole XCDs (8 per device), so every XCD runs the same number of persistent workgroups;
+//   launch_kernel: ensure_dynamic_lds, the launch through a kernel function pointer, check_launch. `who` names the entry point
+//                  (error prefix of the LDS grant), `kernel_name` the kernel (error prefix of the launch check);
+//   launch_one_per_cu: the three together for the grid rule min(units, whole_xcds(CUs)).
+inline int query_cus(const char* who, int& cus) {
+    cus = device_cu_count();
+    return cus > 0 ? MRCNN_OK : fail(MRCNN_ERR_LAUNCH, "%s: cannot query the device", who);
+}
+inline int whole_xcds(int cus) { return cus >= 8 ? (cus / 8) * 8 : 8; }
+
+template <typename P>
+struct kernel_arg {  // keeps launch_kernel's last parameter out of deduction: a derived parameter block converts to the kernel's
+    using type = P;
+};
+template <typename P>
+int launch_kernel(void (*kern)(P), long long grid, int threads, size_t lds_bytes, hipStream_t stream, const char* who,
+                  const char* kernel_name, const typename kernel_arg<P>::type& p) {
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_bytes, who)) return rc;
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(threads), lds_bytes, stream, p);
+    return check_launch(kernel_name);
+}
+// The grid rule of the Winograd and fused-Bottleneck kernels: one workgroup per CU of the whole XCDs, fewer when there are
+// fewer `units` of work; a workgroup walks the units beyond its own.
+template <typename P>
+int launch_one_per_cu(void (*kern)(P), long long units, int threads, size_t lds_bytes, hipStream_t stream, const char* who,
+                      const char* kernel_name, const typename kernel_arg<P>::type& p) {
+    int cus;
+    if (int rc = query_cus(who, cus)) return rc;
+    return launch_kernel(kern, std::min<long long>(units, whole_xcds(cus)), threads, lds_bytes, stream, who, kernel_name, p);
+}
 
 // Tuning switches of the launch paths (tile overrides, kernel A/B routes): environment variables honoured ONLY in -DMRCNN_TUNING
 // builds (`build.py --variant tuning -DMRCNN_TUNING`, which tools/ load through MRCNN_LIB); the product library ignores them —

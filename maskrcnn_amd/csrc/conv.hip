@@ -500,14 +500,11 @@ __global__ __launch_bounds__(256, 2) void conv_pw_stream_f32(const ConvParams p)
 template <int KC, int TN, int TNP>
 int launch_pw_stream(ConvParams p, hipStream_t stream) {
     constexpr size_t lds = sizeof(float) * 32 * TN * (KC * 8 + 4);
-    auto kern = conv_pw_stream_f32<KC, TN, TNP>;
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "conv_pw_stream")) return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv_pw_stream: no device");
+    int cus;
+    if (int rc = mrcnn::query_cus("conv_pw_stream", cus)) return rc;
     const int nblocks = (p.M + 31) / 32;
     const int grid = std::min(2 * cus, (nblocks + 3) / 4);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(256), lds, stream, p);
-    return mrcnn::check_launch("conv_pw_stream_f32");
+    return mrcnn::launch_kernel(conv_pw_stream_f32<KC, TN, TNP>, grid, 256, lds, stream, "conv_pw_stream", "conv_pw_stream_f32", p);
 }
 
 // K >= this and one of the three tiles the long-K layers take (128x128 BK32, 128x64 BK16, 128x32 BK32), aligned-tap or
@@ -522,24 +519,18 @@ constexpr bool split_tile() {
 template <int BM, int BN, int WM, int WN, int BK>
 int launch_conv(ConvParams p, int mode, hipStream_t stream) {  // mode: 0 aligned taps, 1 generic, 2 pointwise
     const bool generic = mode == 1;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.Cout + BN - 1) / BN;
-    const long long grid = tile_grid(p);
-    if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: grid too large");
+    long long grid;
+    if (int rc = set_tile_grid<BM, BN>(p, "conv", grid)) return rc;
     constexpr size_t lds = conv_lds_bytes<BM, BN, BK>();
     const int res = epilogue_variant(p, p.w_head != nullptr);
-    auto go = [&](auto kern) -> int {
-        if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "conv")) return rc;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(256), lds, stream, p);
-        return MRCNN_OK;
-    };
-    int rc;
+    const char* name = "conv_igemm_f32";  // what a failed launch is reported as
+    auto go = [&](auto kern) -> int { return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv", name, p); };
 #ifdef MRCNN_ABLATIONS
     if constexpr (BM == 128 && BN == 128 && WM == 2 && WN == 2 && BK == 32) {
         if (res == 5) {
             if (generic) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: fused heads need Cin %% 32 == 0");
-            if ((rc = go(conv_igemm_f32<BM, BN, WM, WN, BK, 0, 5>))) return rc;
-            return mrcnn::check_launch("conv_igemm_f32<heads>");
+            name = "conv_igemm_f32<heads>";
+            return go(conv_igemm_f32<BM, BN, WM, WN, BK, 0, 5>);
         }
     }
 #else
@@ -555,9 +546,8 @@ int launch_conv(ConvParams p, int mode, hipStream_t stream) {  // mode: 0 aligne
                      : res == 1 ? go(conv_igemm_f32<BM, BN, WM, WN, BK, MD, 1, true>)
                                 : go(conv_igemm_f32<BM, BN, WM, WN, BK, MD, 2, true>);
             };
-            rc = mode == 2 ? by_res_split(std::integral_constant<int, 2>{}) : by_res_split(std::integral_constant<int, 0>{});
-            if (rc) return rc;
-            return mrcnn::check_launch("conv_igemm_f32<split>");
+            name = "conv_igemm_f32<split>";
+            return mode == 2 ? by_res_split(std::integral_constant<int, 2>{}) : by_res_split(std::integral_constant<int, 0>{});
         }
     }
     auto by_res = [&](auto mode_tag) -> int {
@@ -568,11 +558,9 @@ int launch_conv(ConvParams p, int mode, hipStream_t stream) {  // mode: 0 aligne
              : res == 3 ? go(conv_igemm_f32<BM, BN, WM, WN, BK, MD, 3>)
                         : go(conv_igemm_f32<BM, BN, WM, WN, BK, MD, 4>);
     };
-    rc = mode == 1 ? by_res(std::integral_constant<int, 1>{})
-       : mode == 2 ? by_res(std::integral_constant<int, 2>{})
-                   : by_res(std::integral_constant<int, 0>{});
-    if (rc) return rc;
-    return mrcnn::check_launch("conv_igemm_f32");
+    return mode == 1 ? by_res(std::integral_constant<int, 1>{})
+         : mode == 2 ? by_res(std::integral_constant<int, 2>{})
+                     : by_res(std::integral_constant<int, 0>{});
 }
 
 }  // namespace
@@ -637,11 +625,13 @@ static int run_conv_f32(const float* x, int32_t batch, int32_t height, int32_t w
     // The same tile when 128x128 tiles would not even give every CU one workgroup (P5 lateral at batch 8: 128 tiles; 131 ->
     // 94 us). Same products in the same order per output: the choice never changes a result.
     const long long tiles128 = ((p.M + 127) / 128) * static_cast<long long>((cout + 127) / 128);
-    const bool underfilled = cout >= 128 && tiles128 < mrcnn::device_cu_count();
+    int cus;
+    if (int rc = mrcnn::query_cus("conv", cus)) return rc;
+    const bool underfilled = cout >= 128 && tiles128 < cus;
     // ... and when even 128x64 tiles give a CU only one workgroup with a long K to walk alone (P5 lateral at batch 8: 256 tiles,
     // K = 2048: 0.104 ms at 0.56 of its MFMA floor), 128x32 tiles put two on every CU: 0.072 ms (MRCNN_CONV_TILE=5: 128x64)
     if (!generic && force == 0 && underfilled && p.K >= 1024 &&
-        ((p.M + 127) / 128) * static_cast<long long>((cout + 63) / 64) <= mrcnn::device_cu_count())
+        ((p.M + 127) / 128) * static_cast<long long>((cout + 63) / 64) <= cus)
         return launch_conv<128, 32, 4, 1, 32>(p, mode, s);
     if (!generic && force != 1 &&
         (force == 5 || underfilled || (p.K <= 256 && p.residual && p.res_div == 1 && cout >= 128)))

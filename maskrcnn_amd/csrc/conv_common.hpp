@@ -98,6 +98,21 @@ __device__ __forceinline__ bool tile_origin(const ConvCommon& p, int BM, int BN,
     return true;
 }
 inline long long tile_grid(const ConvCommon& p) { return 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n; }
+// Host: the BM x BN tiling of the GEMM and its launch grid (one workgroup per tile), refused past 2^31 - 1 workgroups.
+template <int BM, int BN>
+inline int set_tile_grid(ConvCommon& p, const char* who, long long& grid) {
+    p.tiles_m = (p.M + BM - 1) / BM;
+    p.tiles_n = (p.Cout + BN - 1) / BN;
+    grid = tile_grid(p);
+    if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "%s: grid too large", who);
+    return MRCNN_OK;
+}
+
+// Host: the M tiles of the F(4x4) Winograd kernel (conv_wino4.hip) — 16 x 32 output pixels, i.e. 4 x 8 blocks of 4 x 4 — per
+// image. modules.py applies the same rule to every F(4x4) layer.
+inline int wino4_tile_rows(int height) { return (height / 4 + 3) / 4; }
+inline int wino4_tile_cols(int width) { return (width / 4 + 7) / 8; }
+inline int wino4_tiles_per_image(int height, int width) { return wino4_tile_rows(height) * wino4_tile_cols(width); }
 
 // im2col bookkeeping of the PA tile rows a thread stages: element offset of pixel (b, iy0, ix0) and the
 // (iy0, ix0) themselves for the zero-padding predicate; rows beyond M can never be in range.

@@ -386,68 +386,54 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void conv_igemm
 
 template <int BM, int BN, int WM, int WN, int PRODUCTS>
 int launch(ConvParamsH p, bool generic, hipStream_t stream) {
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.Cout + BN - 1) / BN;
-    const long long grid = tile_grid(p);
-    if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16: grid too large");
+    long long grid;
+    if (int rc = set_tile_grid<BM, BN>(p, "conv_f16", grid)) return rc;
     constexpr size_t lds = lds_bytes<BM, BN, PRODUCTS>();
     const int res = epilogue_variant(p, false);
-    auto go = [&](auto kern) -> int {
-        if (int rc2 = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "conv_f16")) return rc2;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(256), lds, stream, p);
-        return MRCNN_OK;
-    };
-    int rc;
+    auto go = [&](auto kern) -> int { return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv_f16", "conv_igemm_f16", p); };
     if (generic)
-        rc = res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 0>)
-           : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 1>)
-           : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 2>)
-           : res == 3 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 3>)
-                      : go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 4>);
-    else
-        rc = res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 0>)
-           : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 1>)
-           : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 2>)
-           : res == 3 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 3>)
-                      : go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 4>);
-    if (rc) return rc;
-    return mrcnn::check_launch("conv_igemm_f16");
+        return res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 0>)
+             : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 1>)
+             : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 2>)
+             : res == 3 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 3>)
+                        : go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 4>);
+    return res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 0>)
+         : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 1>)
+         : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 2>)
+         : res == 3 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 3>)
+                    : go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, false, 4>);
 }
 
 // fp16 storage variants (PRODUCTS = 1). in16/out16 choose the instantiation; only the combinations the pipeline uses
 // exist: fp32 → fp16 (RES 0; the stem is GENERIC), fp16 → fp16 (RES 0, 1, 2, 4), fp16 → fp32 (RES 0, 3).
 template <int BM, int BN, int WM, int WN>
 int launch16(ConvParamsH p, bool generic, bool in16, bool out16, hipStream_t stream) {
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.Cout + BN - 1) / BN;
-    const long long grid = tile_grid(p);
-    if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16: grid too large");
+    long long grid;
+    if (int rc = set_tile_grid<BM, BN>(p, "conv_f16", grid)) return rc;
     constexpr size_t lds = lds_bytes<BM, BN, 1>();
     const int res = epilogue_variant(p, false);
     auto go = [&](auto kern) -> int {
-        if (int rc2 = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "conv_f16")) return rc2;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(256), lds, stream, p);
-        return MRCNN_OK;
+        return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv_f16", "conv_igemm_f16<io16>", p);
     };
-    int rc = MRCNN_ERR_UNSUPPORTED;
     if (!in16 && out16) {
         if (res != 0) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16: fp32 → fp16 supports no residual / sigmoid / scatter");
-        rc = generic ? go(conv_igemm_f16<BM, BN, WM, WN, 1, true, 0, false, true>)
-                     : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, false, true>);
-    } else if (in16 && out16) {
+        return generic ? go(conv_igemm_f16<BM, BN, WM, WN, 1, true, 0, false, true>)
+                       : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, false, true>);
+    }
+    if (in16 && out16) {
         if (generic || res == 3) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16: fp16 → fp16 needs Cin %% 32 == 0, no sigmoid");
-        rc = res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, true, true>)
-           : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 1, true, true>)
-           : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 2, true, true>)
-                      : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 4, true, true>);
-    } else if (in16 && !out16) {
+        return res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, true, true>)
+             : res == 1 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 1, true, true>)
+             : res == 2 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 2, true, true>)
+                        : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 4, true, true>);
+    }
+    if (in16 && !out16) {
         if (generic || !(res == 0 || res == 3))
             return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16: fp16 → fp32 needs Cin %% 32 == 0 and no residual / scatter");
-        rc = res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, true, false>)
-                      : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 3, true, false>);
+        return res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 0, true, false>)
+                        : go(conv_igemm_f16<BM, BN, WM, WN, 1, false, 3, true, false>);
     }
-    if (rc) return rc;
-    return mrcnn::check_launch("conv_igemm_f16<io16>");
+    return MRCNN_ERR_UNSUPPORTED;  // fp32 → fp32 is launch()'s
 }
 
 template <int PRODUCTS>

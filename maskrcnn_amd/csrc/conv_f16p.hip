@@ -465,34 +465,47 @@ int pick_rows(long long m, int cout, int cus) {
     return tmw;
 }
 
-template <int TMW, int NWT, bool RES>
+template <int TMW, int NWT, bool RES, bool HEADS = false>
 int launch_p8r(P8Params p, hipStream_t s) {
     using G = P8Geom<TMW, NWT>;
     p.tiles_m = (p.M + G::BM - 1) / G::BM;
     p.tiles_n = p.Cout / G::BN;
     const long long grid = 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n;
     if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16p: grid too large");
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(conv_f16p<TMW, NWT, RES>), G::LDS, "conv_f16p")) return rc;
-    hipLaunchKernelGGL((conv_f16p<TMW, NWT, RES>), dim3(static_cast<unsigned>(grid)), dim3(512), G::LDS, s, p);
-    return mrcnn::check_launch("conv_f16p");
-}
-
-template <int TMW>
-int launch_p8_heads(P8Params p, hipStream_t s) {
-    using G = P8Geom<TMW, 4>;
-    p.tiles_m = (p.M + G::BM - 1) / G::BM;
-    p.tiles_n = p.Cout / G::BN;
-    const long long grid = 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n;
-    if (grid > 0x7fffffffLL) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv_f16p: grid too large");
-    static_assert(8 * TMW * 16 * 128 <= G::LDS, "the partial head sums fit the operand buffers");
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(conv_f16p<TMW, 4, false, true>), G::LDS, "conv_f16p")) return rc;
-    hipLaunchKernelGGL((conv_f16p<TMW, 4, false, true>), dim3(static_cast<unsigned>(grid)), dim3(512), G::LDS, s, p);
-    return mrcnn::check_launch("conv_f16p<heads>");
+    static_assert(!HEADS || 8 * TMW * 16 * 128 <= G::LDS, "the partial head sums fit the operand buffers");
+    return mrcnn::launch_kernel(conv_f16p<TMW, NWT, RES, HEADS>, grid, 512, G::LDS, s, "conv_f16p",
+                                HEADS ? "conv_f16p<heads>" : "conv_f16p", p);
 }
 
 template <int TMW, int NWT>
 int launch_p8(const P8Params& p, hipStream_t s) {
     return p.residual ? launch_p8r<TMW, NWT, true>(p, s) : launch_p8r<TMW, NWT, false>(p, s);
+}
+
+// The one fill of P8Params, for a shape mrcnn_conv_f16_pipelined_supported has accepted: tensors, geometry, GEMM sizes and
+// byte ranges, with no residual (res_div 1) and no output or head pointer: the entry points set those.
+void fill_p8(P8Params& p, const void* x_f16, int batch, int height, int width, int cin, const void* w_f16, int cout, int kh,
+             int kw, int stride, int pad_top, int pad_left, int pad_bottom, int pad_right, const float* scale,
+             const float* shift, int activation) {
+    p = P8Params{};
+    p.x = static_cast<const _Float16*>(x_f16);
+    p.w = static_cast<const _Float16*>(w_f16);
+    p.scale = scale;
+    p.shift = shift;
+    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout; p.KH = kh; p.KW = kw; p.stride = stride;
+    p.pad_t = pad_top; p.pad_l = pad_left;
+    p.OH = (height + pad_top + pad_bottom - kh) / stride + 1;
+    p.OW = (width + pad_left + pad_right - kw) / stride + 1;
+    p.M = batch * p.OH * p.OW;
+    p.K = kh * kw * cin;
+    p.nk = p.K / 64;
+    p.relu = activation;
+    p.res_div = 1;
+    p.x_bytes = static_cast<unsigned>(static_cast<long long>(batch) * height * width * cin * 2);
+    p.w_bytes = static_cast<unsigned>(static_cast<long long>(cout) * p.K * 2);
+    p.x_bias = static_cast<unsigned>((pad_top * width + pad_left) * cin * 2);
+    p.y_elems = static_cast<unsigned>(static_cast<long long>(p.M) * cout);
+    p.r_elems = p.y_elems;
 }
 
 }  // namespace
@@ -527,36 +540,16 @@ extern "C" int mrcnn_conv_f16_pipelined(const void* x_f16, int32_t batch, int32_
                            "conv_f16_pipelined: needs Cin %% 64 == 0, Cout %% 64 == 0, <= 25 taps, 0 <= pads < kernel, "
                            "32-bit byte offsets (got %dx%dx%dx%d -> %d, %dx%d stride %d)", batch, height, width, cin, cout,
                            kh, kw, stride);
-    P8Params p{};
-    p.x = static_cast<const _Float16*>(x_f16);
-    p.w = static_cast<const _Float16*>(w_f16);
-    p.scale = scale;
-    p.shift = shift;
+    P8Params p;
+    fill_p8(p, x_f16, batch, height, width, cin, w_f16, cout, kh, kw, stride, pad_top, pad_left, pad_bottom, pad_right, scale, shift,
+            activation);
     p.residual = static_cast<const _Float16*>(residual_f16);
     p.y16 = static_cast<_Float16*>(y_f16);
     p.y32 = y_f32;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout; p.KH = kh; p.KW = kw; p.stride = stride;
-    p.pad_t = pad_top; p.pad_l = pad_left;
-    p.OH = (height + pad_top + pad_bottom - kh) / stride + 1;
-    p.OW = (width + pad_left + pad_right - kw) / stride + 1;
-    p.M = batch * p.OH * p.OW;
-    p.K = kh * kw * cin;
-    p.nk = p.K / 64;
-    p.relu = activation;
     p.res_div = residual_f16 ? res_div : 1;
     MRCNN_REQUIRE(p.res_div == 1 || (p.res_div == 2 && p.OH % 2 == 0 && p.OW % 2 == 0),
                   "conv_f16_pipelined: res_div must be 1, or 2 with even output sizes (got %d, %dx%d)", res_div, p.OH, p.OW);
-    p.x_bytes = static_cast<unsigned>(static_cast<long long>(batch) * height * width * cin * 2);
-    p.w_bytes = static_cast<unsigned>(static_cast<long long>(cout) * p.K * 2);
-    p.x_bias = static_cast<unsigned>((pad_top * width + pad_left) * cin * 2);
-    p.y_elems = static_cast<unsigned>(static_cast<long long>(p.M) * cout);
     p.r_elems = p.y_elems / static_cast<unsigned>(p.res_div * p.res_div);
-    // tile: 0 = automatic. Columns: 256 when Cout allows it — except for a short K (<= 256: the expansion layers) on a map
-    // with fewer than three 256 x 256 tiles per CU, where 128 x 128 at two workgroups per CU covers the prologue / epilogue
-    // better (C4 conv3 of configs[4]: 51.6 -> 49 us; C2 / C3 conv3 with 4-8 tiles per CU: the large tile wins) —, else 128 / 64.
-    // Rows: pick_rows for 256 columns, 128 otherwise.
-    const int cus = mrcnn::device_cu_count() > 0 ? mrcnn::device_cu_count() : 256;
-    const bool few_tiles = static_cast<long long>(p.M) * cout < 3LL * cus * 65536;
     // tuning (in-pipeline sweeps, read once per process): MRCNN_F16P_TILE="rows x cols[:Mmin-Mmax]" forces a tile for the automatic
     // choices (optionally only for layers with Mmin <= M <= Mmax), e.g. "192x256:30000-40000"
     struct ForcedTile {   // parsed once per process (a getenv per launch walks the whole environment)
@@ -576,16 +569,29 @@ extern "C" int mrcnn_conv_f16_pipelined(const void* x_f16, int32_t batch, int32_
             tile_cols = c;
         }
     }
-    int nwt = tile_cols ? tile_cols / 64 : (cout % 256 == 0 && !(p.K <= 256 && few_tiles)) ? 4 : (cout % 128 == 0 ? 2 : 1);
-    // Small maps (P5 / P6 of configs[4]: M = 8 736 / 2 184 rows): when even 128-row tiles of this width leave more than half the CUs
-    // without a workgroup, narrower tiles — two workgroups per CU — fill the chip (round 5, tools/f16_small_probe.py: P5 lateral
-    // 31.5 -> 23.0 us, P5 smoothing 33.5 -> 25.5, RPN P6 32.2 -> 23.0; layers with >= cus / 2 tiles are best where they are).
-    // The tile never changes a result (same operands, same k order per output element).
-    if (!tile_cols && !tile_rows) {
-        while (nwt > 1 && ((p.M + 127) / 128) * static_cast<long long>(cout / (64 * nwt)) < cus / 2) nwt >>= 1;
+    // Only the automatic choices need the CU count, and `cus` is read nowhere but in the two `if (!tile_...)` blocks below: a
+    // call that names both tile sizes is checked (and launched) without the query.
+    int cus = 0;
+    if (!tile_cols || !tile_rows)
+        if (int rc = mrcnn::query_cus("conv_f16_pipelined", cus)) return rc;
+    // tile: 0 = automatic. Columns: 256 when Cout allows it — except for a short K (<= 256: the expansion layers) on a map
+    // with fewer than three 256 x 256 tiles per CU, where 128 x 128 at two workgroups per CU covers the prologue / epilogue
+    // better (C4 conv3 of configs[4]: 51.6 -> 49 us; C2 / C3 conv3 with 4-8 tiles per CU: the large tile wins) —, else 128 / 64.
+    // Rows: pick_rows for 256 columns, 128 otherwise.
+    int nwt = tile_cols / 64;
+    if (!tile_cols) {
+        const bool few_tiles = static_cast<long long>(p.M) * cout < 3LL * cus * 65536;
+        nwt = (cout % 256 == 0 && !(p.K <= 256 && few_tiles)) ? 4 : (cout % 128 == 0 ? 2 : 1);
+        // Small maps (P5 / P6 of configs[4]: M = 8 736 / 2 184 rows): when even 128-row tiles of this width leave more than half the
+        // CUs without a workgroup, narrower tiles — two workgroups per CU — fill the chip (round 5, tools/f16_small_probe.py: P5
+        // lateral 31.5 -> 23.0 us, P5 smoothing 33.5 -> 25.5, RPN P6 32.2 -> 23.0; layers with >= cus / 2 tiles are best where they
+        // are). The tile never changes a result (same operands, same k order per output element).
+        if (!tile_rows)
+            while (nwt > 1 && ((p.M + 127) / 128) * static_cast<long long>(cout / (64 * nwt)) < cus / 2) nwt >>= 1;
     }
-    int tmw = tile_rows ? tile_rows / 32 : 0;
-    if (!tmw) tmw = nwt == 4 ? pick_rows(p.M, cout, cus) : 4;
+    // a named height is never replaced by a chosen one: one below 32 gives 0 here and fails the fit check, as any other misfit
+    int tmw = tile_rows / 32;
+    if (!tile_rows) tmw = nwt == 4 ? pick_rows(p.M, cout, cus) : 4;
     MRCNN_REQUIRE((tile_cols == 0 || tile_cols == 64 * nwt) && (tile_rows == 0 || tile_rows == 32 * tmw) && nwt >= 1 &&
                       cout % (64 * nwt) == 0,
                   "conv_f16_pipelined: tile %d x %d does not fit Cout %d", tile_rows, tile_cols, cout);
@@ -628,35 +634,21 @@ extern "C" int mrcnn_conv_f16_pipelined_heads(const void* x_f16, int32_t batch, 
         return mrcnn::fail(MRCNN_ERR_UNSUPPORTED,
                            "conv_f16_pipelined_heads: needs Cin %% 64 == 0, Cout %% 256 == 0, <= 25 taps, 0 <= pads < kernel, "
                            "32-bit byte offsets (got %dx%dx%dx%d -> %d, %dx%d)", batch, height, width, cin, cout, kh, kw);
-    P8Params p{};
-    p.x = static_cast<const _Float16*>(x_f16);
-    p.w = static_cast<const _Float16*>(w_f16);
-    p.scale = scale;
-    p.shift = shift;
+    P8Params p;
+    fill_p8(p, x_f16, batch, height, width, cin, w_f16, cout, kh, kw, 1, pad_top, pad_left, pad_bottom, pad_right, scale, shift,
+            activation);
     p.w_head = static_cast<const _Float16*>(w_head_f16);
     p.head_part = head_part;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout; p.KH = kh; p.KW = kw; p.stride = 1;
-    p.pad_t = pad_top; p.pad_l = pad_left;
-    p.OH = height + pad_top + pad_bottom - kh + 1;
-    p.OW = width + pad_left + pad_right - kw + 1;
-    p.M = batch * p.OH * p.OW;
-    p.K = kh * kw * cin;
-    p.nk = p.K / 64;
-    p.relu = activation;
-    p.res_div = 1;
-    p.x_bytes = static_cast<unsigned>(static_cast<long long>(batch) * height * width * cin * 2);
-    p.w_bytes = static_cast<unsigned>(static_cast<long long>(cout) * p.K * 2);
-    p.x_bias = static_cast<unsigned>((pad_top * width + pad_left) * cin * 2);
-    p.y_elems = static_cast<unsigned>(static_cast<long long>(p.M) * cout);
-    p.r_elems = p.y_elems;
-    const int cus = mrcnn::device_cu_count() > 0 ? mrcnn::device_cu_count() : 256;
+    int cus = 0;   // as above: only the automatic row choice needs it
+    if (!tile_rows)
+        if (int rc = mrcnn::query_cus("conv_f16_pipelined_heads", cus)) return rc;
     const int tmw = tile_rows ? tile_rows / 32 : pick_rows(p.M, cout, cus);
     hipStream_t s = mrcnn::as_stream(stream);
     switch (tmw) {
-        case 4: return launch_p8_heads<4>(p, s);
-        case 5: return launch_p8_heads<5>(p, s);
-        case 6: return launch_p8_heads<6>(p, s);
-        case 8: return launch_p8_heads<8>(p, s);
+        case 4: return launch_p8r<4, 4, false, true>(p, s);
+        case 5: return launch_p8r<5, 4, false, true>(p, s);
+        case 6: return launch_p8r<6, 4, false, true>(p, s);
+        case 8: return launch_p8r<8, 4, false, true>(p, s);
         default: break;
     }
     return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "conv_f16_pipelined_heads: tile_rows must be 0 (auto), 128, 160, 192 or 256");

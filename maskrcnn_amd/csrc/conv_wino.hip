@@ -1102,6 +1102,47 @@ extern "C" size_t mrcnn_conv3x3_winograd_workspace_bytes(int32_t batch, int32_t 
     return sizeof(float) * static_cast<size_t>(batch) * height * width * cin;
 }
 
+namespace {
+
+// Spatial tiles (8 x 8 position blocks of one image) for maps of at least 8 x 8 positions — the default; MRCNN_WINO_SPATIAL=0
+// (or mrcnn_winograd_set_spatial(0)) keeps the linear tiles (64 consecutive positions) everywhere. Same results bit for bit.
+bool wino_spatial_tiles(int height, int width) {
+    if (g_spatial < 0) g_spatial = (getenv("MRCNN_WINO_SPATIAL") && atoi(getenv("MRCNN_WINO_SPATIAL")) == 0) ? 0 : 1;
+    return g_spatial == 1 && height / 2 >= 8 && width / 2 >= 8;
+}
+
+// The one fill of WinoParams / WinoSParams: the shape, channel and activation checks (`heads`: Cout in whole N tiles;
+// `kblocked_out`: the caller writes a k-blocked output), the geometry of both tilings with tiles_m that of the LINEAR one,
+// and the byte ranges of x and u. Every output and the heads' fields are zero: an entry point sets its own after this,
+// checks its own size limits, and takes tiles_m = B * tyb * txb where it launches a spatial-tile kernel.
+int fill_wino(WinoSParams& p, const char* who, bool heads, bool kblocked_out, const float* x_kblocked, int batch, int height,
+              int width, int cin, const float* u, int cout, const float* scale, const float* shift, int activation) {
+    MRCNN_REQUIRE(batch >= 1 && height >= 2 && width >= 2 && height % 2 == 0 && width % 2 == 0,
+                  "%s: B=%d H=%d W=%d (even sizes required)", who, batch, height, width);
+    if (heads)
+        MRCNN_REQUIRE(cin >= 8 && cin % 8 == 0 && cout >= WN && cout % WN == 0,
+                      "%s: Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0) required", who, cin, cout);
+    else
+        MRCNN_REQUIRE(cin >= 8 && cin % 8 == 0 && cout >= 1, "%s: Cin=%d (%% 8 == 0 required) Cout=%d", who, cin, cout);
+    MRCNN_REQUIRE(!kblocked_out || cout % 8 == 0, "%s: a k-blocked output needs Cout %% 8 == 0", who);
+    MRCNN_REQUIRE(activation == 0 || activation == 1, "%s: activation must be 0 or 1", who);
+    const long long px = 1LL * batch * height * width;
+    p = WinoSParams{};
+    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift;
+    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
+    p.TH = height / 2; p.TW = width / 2; p.T = batch * p.TH * p.TW; p.act = activation;
+    p.tyb = (p.TH + 7) / 8; p.txb = (p.TW + 7) / 8;
+    p.tiles_m = (p.T + WT - 1) / WT;
+    p.tiles_n = (cout + WN - 1) / WN;
+    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
+    p.u_bytes = static_cast<unsigned>(4LL * 16 * cin * cout);
+    p.x_plane = static_cast<unsigned>(4LL * px * WK);
+    p.u_plane = static_cast<unsigned>(4LL * 16 * cout * WK);
+    return MRCNN_OK;
+}
+
+}  // namespace
+
 extern "C" int mrcnn_conv3x3_winograd_f32(const float* x, int32_t x_layout, int32_t batch, int32_t height,
                                           int32_t width, int32_t cin, const float* u, int32_t cout,
                                           const float* scale, const float* shift, int32_t activation, float* y_nhwc,
@@ -1112,78 +1153,40 @@ extern "C" int mrcnn_conv3x3_winograd_f32(const float* x, int32_t x_layout, int3
     MRCNN_REQUIRE(x_layout == MRCNN_LAYOUT_KBLOCKED ||
                       (workspace && workspace_bytes >= mrcnn_conv3x3_winograd_workspace_bytes(batch, height, width, cin)),
                   "conv3x3_winograd: an NHWC input needs a workspace of mrcnn_conv3x3_winograd_workspace_bytes()");
-    MRCNN_REQUIRE(batch >= 1 && height >= 2 && width >= 2 && height % 2 == 0 && width % 2 == 0,
-                  "conv3x3_winograd: B=%d H=%d W=%d (even sizes required)", batch, height, width);
-    MRCNN_REQUIRE(cin >= 8 && cin % 8 == 0 && cout >= 1, "conv3x3_winograd: Cin=%d (%% 8 == 0 required) Cout=%d", cin, cout);
-    MRCNN_REQUIRE(y_kblocked == nullptr || cout % 8 == 0, "conv3x3_winograd: a k-blocked output needs Cout %% 8 == 0");
-    MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd: activation must be 0 or 1");
+    WinoSParams p;
+    if (int rc = fill_wino(p, "conv3x3_winograd", false, y_kblocked != nullptr, x, batch, height, width, cin, u, cout, scale, shift,
+                           activation))
+        return rc;
     const long long px = 1LL * batch * height * width;
     MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES &&
                       64LL * cin * cout <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd: tensor too large (32-bit buffer byte offsets)");
+    p.y = y_nhwc; p.yk = y_kblocked;
+    p.yk_plane = static_cast<unsigned>(4LL * px * 8);
+    p.y_bytes = static_cast<unsigned>(4LL * px * cout);
+    const bool spatial = wino_spatial_tiles(height, width);
+    if (spatial) p.tiles_m = batch * p.tyb * p.txb;
+    const long long grid = 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n;
+    MRCNN_REQUIRE(grid <= 0x7fffffffLL, "conv3x3_winograd: grid too large");
     hipStream_t st = mrcnn::as_stream(stream);
-    const float* x8 = x;
     if (x_layout == MRCNN_LAYOUT_NHWC) {
         float* t = static_cast<float*>(workspace);
         hipLaunchKernelGGL(kblock_kernel, dim3(static_cast<unsigned>((px + 31) / 32), (cin + 63) / 64), dim3(256), 0, st,
                            x, static_cast<int64_t>(px), cin, t);
-        x8 = t;
+        p.x = t;
     }
-    WinoParams p;
-    p.x = x8; p.u = u; p.scale = scale; p.shift = shift; p.y = y_nhwc; p.yk = y_kblocked;
-    p.w_head = nullptr; p.head_part = nullptr; p.head_bytes = 0;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
-    p.TH = height / 2; p.TW = width / 2; p.T = batch * p.TH * p.TW; p.act = activation;
-    p.tiles_m = (p.T + WT - 1) / WT;
-    p.tiles_n = (cout + WN - 1) / WN;
-    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
-    p.u_bytes = static_cast<unsigned>(4LL * 16 * cin * cout);
-    p.x_plane = static_cast<unsigned>(4LL * px * WK);
-    p.u_plane = static_cast<unsigned>(4LL * 16 * cout * WK);
-    p.yk_plane = static_cast<unsigned>(4LL * px * 8);
-    p.y_bytes = static_cast<unsigned>(4LL * px * cout);
-    const long long grid = 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n;
-    MRCNN_REQUIRE(grid <= 0x7fffffffLL, "conv3x3_winograd: grid too large");
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(conv3x3_wino8_f32<false>), WINO_LDS, "conv3x3_winograd"))
-        return rc;
-    // spatial-tile kernel (8 x 8 position blocks of one image) for maps of at least 8 x 8 positions — the default;
-    // MRCNN_WINO_SPATIAL=0 (or mrcnn_winograd_set_spatial(0)) keeps the linear-tile kernel everywhere. Same results bit for bit.
-    if (g_spatial < 0) g_spatial = (getenv("MRCNN_WINO_SPATIAL") && atoi(getenv("MRCNN_WINO_SPATIAL")) == 0) ? 0 : 1;
-    if (g_spatial == 1 && p.TH >= 8 && p.TW >= 8) {
-        WinoSParams q;
-        static_cast<WinoParams&>(q) = p;
-        q.tyb = (p.TH + 7) / 8;
-        q.txb = (p.TW + 7) / 8;
-        q.tiles_m = batch * q.tyb * q.txb;
-        const long long sgrid = 8LL * ((q.tiles_m + 7) / 8) * q.tiles_n;
-        MRCNN_REQUIRE(sgrid <= 0x7fffffffLL, "conv3x3_winograd: grid too large");
-        if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(conv3x3_wino8s_f32<false>), WINOS_LDS, "conv3x3_winograd"))
-            return rc;
-        const int cus = mrcnn::device_cu_count();
-        if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd: cannot query the device");
-        const int ncu = cus >= 8 ? (cus / 8) * 8 : 8;
-        const long long launch = sgrid > ncu ? ncu : sgrid;
-        hipLaunchKernelGGL(conv3x3_wino8s_f32<false>, dim3(static_cast<unsigned>(launch)), dim3(512), WINOS_LDS, st, q);
-        return mrcnn::check_launch("conv3x3_wino8s_f32");
-    }
+    if (!spatial) {
 #ifdef MRCNN_ABLATIONS
-    static const bool four_waves = mrcnn::tuning_env("MRCNN_WINO_WAVES") && atoi(mrcnn::tuning_env("MRCNN_WINO_WAVES")) == 4;
-    if (four_waves) {
-        if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(conv3x3_wino_f32), WINO_LDS, "conv3x3_winograd"))
-            return rc;
-        hipLaunchKernelGGL(conv3x3_wino_f32, dim3(static_cast<unsigned>(grid)), dim3(256), WINO_LDS, st, p);
-        return mrcnn::check_launch("conv3x3_wino_f32");
-    }
+        static const bool four_waves = mrcnn::tuning_env("MRCNN_WINO_WAVES") && atoi(mrcnn::tuning_env("MRCNN_WINO_WAVES")) == 4;
+        if (four_waves)
+            return mrcnn::launch_kernel(conv3x3_wino_f32, grid, 256, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
 #endif
-    {
-        const int cus = mrcnn::device_cu_count();
-        if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd: cannot query the device");
-        const int num_cu = cus >= 8 ? (cus / 8) * 8 : 8;
         static const bool persistent = !(mrcnn::tuning_env("MRCNN_WINO_PERSISTENT") && atoi(mrcnn::tuning_env("MRCNN_WINO_PERSISTENT")) == 0);
-        const long long launch = (persistent && grid > num_cu) ? num_cu : grid;
-        hipLaunchKernelGGL(conv3x3_wino8_f32<false>, dim3(static_cast<unsigned>(launch)), dim3(512), WINO_LDS, st, p);
+        if (!persistent)
+            return mrcnn::launch_kernel(conv3x3_wino8_f32<false>, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
+        return mrcnn::launch_one_per_cu(conv3x3_wino8_f32<false>, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
     }
-    return mrcnn::check_launch("conv3x3_wino_f32");
+    return mrcnn::launch_one_per_cu(conv3x3_wino8s_f32<false>, grid, 512, WINOS_LDS, st, "conv3x3_winograd", "conv3x3_wino8s_f32", p);
 }
 
 // tile_mode: 1 = 64 consecutive positions per M tile (rows in position-major order), 2 = 8 x 8 position blocks
@@ -1196,8 +1199,7 @@ extern "C" int64_t mrcnn_conv3x3_winograd_heads_rows(int32_t batch, int32_t heig
 }
 
 extern "C" int32_t mrcnn_conv3x3_winograd_heads_tile_mode(int32_t height, int32_t width) {
-    if (g_spatial < 0) g_spatial = (getenv("MRCNN_WINO_SPATIAL") && atoi(getenv("MRCNN_WINO_SPATIAL")) == 0) ? 0 : 1;
-    return (g_spatial == 1 && height / 2 >= 8 && width / 2 >= 8) ? 2 : 1;
+    return wino_spatial_tiles(height, width) ? 2 : 1;
 }
 
 extern "C" int mrcnn_conv3x3_winograd_heads_f32(const float* x_kblocked, int32_t batch, int32_t height, int32_t width,
@@ -1205,11 +1207,10 @@ extern "C" int mrcnn_conv3x3_winograd_heads_f32(const float* x_kblocked, int32_t
                                                 const float* shift, int32_t activation, const float* w_head32,
                                                 int32_t tile_mode, float* head_part, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && w_head32 && head_part, "conv3x3_winograd_heads: null pointer");
-    MRCNN_REQUIRE(batch >= 1 && height >= 2 && width >= 2 && height % 2 == 0 && width % 2 == 0,
-                  "conv3x3_winograd_heads: B=%d H=%d W=%d (even sizes required)", batch, height, width);
-    MRCNN_REQUIRE(cin >= 8 && cin % 8 == 0 && cout >= WN && cout % WN == 0,
-                  "conv3x3_winograd_heads: Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0) required", cin, cout);
-    MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd_heads: activation must be 0 or 1");
+    WinoSParams p;
+    if (int rc = fill_wino(p, "conv3x3_winograd_heads", true, false, x_kblocked, batch, height, width, cin, u, cout, scale, shift,
+                           activation))
+        return rc;
 #ifdef MRCNN_ABLATIONS
     MRCNN_REQUIRE(tile_mode == 1 || (tile_mode == 2 && height / 2 >= 8 && width / 2 >= 8),
                   "conv3x3_winograd_heads: tile_mode must be 1, or 2 on maps of at least 8 x 8 tile positions");
@@ -1222,40 +1223,18 @@ extern "C" int mrcnn_conv3x3_winograd_heads_f32(const float* x_kblocked, int32_t
     MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 64LL * cin * cout <= MAX_BUFFER_BYTES &&
                       8 * rows * 32 <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd_heads: tensor too large (32-bit buffer byte offsets)");
-    WinoSParams p;
-    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
-    p.TH = height / 2; p.TW = width / 2; p.T = batch * p.TH * p.TW; p.act = activation;
-    p.tyb = (p.TH + 7) / 8; p.txb = (p.TW + 7) / 8;
-    p.tiles_m = tile_mode == 2 ? batch * p.tyb * p.txb : (p.T + WT - 1) / WT;
-    p.tiles_n = cout / WN;
-    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
-    p.u_bytes = static_cast<unsigned>(4LL * 16 * cin * cout);
-    p.x_plane = static_cast<unsigned>(4LL * px * WK);
-    p.u_plane = static_cast<unsigned>(4LL * 16 * cout * WK);
-    p.yk_plane = 0; p.y_bytes = 0;
+    if (tile_mode == 2) p.tiles_m = batch * p.tyb * p.txb;
     p.w_head = w_head32; p.head_part = head_part;
     p.head_bytes = static_cast<unsigned>(4LL * 2 * rows * 32);
-    const void* kern = reinterpret_cast<const void*>(conv3x3_wino8s_f32<true>);
-#ifdef MRCNN_ABLATIONS
-    if (tile_mode != 2) kern = reinterpret_cast<const void*>(conv3x3_wino8_f32<true>);
-#endif
-    if (int rc = mrcnn::ensure_dynamic_lds(kern, WINO_HEADS_LDS, "conv3x3_winograd_heads")) return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd_heads: cannot query the device");
-    const int num_cu = cus >= 8 ? (cus / 8) * 8 : 8;
     const long long units = 8LL * ((p.tiles_m + 7) / 8);  // M-tile units; a workgroup walks the N tiles of its units
-    const long long launch = units < num_cu ? units : num_cu;
+    hipStream_t st = mrcnn::as_stream(stream);
 #ifdef MRCNN_ABLATIONS
-    if (tile_mode != 2) {
-        hipLaunchKernelGGL(conv3x3_wino8_f32<true>, dim3(static_cast<unsigned>(launch)), dim3(512), WINO_HEADS_LDS,
-                           mrcnn::as_stream(stream), static_cast<const WinoParams&>(p));
-        return mrcnn::check_launch("conv3x3_wino8_f32<heads>");
-    }
+    if (tile_mode != 2)
+        return mrcnn::launch_one_per_cu(conv3x3_wino8_f32<true>, units, 512, WINO_HEADS_LDS, st, "conv3x3_winograd_heads",
+                                        "conv3x3_wino8_f32<heads>", p);
 #endif
-    hipLaunchKernelGGL(conv3x3_wino8s_f32<true>, dim3(static_cast<unsigned>(launch)), dim3(512), WINO_HEADS_LDS,
-                       mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("conv3x3_wino8s_f32<heads>");
+    return mrcnn::launch_one_per_cu(conv3x3_wino8s_f32<true>, units, 512, WINO_HEADS_LDS, st, "conv3x3_winograd_heads",
+                                    "conv3x3_wino8s_f32<heads>", p);
 }
 
 extern "C" int mrcnn_conv3x3_winograd_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width,

@@ -879,71 +879,107 @@ extern "C" int32_t mrcnn_conv3x3_winograd4_supported(int32_t batch, int32_t heig
     return 4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES && 144LL * cin * cout <= MAX_BUFFER_BYTES;
 }
 
+namespace {
+
+using Wino4Kernel = void (*)(const Wino4Params);
+
+// The one fill of Wino4Params: the shape and activation checks (mrcnn_conv3x3_winograd4_supported answers every size question
+// of x, u and a Cout-wide output), the tile geometry and the byte ranges of x and u. Every output and every optional field
+// is zero: an entry point sets its own outputs (and their byte ranges) after this. `fixed_cout`: the caller did not choose
+// Cout (the conv2 + conv3 form), so the refusal does not name it.
+int fill_wino4(Wino4Params& p, const char* who, bool fixed_cout, const float* x_kblocked, int batch, int height, int width,
+               int cin, const float* u, int cout, const float* scale, const float* shift, int activation) {
+    if (!mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, cout))
+        return fixed_cout
+                   ? mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT,
+                                 "%s: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required", who,
+                                 batch, height, width, cin)
+                   : mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT,
+                                 "%s: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 "
+                                 "bytes required", who, batch, height, width, cin, cout);
+    MRCNN_REQUIRE(activation == 0 || activation == 1, "%s: activation must be 0 or 1", who);
+    const long long px = 1LL * batch * height * width;
+    p = Wino4Params{};
+    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift;
+    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
+    p.TH = height / 4; p.TW = width / 4; p.act = activation;
+    p.tyb = wino4_tile_rows(height); p.txb = wino4_tile_cols(width);
+    p.tiles_m = batch * p.tyb * p.txb;
+    p.tiles_n = cout / W4_N;
+    p.x_plane = static_cast<unsigned>(4LL * px * 8);
+    p.u_ktile = static_cast<unsigned>(4LL * 36 * 4 * cout);
+    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
+    p.u_bytes = static_cast<unsigned>(4LL * 36 * cin * cout);
+    return MRCNN_OK;
+}
+
+// MRCNN_W4_ABLATIONS builds: MRCNN_W4_DEBUG names a timing variant (wrong results) of the plain or of the heads kernel; any
+// other value keeps `kern`. The variable is read on EVERY call (tests/test_gpu_sync_fuzz.py changes it between calls) and
+// travels to the kernel in p.debug. The product build has no variants and reads nothing.
+Wino4Kernel wino4_debug_kernel(bool heads, Wino4Kernel kern, Wino4Params& p) {
+#ifdef MRCNN_W4_ABLATIONS
+    p.debug = getenv("MRCNN_W4_DEBUG") ? atoi(getenv("MRCNN_W4_DEBUG")) : 0;
+    if (!heads) {
+        switch (p.debug) {
+            case 1: return conv3x3_wino4_f32<1, false>;
+            case 2: return conv3x3_wino4_f32<2, false>;
+            case 4: return conv3x3_wino4_f32<4, false>;
+            case 8: return conv3x3_wino4_f32<8, false>;
+            case 16: return conv3x3_wino4_f32<16, false>;
+            case 31: return conv3x3_wino4_f32<31, false>;
+            case 2048: return conv3x3_wino4_f32<2048, false>;
+            case 4096: return conv3x3_wino4_f32<4096, false, false>;
+            case 8192: return conv3x3_wino4_f32<8192, false, false>;
+            case 12288: return conv3x3_wino4_f32<12288, false, false>;
+            case 63: return conv3x3_wino4_f32<63, false>;
+            case 95: return conv3x3_wino4_f32<95, false>;
+            default: return kern;
+        }
+    }
+    switch (p.debug) {
+        case 32: return conv3x3_wino4_f32<32, true>;
+        case 128: return conv3x3_wino4_f32<128, true>;
+        case 160: return conv3x3_wino4_f32<160, true>;
+        case 256: return conv3x3_wino4_f32<256, true>;
+        case 512: return conv3x3_wino4_f32<512, true>;
+        case 1024: return conv3x3_wino4_f32<1024, true>;
+        case 1792: return conv3x3_wino4_f32<1792, true>;
+        case 2048: return conv3x3_wino4_f32<2048, true>;
+        default: return kern;
+    }
+#else
+    (void)heads;
+    (void)p;
+    return kern;
+#endif
+}
+
+}  // namespace
+
 extern "C" int mrcnn_conv3x3_winograd4_f32(const float* x_kblocked, int32_t batch, int32_t height, int32_t width,
                                            int32_t cin, const float* u, int32_t cout, const float* scale,
                                            const float* shift, int32_t activation, float* y_nhwc, float* y_kblocked,
                                            mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && (y_nhwc || y_kblocked), "conv3x3_winograd4: null pointer");
-    MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, cout),
-                  "conv3x3_winograd4: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required",
-                  batch, height, width, cin, cout);
-    MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd4: activation must be 0 or 1");
-    const long long px = 1LL * batch * height * width;
-    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 4 * px * cout <= MAX_BUFFER_BYTES &&
-                      144LL * cin * cout <= MAX_BUFFER_BYTES,
-                  "conv3x3_winograd4: tensor too large (32-bit buffer byte offsets)");
     Wino4Params p;
-    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = y_nhwc; p.yk = y_kblocked;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
-    p.TH = height / 4; p.TW = width / 4; p.act = activation;
-    p.tyb = (p.TH + 3) / 4; p.txb = (p.TW + 7) / 8;
-    p.tiles_m = batch * p.tyb * p.txb;
-    p.tiles_n = cout / W4_N;
-    p.x_plane = static_cast<unsigned>(4LL * px * 8);
-    p.u_ktile = static_cast<unsigned>(4LL * 36 * 4 * cout);
+    if (int rc = fill_wino4(p, "conv3x3_winograd4", false, x_kblocked, batch, height, width, cin, u, cout, scale, shift,
+                            activation))
+        return rc;
+    const long long px = 1LL * batch * height * width;
+    p.y = y_nhwc; p.yk = y_kblocked;
     p.yk_plane = static_cast<unsigned>(4LL * px * 8);
-    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
-    p.u_bytes = static_cast<unsigned>(4LL * 36 * cin * cout);
     p.y_bytes = static_cast<unsigned>(4LL * px * cout);
-    p.w_head = nullptr; p.head_part = nullptr; p.head_bytes = 0;
-    p.w3 = nullptr; p.scale3 = nullptr; p.shift3 = nullptr; p.res3 = nullptr; p.y3 = nullptr; p.C3 = 0; p.w3_bytes = 0; p.y3_bytes = 0;
-    p.debug = 0;
-#ifdef MRCNN_W4_ABLATIONS
-    p.debug = getenv("MRCNN_W4_DEBUG") ? atoi(getenv("MRCNN_W4_DEBUG")) : 0;
-#endif
     const long long grid = 8LL * ((p.tiles_m + 7) / 8) * p.tiles_n;
     MRCNN_REQUIRE(grid <= 0x7fffffffLL, "conv3x3_winograd4: grid too large");
-    void (*kern)(const Wino4Params) = activation ? conv3x3_wino4_f32<0, false, true> : conv3x3_wino4_f32<0, false, false>;
-#ifdef MRCNN_W4_ABLATIONS
-    switch (p.debug) {
-        case 1: kern = conv3x3_wino4_f32<1, false>; break;
-        case 2: kern = conv3x3_wino4_f32<2, false>; break;
-        case 4: kern = conv3x3_wino4_f32<4, false>; break;
-        case 8: kern = conv3x3_wino4_f32<8, false>; break;
-        case 16: kern = conv3x3_wino4_f32<16, false>; break;
-        case 31: kern = conv3x3_wino4_f32<31, false>; break;
-        case 2048: kern = conv3x3_wino4_f32<2048, false>; break;
-        case 4096: kern = conv3x3_wino4_f32<4096, false, false>; break;
-        case 8192: kern = conv3x3_wino4_f32<8192, false, false>; break;
-        case 12288: kern = conv3x3_wino4_f32<12288, false, false>; break;
-        case 63: kern = conv3x3_wino4_f32<63, false>; break;
-        case 95: kern = conv3x3_wino4_f32<95, false>; break;
-        default: break;
-    }
-#endif
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), WINO4_LDS, "conv3x3_winograd4"))
-        return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd4: cannot query the device");
-    const int ncu = cus >= 8 ? (cus / 8) * 8 : 8;
-    const long long launch = grid > ncu ? ncu : grid;
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(launch)), dim3(256), WINO4_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("conv3x3_wino4_f32");
+    const Wino4Kernel kern = wino4_debug_kernel(
+        false, activation ? conv3x3_wino4_f32<0, false, true> : conv3x3_wino4_f32<0, false, false>, p);
+    return mrcnn::launch_one_per_cu(kern, grid, 256, WINO4_LDS, mrcnn::as_stream(stream), "conv3x3_winograd4", "conv3x3_wino4_f32",
+                                    p);
 }
 
 extern "C" int64_t mrcnn_conv3x3_winograd4_heads_rows(int32_t batch, int32_t height, int32_t width) {
     if (batch < 1 || height < 4 || width < 4 || height % 4 || width % 4) return 0;
-    return static_cast<int64_t>(batch) * ((height / 4 + 3) / 4) * ((width / 4 + 7) / 8) * 512;
+    return static_cast<int64_t>(batch) * wino4_tiles_per_image(height, width) * 512;
 }
 
 extern "C" int mrcnn_conv3x3_winograd4_heads_f32(const float* x_kblocked, int32_t batch, int32_t height, int32_t width,
@@ -951,58 +987,19 @@ extern "C" int mrcnn_conv3x3_winograd4_heads_f32(const float* x_kblocked, int32_
                                                  const float* shift, int32_t activation, const float* w_head32,
                                                  float* head_part, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && w_head32 && head_part, "conv3x3_winograd4_heads: null pointer");
-    MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, cout),
-                  "conv3x3_winograd4_heads: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes "
-                  "required", batch, height, width, cin, cout);
-    MRCNN_REQUIRE(activation == 0 || activation == 1, "conv3x3_winograd4_heads: activation must be 0 or 1");
-    const long long px = 1LL * batch * height * width;
-    const long long rows = mrcnn_conv3x3_winograd4_heads_rows(batch, height, width);
-    MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 144LL * cin * cout <= MAX_BUFFER_BYTES &&
-                      4 * rows * 32 <= MAX_BUFFER_BYTES,
-                  "conv3x3_winograd4_heads: tensor too large (32-bit buffer byte offsets)");
     Wino4Params p;
-    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = cout;
-    p.TH = height / 4; p.TW = width / 4; p.act = activation;
-    p.tyb = (p.TH + 3) / 4; p.txb = (p.TW + 7) / 8;
-    p.tiles_m = batch * p.tyb * p.txb;
-    p.tiles_n = cout / W4_N;
-    p.x_plane = static_cast<unsigned>(4LL * px * 8);
-    p.u_ktile = static_cast<unsigned>(4LL * 36 * 4 * cout);
-    p.yk_plane = 0;
-    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
-    p.u_bytes = static_cast<unsigned>(4LL * 36 * cin * cout);
-    p.y_bytes = 0;
+    if (int rc = fill_wino4(p, "conv3x3_winograd4_heads", false, x_kblocked, batch, height, width, cin, u, cout, scale, shift,
+                            activation))
+        return rc;
+    const long long rows = mrcnn_conv3x3_winograd4_heads_rows(batch, height, width);
+    MRCNN_REQUIRE(4 * rows * 32 <= MAX_BUFFER_BYTES, "conv3x3_winograd4_heads: tensor too large (32-bit buffer byte offsets)");
     p.w_head = w_head32; p.head_part = head_part;
     p.head_bytes = static_cast<unsigned>(4LL * rows * 32);
-    p.w3 = nullptr; p.scale3 = nullptr; p.shift3 = nullptr; p.res3 = nullptr; p.y3 = nullptr; p.C3 = 0; p.w3_bytes = 0; p.y3_bytes = 0;
-    p.debug = 0;
-#ifdef MRCNN_W4_ABLATIONS
-    p.debug = getenv("MRCNN_W4_DEBUG") ? atoi(getenv("MRCNN_W4_DEBUG")) : 0;
-#endif
-    void (*kern)(const Wino4Params) = activation ? conv3x3_wino4_f32<0, true, true> : conv3x3_wino4_f32<0, true, false>;
-#ifdef MRCNN_W4_ABLATIONS
-    switch (p.debug) {
-        case 32: kern = conv3x3_wino4_f32<32, true>; break;
-        case 128: kern = conv3x3_wino4_f32<128, true>; break;
-        case 160: kern = conv3x3_wino4_f32<160, true>; break;
-        case 256: kern = conv3x3_wino4_f32<256, true>; break;
-        case 512: kern = conv3x3_wino4_f32<512, true>; break;
-        case 1024: kern = conv3x3_wino4_f32<1024, true>; break;
-        case 1792: kern = conv3x3_wino4_f32<1792, true>; break;
-        case 2048: kern = conv3x3_wino4_f32<2048, true>; break;
-        default: break;
-    }
-#endif
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), WINO4_HEADS_LDS, "conv3x3_winograd4_heads"))
-        return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd4_heads: cannot query the device");
-    const int ncu = cus >= 8 ? (cus / 8) * 8 : 8;
-    const long long units = 8LL * ((p.tiles_m + 7) / 8);  // M-tile units; a workgroup walks the N tiles of its units
-    const long long launch = units < ncu ? units : ncu;
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(launch)), dim3(256), WINO4_HEADS_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("conv3x3_wino4_f32<heads>");
+    const Wino4Kernel kern = wino4_debug_kernel(
+        true, activation ? conv3x3_wino4_f32<0, true, true> : conv3x3_wino4_f32<0, true, false>, p);
+    // M-tile units; a workgroup walks the N tiles of its units
+    return mrcnn::launch_one_per_cu(kern, 8LL * ((p.tiles_m + 7) / 8), 256, WINO4_HEADS_LDS, mrcnn::as_stream(stream),
+                                    "conv3x3_winograd4_heads", "conv3x3_wino4_f32<heads>", p);
 }
 
 // conv2 (3x3, planes -> planes = 64) + BN + ReLU, then conv3 (1x1, 64 -> c3) + BN + residual + ReLU of a ResNet Bottleneck
@@ -1012,39 +1009,16 @@ extern "C" int mrcnn_conv3x3_winograd4_conv3_f32(const float* x_kblocked, int32_
                                                  const float* w3, int32_t c3, const float* scale3, const float* shift3,
                                                  const float* residual, float* y, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(x_kblocked && u && w3 && residual && y, "conv3x3_winograd4_conv3: null pointer");
-    MRCNN_REQUIRE(batch >= 1 && mrcnn_conv3x3_winograd4_supported(batch, height, width, cin, W4_N),
-                  "conv3x3_winograd4_conv3: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required", batch,
-                  height, width, cin);
+    Wino4Params p;
+    if (int rc = fill_wino4(p, "conv3x3_winograd4_conv3", true, x_kblocked, batch, height, width, cin, u, W4_N, scale, shift, 1))
+        return rc;
     MRCNN_REQUIRE(c3 >= 32 && c3 % 32 == 0 && c3 <= 256, "conv3x3_winograd4_conv3: c3=%d must be a multiple of 32, at most 256", c3);
     MRCNN_REQUIRE(residual != y, "conv3x3_winograd4_conv3: in-place operation is not supported");
     const long long px = 1LL * batch * height * width;
     MRCNN_REQUIRE(4 * px * c3 <= MAX_BUFFER_BYTES, "conv3x3_winograd4_conv3: tensor too large (32-bit buffer byte offsets)");
-    Wino4Params p;
-    p.x = x_kblocked; p.u = u; p.scale = scale; p.shift = shift; p.y = nullptr; p.yk = nullptr;
-    p.B = batch; p.H = height; p.W = width; p.Cin = cin; p.Cout = W4_N;
-    p.TH = height / 4; p.TW = width / 4; p.act = 1;
-    p.tyb = (p.TH + 3) / 4; p.txb = (p.TW + 7) / 8;
-    p.tiles_m = batch * p.tyb * p.txb;
-    p.tiles_n = 1;
-    p.x_plane = static_cast<unsigned>(4LL * px * 8);
-    p.u_ktile = static_cast<unsigned>(4LL * 36 * 4 * W4_N);
-    p.yk_plane = 0;
-    p.x_bytes = static_cast<unsigned>(4LL * px * cin);
-    p.u_bytes = static_cast<unsigned>(4LL * 36 * cin * W4_N);
-    p.y_bytes = 0;
-    p.w_head = nullptr; p.head_part = nullptr; p.head_bytes = 0;
     p.w3 = w3; p.scale3 = scale3; p.shift3 = shift3; p.res3 = residual; p.y3 = y; p.C3 = c3;
     p.w3_bytes = static_cast<unsigned>(4LL * c3 * W4_N);
     p.y3_bytes = static_cast<unsigned>(4LL * px * c3);
-    p.debug = 0;
-    void (*kern)(const Wino4Params) = conv3x3_wino4_f32<0, false, true, true>;
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), WINO4_CONV3_LDS, "conv3x3_winograd4_conv3"))
-        return rc;
-    const int cus = mrcnn::device_cu_count();
-    if (cus <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "conv3x3_winograd4_conv3: cannot query the device");
-    const int ncu = cus >= 8 ? (cus / 8) * 8 : 8;
-    const long long grid = 8LL * ((p.tiles_m + 7) / 8);
-    const long long launch = grid > ncu ? ncu : grid;
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(launch)), dim3(256), WINO4_CONV3_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("conv3x3_wino4_f32<conv3>");
+    return mrcnn::launch_one_per_cu(conv3x3_wino4_f32<0, false, true, true>, 8LL * ((p.tiles_m + 7) / 8), 256, WINO4_CONV3_LDS,
+                                    mrcnn::as_stream(stream), "conv3x3_winograd4_conv3", "conv3x3_wino4_f32<conv3>", p);
 }

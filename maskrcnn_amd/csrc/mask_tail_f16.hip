@@ -259,9 +259,8 @@ extern "C" int mrcnn_mask_tail_f16(const void* x_f16, int32_t rois, int32_t heig
     p.items = p.sets * 4;
     p.x_bytes = static_cast<unsigned>(static_cast<long long>(p.M) * 512);
     p.y_bytes = static_cast<unsigned>(static_cast<long long>(p.M) * 4 * classes * 4);
-    const int cus = mrcnn::device_cu_count() > 0 ? mrcnn::device_cu_count() : 256;
-    const int grid = std::max(1, std::min(cus, p.items));
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(mask_tail_f16), MT_LDS, "mask_tail_f16")) return rc;
-    hipLaunchKernelGGL(mask_tail_f16, dim3(grid), dim3(512), MT_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("mask_tail_f16");
+    int cus;
+    if (int rc = mrcnn::query_cus("mask_tail_f16", cus)) return rc;
+    return mrcnn::launch_kernel(mask_tail_f16, std::max(1, std::min(cus, p.items)), 512, MT_LDS, mrcnn::as_stream(stream),
+                                "mask_tail_f16", "mask_tail_f16", p);
 }

@@ -649,6 +649,17 @@ __global__ __launch_bounds__(256, 1) void stem7x7_s2_pool_f32(const StemPool32Pa
 }  // namespace
 
 namespace {
+
+// Persistent launch of a stem kernel: `per_cu` workgroups per CU, fewer when there are fewer tiles.
+template <typename P>
+int launch_stem(void (*kern)(P), const typename mrcnn::kernel_arg<P>::type& p, int per_cu, int threads, size_t lds_bytes,
+                const char* who, const char* kernel_name, mrcnn_stream_t stream) {
+    int cus;
+    if (int rc = mrcnn::query_cus(who, cus)) return rc;
+    return mrcnn::launch_kernel(kern, std::min(p.tiles, per_cu * cus), threads, lds_bytes, mrcnn::as_stream(stream), who,
+                                kernel_name, p);
+}
+
 int run_stem(bool nchw, const float* x, int32_t batch, int32_t height, int32_t width, const float* w, const float* scale,
              const float* shift, int32_t activation, float* y, mrcnn_stream_t stream, bool out16 = false) {
     MRCNN_REQUIRE(!out16 || nchw, "stem: the fp16-output form reads the NCHW image");
@@ -667,17 +678,32 @@ int run_stem(bool nchw, const float* x, int32_t batch, int32_t height, int32_t w
     p.act = activation;
     p.x_bytes = static_cast<unsigned>((nchw ? 12LL : 16LL) * batch * height * width);
     p.y_bytes = static_cast<unsigned>((out16 ? 128LL : 256LL) * batch * p.OH * p.OW);
-    const void* kern = out16 ? reinterpret_cast<const void*>(stem7x7_s2_f32<true, true>)
-                     : nchw ? reinterpret_cast<const void*>(stem7x7_s2_f32<true>) : reinterpret_cast<const void*>(stem7x7_s2_f32<false>);
-    if (int rc = mrcnn::ensure_dynamic_lds(kern, STEM_LDS, "stem")) return rc;
-    const int num_cu = mrcnn::device_cu_count();
-    if (num_cu <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "stem: cannot query the device");
-    const int grid = p.tiles < 2 * num_cu ? p.tiles : 2 * num_cu;  // persistent: two workgroups per CU
-    if (out16) hipLaunchKernelGGL((stem7x7_s2_f32<true, true>), dim3(grid), dim3(256), STEM_LDS, mrcnn::as_stream(stream), p);
-    else if (nchw) hipLaunchKernelGGL(stem7x7_s2_f32<true>, dim3(grid), dim3(256), STEM_LDS, mrcnn::as_stream(stream), p);
-    else hipLaunchKernelGGL(stem7x7_s2_f32<false>, dim3(grid), dim3(256), STEM_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("stem7x7_s2_f32");
+    void (*kern)(const StemParams) = stem7x7_s2_f32<true, true>;
+    if (!out16) kern = nchw ? stem7x7_s2_f32<true> : stem7x7_s2_f32<false>;
+    return launch_stem(kern, p, 2, 256, STEM_LDS, "stem", "stem7x7_s2_f32", stream);  // two workgroups per CU
 }
+
+// The one fill of the two stem + pool parameter blocks (P: StemPoolParams / StemPool32Params, PH x PW: pooled pixels per
+// tile): the pointer and shape checks, the conv and pooled sizes, the tiling and the byte ranges. The size limit differs
+// between the two forms: each entry point checks its own right after this (a shape past it leaves only numbers in p).
+template <typename P, int PH, int PW, typename Y>
+int fill_stem_pool(P& p, const char* who, const float* x_nchw, int batch, int height, int width, const float* w,
+                   const float* scale, const float* shift, Y* y) {
+    MRCNN_REQUIRE(x_nchw && w && y, "%s: null pointer", who);
+    // (an odd conv size would give SamePad2d(3, 2) a top / left component — model.py:64-87 — and shift the pooling windows)
+    MRCNN_REQUIRE(batch >= 1 && height >= 4 && width >= 4 && height % 4 == 0 && width % 4 == 0,
+                  "%s: B=%d H=%d W=%d (multiples of 4 required)", who, batch, height, width);
+    p.x = x_nchw; p.w = w; p.scale = scale; p.shift = shift; p.y = y;
+    p.B = batch; p.H = height; p.W = width; p.OH = height / 2; p.OW = width / 2;
+    p.POH = (p.OH + 1) / 2; p.POW = (p.OW + 1) / 2;   // SamePad2d(3, 2) + MaxPool2d(3, 2): ceil(n / 2) (model.py:64-87,227-228)
+    p.tiles_x = (p.POW + PW - 1) / PW;
+    p.tiles_y = (p.POH + PH - 1) / PH;
+    p.tiles = static_cast<int>(1LL * batch * p.tiles_x * p.tiles_y);
+    p.x_bytes = static_cast<unsigned>(12LL * batch * height * width);
+    p.y_bytes = static_cast<unsigned>(64LL * sizeof(Y) * batch * p.POH * p.POW);
+    return MRCNN_OK;
+}
+
 }  // namespace
 
 extern "C" int mrcnn_stem_conv7x7_s2_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width,
@@ -700,50 +726,23 @@ extern "C" int mrcnn_stem_conv7x7_s2_nchw_f16out(const float* x_nchw, int32_t ba
 
 extern "C" int mrcnn_stem_conv7x7_s2_pool_f16(const float* x_nchw, int32_t batch, int32_t height, int32_t width, const float* w,
                                               const float* scale, const float* shift, void* y_f16, mrcnn_stream_t stream) {
-    MRCNN_REQUIRE(x_nchw && w && y_f16, "stem_pool: null pointer");
-    // (an odd conv size would give SamePad2d(3, 2) a top / left component — model.py:64-87 — and shift the pooling windows)
-    MRCNN_REQUIRE(batch >= 1 && height >= 4 && width >= 4 && height % 4 == 0 && width % 4 == 0,
-                  "stem_pool: B=%d H=%d W=%d (multiples of 4 required)", batch, height, width);
-    MRCNN_REQUIRE(12LL * batch * height * width <= MAX_BUFFER_BYTES, "stem_pool: tensor too large (32-bit buffer byte offsets)");
     StemPoolParams p;
-    p.x = x_nchw; p.w = w; p.scale = scale; p.shift = shift; p.y = static_cast<_Float16*>(y_f16);
-    p.B = batch; p.H = height; p.W = width; p.OH = height / 2; p.OW = width / 2;
-    p.POH = (p.OH + 1) / 2; p.POW = (p.OW + 1) / 2;   // SamePad2d(3, 2) + MaxPool2d(3, 2): ceil(n / 2) (model.py:64-87,227-228)
-    p.tiles_x = (p.POW + SP_PW - 1) / SP_PW;
-    p.tiles_y = (p.POH + SP_PH - 1) / SP_PH;
-    p.tiles = batch * p.tiles_x * p.tiles_y;
-    p.x_bytes = static_cast<unsigned>(12LL * batch * height * width);
-    p.y_bytes = static_cast<unsigned>(128LL * batch * p.POH * p.POW);
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(stem7x7_s2_pool_f16), STEM_POOL_LDS, "stem_pool")) return rc;
-    const int num_cu = mrcnn::device_cu_count();
-    if (num_cu <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "stem_pool: cannot query the device");
-    const int grid = p.tiles < num_cu ? p.tiles : num_cu;   // persistent: one eight-wave workgroup per CU
-    hipLaunchKernelGGL(stem7x7_s2_pool_f16, dim3(grid), dim3(SP_THREADS), STEM_POOL_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("stem7x7_s2_pool_f16");
+    if (int rc = fill_stem_pool<StemPoolParams, SP_PH, SP_PW>(p, "stem_pool", x_nchw, batch, height, width, w, scale, shift,
+                                                              static_cast<_Float16*>(y_f16)))
+        return rc;
+    MRCNN_REQUIRE(12LL * batch * height * width <= MAX_BUFFER_BYTES, "stem_pool: tensor too large (32-bit buffer byte offsets)");
+    // one nine-wave workgroup per CU
+    return launch_stem(stem7x7_s2_pool_f16, p, 1, SP_THREADS, STEM_POOL_LDS, "stem_pool", "stem7x7_s2_pool_f16", stream);
 }
 
 extern "C" int mrcnn_stem_conv7x7_s2_pool_f32(const float* x_nchw, int32_t batch, int32_t height, int32_t width, const float* w,
                                               const float* scale, const float* shift, float* y, mrcnn_stream_t stream) {
-    MRCNN_REQUIRE(x_nchw && w && y, "stem_pool_f32: null pointer");
-    // (an odd conv size would give SamePad2d(3, 2) a top / left component — model.py:64-87 — and shift the pooling windows)
-    MRCNN_REQUIRE(batch >= 1 && height >= 4 && width >= 4 && height % 4 == 0 && width % 4 == 0,
-                  "stem_pool_f32: B=%d H=%d W=%d (multiples of 4 required)", batch, height, width);
+    StemPool32Params p;
+    if (int rc = fill_stem_pool<StemPool32Params, S3_PH, S3_PW>(p, "stem_pool_f32", x_nchw, batch, height, width, w, scale, shift, y))
+        return rc;
     // input 12 B and output 16 B per input pixel (64 fp32 channels per 4 x 4 pixels): the output is the larger tensor
     MRCNN_REQUIRE(12LL * batch * height * width <= MAX_BUFFER_BYTES && 16LL * batch * height * width < (1LL << 31),
                   "stem_pool_f32: tensor too large (32-bit buffer byte offsets: B*H*W < 2^27 pixels)");
-    StemPool32Params p;
-    p.x = x_nchw; p.w = w; p.scale = scale; p.shift = shift; p.y = y;
-    p.B = batch; p.H = height; p.W = width; p.OH = height / 2; p.OW = width / 2;
-    p.POH = (p.OH + 1) / 2; p.POW = (p.OW + 1) / 2;   // SamePad2d(3, 2) + MaxPool2d(3, 2): ceil(n / 2) (model.py:64-87,227-228)
-    p.tiles_x = (p.POW + S3_PW - 1) / S3_PW;
-    p.tiles_y = (p.POH + S3_PH - 1) / S3_PH;
-    p.tiles = batch * p.tiles_x * p.tiles_y;
-    p.x_bytes = static_cast<unsigned>(12LL * batch * height * width);
-    p.y_bytes = static_cast<unsigned>(256LL * batch * p.POH * p.POW);
-    if (int rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(stem7x7_s2_pool_f32), STEM_POOL32_LDS, "stem_pool_f32")) return rc;
-    const int num_cu = mrcnn::device_cu_count();
-    if (num_cu <= 0) return mrcnn::fail(MRCNN_ERR_LAUNCH, "stem_pool_f32: cannot query the device");
-    const int grid = p.tiles < num_cu ? p.tiles : num_cu;   // persistent: one four-wave workgroup per CU
-    hipLaunchKernelGGL(stem7x7_s2_pool_f32, dim3(grid), dim3(256), STEM_POOL32_LDS, mrcnn::as_stream(stream), p);
-    return mrcnn::check_launch("stem7x7_s2_pool_f32");
+    // one four-wave workgroup per CU
+    return launch_stem(stem7x7_s2_pool_f32, p, 1, 256, STEM_POOL32_LDS, "stem_pool_f32", "stem7x7_s2_pool_f32", stream);
 }

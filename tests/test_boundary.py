@@ -355,6 +355,203 @@ def test_entry_points_refuse_the_first_shape_past_their_limit():
     assert not lib.mrcnn_mask_tail_f16_supported(16908, 14, 14, 256, 256, 81)
 
 
+def test_conv_entry_points_with_a_shared_fill_keep_every_refusal():
+    """The conv entry points whose parameter blocks are filled by one shared function (F(4x4) plain / heads / conv3, F(2x2)
+    plain / NHWC / heads, the pipelined fp16 conv and its heads form, the stem and the two stem + pool forms): one row per check of
+    each entry point — return code and exact message —, and where one bad tuple trips two checks, the one that came first
+    still wins. Validation runs before any HIP call (dummy pointers, never touched); every row is a refusal, so nothing is
+    launched on a machine that has a GPU."""
+    from maskrcnn_amd import _lib
+    lib = _lib.lib
+    dp, dq, N = ctypes.c_void_p(16), ctypes.c_void_p(4096), None
+    INVALID, UNSUPPORTED = -1, -2
+    big = ctypes.c_size_t(1 << 40)
+
+    def row(rc, code, text):
+        assert (rc, lib.mrcnn_last_error()) == (code, text.encode()), (text, rc, lib.mrcnn_last_error())
+
+    # ---- F(4x4) plain: (x, B, H, W, Cin, u, Cout, scale, shift, act, y, yk, stream)
+    w4 = lib.mrcnn_conv3x3_winograd4_f32
+    shape4 = "%s: B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required"
+    who = "conv3x3_winograd4"
+    row(w4(N, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, N), INVALID, who + ": null pointer")
+    row(w4(dp, 1, 8, 8, 8, N, 64, N, N, 1, dq, N, N), INVALID, who + ": null pointer")
+    row(w4(dp, 1, 8, 8, 8, dp, 64, N, N, 1, N, N, N), INVALID, who + ": null pointer")
+    for b, h, w, cin, cout in ((0, 8, 8, 8, 64), (1, 6, 8, 8, 64), (1, 8, 10, 8, 64), (1, 0, 8, 8, 64), (1, 8, 8, 12, 64),
+                               (1, 8, 8, 0, 64), (1, 8, 8, 8, 96), (1, 8, 8, 8, 32),
+                               (4, 512, 512, 1024, 64), (4, 512, 512, 8, 1024), (1, 8, 8, 8192, 4096)):   # the three byte limits
+        row(w4(dp, b, h, w, cin, dp, cout, N, N, 1, dq, N, N), INVALID, shape4 % (who, b, h, w, cin, cout))
+    row(w4(dp, 1, 8, 8, 8, dp, 64, N, N, 2, dq, N, N), INVALID, who + ": activation must be 0 or 1")
+    row(w4(dp, 1, 8, 8, 8, dp, 64, N, N, -1, N, dq, N), INVALID, who + ": activation must be 0 or 1")
+    row(w4(N, 1, 6, 8, 8, dp, 64, N, N, 2, dq, N, N), INVALID, who + ": null pointer")                    # first check wins
+    row(w4(dp, 1, 6, 8, 8, dp, 64, N, N, 2, dq, N, N), INVALID, shape4 % (who, 1, 6, 8, 8, 64))
+    # ---- F(4x4) heads: (x, B, H, W, Cin, u, Cout, scale, shift, act, w_head, head_part, stream)
+    w4h = lib.mrcnn_conv3x3_winograd4_heads_f32
+    who = "conv3x3_winograd4_heads"
+    row(w4h(dp, 1, 8, 8, 8, dp, 64, N, N, 1, N, dq, N), INVALID, who + ": null pointer")
+    row(w4h(dp, 1, 8, 8, 8, dp, 64, N, N, 1, dp, N, N), INVALID, who + ": null pointer")
+    for b, h, w, cin, cout in ((1, 6, 8, 8, 64), (1, 8, 8, 12, 64), (1, 8, 8, 8, 96), (4, 512, 512, 1024, 64)):
+        row(w4h(dp, b, h, w, cin, dp, cout, N, N, 1, dp, dq, N), INVALID, shape4 % (who, b, h, w, cin, cout))
+    row(w4h(dp, 1, 8, 8, 8, dp, 64, N, N, 2, dp, dq, N), INVALID, who + ": activation must be 0 or 1")
+    # the head sums: 512 rows x 32 fp32 per M tile, a tile per 4 x 4 image here: 65 536 tiles are 2^32 bytes
+    assert lib.mrcnn_conv3x3_winograd4_supported(65536, 4, 4, 8, 64) and 4 * 65536 * 512 * 32 > OOB >= 4 * 65535 * 512 * 32
+    row(w4h(dp, 65536, 4, 4, 8, dp, 64, N, N, 1, dp, dq, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w4h(dp, 65536, 4, 4, 8, dp, 64, N, N, 2, dp, dq, N), INVALID, who + ": activation must be 0 or 1")   # first check wins
+    row(w4h(dp, 65536, 4, 4, 12, dp, 64, N, N, 2, dp, dq, N), INVALID, shape4 % (who, 65536, 4, 4, 12, 64))
+    # ---- F(4x4) conv2 + conv3: (x, B, H, W, Cin, u, scale, shift, w3, c3, scale3, shift3, residual, y, stream)
+    w43 = lib.mrcnn_conv3x3_winograd4_conv3_f32
+    who = "conv3x3_winograd4_conv3"
+    shape43 = who + ": B=%d H=%d W=%d (%% 4 == 0) Cin=%d (%% 8 == 0), 4*B*H*W*C <= 0xFFFFFFF0 bytes required"
+    row(w43(dp, 1, 8, 8, 64, dp, N, N, N, 256, N, N, dp, dq, N), INVALID, who + ": null pointer")
+    row(w43(dp, 1, 8, 8, 64, dp, N, N, dp, 256, N, N, N, dq, N), INVALID, who + ": null pointer")
+    row(w43(dp, 1, 8, 8, 64, dp, N, N, dp, 256, N, N, dp, N, N), INVALID, who + ": null pointer")
+    for b, h, w, cin in ((1, 6, 8, 64), (1, 8, 8, 12), (0, 8, 8, 64), (16, 1024, 1024, 64)):
+        row(w43(dp, b, h, w, cin, dp, N, N, dp, 256, N, N, dp, dq, N), INVALID, shape43 % (b, h, w, cin))
+    for c3 in (0, 48, 288):
+        row(w43(dp, 1, 8, 8, 64, dp, N, N, dp, c3, N, N, dp, dq, N), INVALID,
+            who + ": c3=%d must be a multiple of 32, at most 256" % c3)
+    row(w43(dp, 1, 8, 8, 64, dp, N, N, dp, 256, N, N, dq, dq, N), INVALID, who + ": in-place operation is not supported")
+    assert lib.mrcnn_conv3x3_winograd4_supported(32, 512, 512, 64, 64) and 4 * 32 * 512 * 512 * 256 > OOB
+    row(w43(dp, 32, 512, 512, 64, dp, N, N, dp, 256, N, N, dp, dq, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w43(dp, 1, 6, 8, 64, dp, N, N, dp, 48, N, N, dq, dq, N), INVALID, shape43 % (1, 6, 8, 64))              # first check wins
+    row(w43(dp, 1, 8, 8, 64, dp, N, N, dp, 48, N, N, dq, dq, N), INVALID, who + ": c3=48 must be a multiple of 32, at most 256")
+    row(w43(dp, 32, 512, 512, 64, dp, N, N, dp, 256, N, N, dq, dq, N), INVALID, who + ": in-place operation is not supported")
+
+    # ---- F(2x2) plain: (x, x_layout, B, H, W, Cin, u, Cout, scale, shift, act, y, yk, workspace, workspace_bytes, stream)
+    w2 = lib.mrcnn_conv3x3_winograd_f32
+    who = "conv3x3_winograd"
+    need_ws = who + ": an NHWC input needs a workspace of mrcnn_conv3x3_winograd_workspace_bytes()"
+    row(w2(N, 1, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": null pointer")
+    row(w2(dp, 1, 1, 8, 8, 8, N, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": null pointer")
+    row(w2(dp, 1, 1, 8, 8, 8, dp, 64, N, N, 1, N, N, N, 0, N), INVALID, who + ": null pointer")
+    row(w2(dp, 2, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": bad x_layout")
+    row(w2(dp, 0, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, N, big, N), INVALID, need_ws)
+    row(w2(dp, 0, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, dq, 4 * 8 * 8 * 8 - 1, N), INVALID, need_ws)
+    for b, h, w in ((0, 8, 8), (1, 7, 8), (1, 8, 9), (1, 0, 8)):
+        row(w2(dp, 1, b, h, w, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID,
+            who + ": B=%d H=%d W=%d (even sizes required)" % (b, h, w))
+    for cin, cout in ((12, 64), (0, 64), (8, 0)):
+        row(w2(dp, 1, 1, 8, 8, cin, dp, cout, N, N, 1, dq, N, N, 0, N), INVALID,
+            who + ": Cin=%d (%% 8 == 0 required) Cout=%d" % (cin, cout))
+    row(w2(dp, 1, 1, 8, 8, 8, dp, 12, N, N, 1, N, dq, N, 0, N), INVALID, who + ": a k-blocked output needs Cout % 8 == 0")
+    row(w2(dp, 1, 1, 8, 8, 8, dp, 12, N, N, 2, dq, N, N, 0, N), INVALID, who + ": activation must be 0 or 1")
+    for cin, cout in ((1024, 1000), (8, 1024)):   # 4 B H W Cin, 4 B H W Cout; 64 Cin Cout below
+        row(w2(dp, 1, 4, 512, 512, cin, dp, cout, N, N, 0, dq, N, N, 0, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w2(dp, 1, 1, 8, 8, 8192, dp, 8192, N, N, 0, dq, N, N, 0, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w2(N, 2, 1, 7, 8, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": null pointer")                # first check wins
+    row(w2(dp, 2, 1, 7, 8, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": bad x_layout")
+    row(w2(dp, 0, 1, 7, 8, 8, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, need_ws)
+    row(w2(dp, 1, 1, 7, 8, 12, dp, 64, N, N, 1, dq, N, N, 0, N), INVALID, who + ": B=1 H=7 W=8 (even sizes required)")
+    row(w2(dp, 1, 1, 8, 8, 12, dp, 12, N, N, 1, dq, dq, N, 0, N), INVALID, who + ": Cin=12 (% 8 == 0 required) Cout=12")
+    row(w2(dp, 1, 1, 8, 8, 8, dp, 12, N, N, 2, dq, dq, N, 0, N), INVALID, who + ": a k-blocked output needs Cout % 8 == 0")
+    row(w2(dp, 1, 4, 512, 512, 1024, dp, 1000, N, N, 2, dq, N, N, 0, N), INVALID, who + ": activation must be 0 or 1")
+    # ---- F(2x2), the NHWC form: (x, B, H, W, Cin, u, Cout, scale, shift, act, y, workspace, workspace_bytes, stream): the same checks
+    w2n = lib.mrcnn_conv3x3_winograd_nhwc_f32
+    row(w2n(dp, 1, 8, 8, 8, dp, 64, N, N, 1, N, dq, big, N), INVALID, who + ": null pointer")
+    row(w2n(dp, 1, 8, 8, 8, dp, 64, N, N, 1, dq, N, big, N), INVALID, need_ws)
+    row(w2n(dp, 1, 8, 8, 8, dp, 64, N, N, 1, dq, dq, 4 * 8 * 8 * 8 - 1, N), INVALID, need_ws)
+    row(w2n(dp, 1, 7, 8, 8, dp, 64, N, N, 1, dq, dq, big, N), INVALID, who + ": B=1 H=7 W=8 (even sizes required)")
+    row(w2n(dp, 1, 8, 8, 12, dp, 64, N, N, 1, dq, dq, big, N), INVALID, who + ": Cin=12 (% 8 == 0 required) Cout=64")
+    row(w2n(dp, 1, 8, 8, 8, dp, 64, N, N, 2, dq, dq, big, N), INVALID, who + ": activation must be 0 or 1")
+    row(w2n(dp, 4, 512, 512, 1024, dp, 1000, N, N, 0, dq, dq, big, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w2n(dp, 1, 7, 8, 8, dp, 64, N, N, 2, dq, N, big, N), INVALID, need_ws)                                   # first check wins
+    # ---- F(2x2) heads: (x, B, H, W, Cin, u, Cout, scale, shift, act, w_head, tile_mode, head_part, stream)
+    w2h = lib.mrcnn_conv3x3_winograd_heads_f32
+    who = "conv3x3_winograd_heads"
+    # (a library built with MRCNN_ABLATIONS — it exports the direct-kernel RPN level — also takes tile_mode 1)
+    bad_mode = who + (": tile_mode must be 1, or 2 on maps of at least 8 x 8 tile positions" if hasattr(lib, "mrcnn_rpn_level_fused_f32")
+                      else ": tile_mode must be 2 (8 x 8 position blocks), on maps of at least 8 x 8 tile positions")
+    row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 1, N, 2, dq, N), INVALID, who + ": null pointer")
+    row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 1, dp, 2, N, N), INVALID, who + ": null pointer")
+    row(w2h(dp, 1, 15, 16, 8, dp, 64, N, N, 1, dp, 2, dq, N), INVALID, who + ": B=1 H=15 W=16 (even sizes required)")
+    for cin, cout in ((12, 64), (8, 96), (8, 32)):
+        row(w2h(dp, 1, 16, 16, cin, dp, cout, N, N, 1, dp, 2, dq, N), INVALID,
+            who + ": Cin=%d (%% 8 == 0) Cout=%d (%% 64 == 0) required" % (cin, cout))
+    row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 2, dp, 2, dq, N), INVALID, who + ": activation must be 0 or 1")
+    row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 1, dp, 3, dq, N), INVALID, bad_mode)
+    row(w2h(dp, 1, 16, 14, 8, dp, 64, N, N, 1, dp, 2, dq, N), INVALID, bad_mode)    # 8 x 7 tile positions
+    row(w2h(dp, 16, 512, 512, 256, dp, 512, N, N, 1, dp, 2, dq, N), INVALID, who + ": tensor too large (32-bit buffer byte offsets)")
+    row(w2h(dp, 1, 15, 16, 12, dp, 64, N, N, 1, dp, 2, dq, N), INVALID, who + ": B=1 H=15 W=16 (even sizes required)")   # first wins
+    row(w2h(dp, 1, 16, 16, 12, dp, 64, N, N, 2, dp, 2, dq, N), INVALID, who + ": Cin=12 (% 8 == 0) Cout=64 (% 64 == 0) required")
+    row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 2, dp, 3, dq, N), INVALID, who + ": activation must be 0 or 1")
+    row(w2h(dp, 16, 512, 512, 256, dp, 512, N, N, 1, dp, 3, dq, N), INVALID, bad_mode)
+
+    # ---- the pipelined fp16 conv: (x, B, H, W, Cin, w, Cout, kh, kw, stride, pads t l b r, scale, shift, residual, res_div, act,
+    #      y16, y32, tile_rows, tile_cols, stream). A call that names both tile sizes needs no device query.
+    p8 = lib.mrcnn_conv_f16_pipelined
+    who = "conv_f16_pipelined"
+    unsup = (who + ": needs Cin %% 64 == 0, Cout %% 64 == 0, <= 25 taps, 0 <= pads < kernel, 32-bit byte offsets "
+             "(got %dx%dx%dx%d -> %d, %dx%d stride %d)")
+    row(p8(N, 1, 8, 8, 64, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 1, dq, N, 128, 64, N), INVALID, who + ": null pointer")
+    row(p8(dp, 1, 8, 8, 64, N, 64, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 1, dq, N, 128, 64, N), INVALID, who + ": null pointer")
+    row(p8(dp, 1, 8, 8, 64, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 1, N, N, 128, 64, N), INVALID, who + ": null pointer")
+    row(p8(dp, 1, 8, 8, 64, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 2, dq, N, 128, 64, N), INVALID,
+        who + ": activation must be 0 (none) or 1 (ReLU)")
+    for b, h, w, cin, cout, k, s, pad in ((1, 8, 8, 32, 64, 3, 1, 1), (1, 8, 8, 64, 96, 3, 1, 1), (1, 8, 8, 64, 64, 6, 1, 1),
+                                          (1, 8, 8, 64, 64, 3, 9, 1), (1, 8, 8, 64, 64, 3, 1, 3), (0, 8, 8, 64, 64, 3, 1, 1),
+                                          (8, 512, 512, 256, 256, 3, 1, 1)):
+        row(p8(dp, b, h, w, cin, dp, cout, k, k, s, pad, pad, pad, pad, N, N, N, 1, 1, dq, N, 128, 64, N), UNSUPPORTED,
+            unsup % (b, h, w, cin, cout, k, k, s))
+    row(p8(dp, 1, 8, 8, 64, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, dp, 3, 1, dq, N, 128, 64, N), INVALID,
+        who + ": res_div must be 1, or 2 with even output sizes (got 3, 8x8)")
+    row(p8(dp, 1, 7, 8, 64, dp, 64, 1, 1, 1, 0, 0, 0, 0, N, N, dp, 2, 1, dq, N, 128, 64, N), INVALID,
+        who + ": res_div must be 1, or 2 with even output sizes (got 2, 7x8)")
+    for rows, cols, cout in ((100, 256, 256), (128, 256, 128), (128, 100, 256), (128, 128, 192),
+                             (16, 256, 256), (31, 256, 256), (-5, 256, 256), (-31, 128, 128), (128, 32, 64), (128, -5, 64)):   # x / 32, x / 64 == 0
+        row(p8(dp, 1, 8, 8, 64, dp, cout, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 1, dq, N, rows, cols, N), INVALID,
+            who + ": tile %d x %d does not fit Cout %d" % (rows, cols, cout))
+    for rows, cols, cout in ((160, 128, 128), (192, 64, 64), (96, 256, 256), (128, 192, 192), (128, 512, 512)):
+        row(p8(dp, 1, 8, 8, 64, dp, cout, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 1, dq, N, rows, cols, N), INVALID,
+            who + ": tile must be 0 (auto), rows 128 / 160 / 192 / 256 x 256 columns, or rows 128 / 256 x 128 / 64 columns "
+            "(got %d x %d)" % (rows, cols))
+    row(p8(N, 1, 8, 8, 32, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, N, 1, 2, dq, N, 100, 256, N), INVALID, who + ": null pointer")   # first wins
+    row(p8(dp, 1, 8, 8, 32, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, dp, 3, 2, dq, N, 100, 256, N), INVALID,
+        who + ": activation must be 0 (none) or 1 (ReLU)")
+    row(p8(dp, 1, 8, 8, 32, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, dp, 3, 1, dq, N, 100, 256, N), UNSUPPORTED, unsup % (1, 8, 8, 32, 64, 3, 3, 1))
+    row(p8(dp, 1, 8, 8, 64, dp, 64, 3, 3, 1, 1, 1, 1, 1, N, N, dp, 3, 1, dq, N, 100, 256, N), INVALID,
+        who + ": res_div must be 1, or 2 with even output sizes (got 3, 8x8)")
+    # ---- its heads form: (x, B, H, W, Cin, w, Cout, kh, kw, pads t l b r, scale, shift, act, w_head, head_part, tile_rows, stream)
+    p8h = lib.mrcnn_conv_f16_pipelined_heads
+    who = "conv_f16_pipelined_heads"
+    unsup = (who + ": needs Cin %% 64 == 0, Cout %% 256 == 0, <= 25 taps, 0 <= pads < kernel, 32-bit byte offsets "
+             "(got %dx%dx%dx%d -> %d, %dx%d)")
+    row(p8h(dp, 1, 8, 8, 64, dp, 256, 3, 3, 1, 1, 1, 1, N, N, 1, N, dq, 128, N), INVALID, who + ": null pointer")
+    row(p8h(dp, 1, 8, 8, 64, dp, 256, 3, 3, 1, 1, 1, 1, N, N, 1, dp, N, 128, N), INVALID, who + ": null pointer")
+    row(p8h(dp, 1, 8, 8, 64, dp, 256, 3, 3, 1, 1, 1, 1, N, N, 2, dp, dq, 128, N), INVALID, who + ": activation must be 0 (none) or 1 (ReLU)")
+    for cin, cout, k in ((64, 128, 3), (32, 256, 3), (64, 256, 6)):
+        row(p8h(dp, 1, 8, 8, cin, dp, cout, k, k, 1, 1, 1, 1, N, N, 1, dp, dq, 128, N), UNSUPPORTED, unsup % (1, 8, 8, cin, cout, k, k))
+    for rows in (96, 100, 224, 288, 16, 31, -5):
+        row(p8h(dp, 1, 8, 8, 64, dp, 256, 3, 3, 1, 1, 1, 1, N, N, 1, dp, dq, rows, N), INVALID,
+            who + ": tile_rows must be 0 (auto), 128, 160, 192 or 256")
+    row(p8h(dp, 1, 8, 8, 64, dp, 128, 3, 3, 1, 1, 1, 1, N, N, 2, dp, dq, 96, N), INVALID, who + ": activation must be 0 (none) or 1 (ReLU)")
+    row(p8h(dp, 1, 8, 8, 64, dp, 128, 3, 3, 1, 1, 1, 1, N, N, 1, dp, dq, 96, N), UNSUPPORTED, unsup % (1, 8, 8, 64, 128, 3, 3))
+
+    # ---- the stem: (x, B, H, W, w, scale, shift, act, y, stream), three forms with the same checks
+    for f in (lib.mrcnn_stem_conv7x7_s2_nhwc_f32, lib.mrcnn_stem_conv7x7_s2_nchw_f32, lib.mrcnn_stem_conv7x7_s2_nchw_f16out):
+        row(f(N, 1, 8, 8, dp, N, N, 1, dq, N), INVALID, "stem: null pointer")
+        row(f(dp, 1, 8, 8, N, N, N, 1, dq, N), INVALID, "stem: null pointer")
+        row(f(dp, 1, 8, 8, dp, N, N, 1, N, N), INVALID, "stem: null pointer")
+        for b, h, w in ((0, 8, 8), (1, 7, 8), (1, 8, 9), (1, 0, 8)):
+            row(f(dp, b, h, w, dp, N, N, 1, dq, N), INVALID, "stem: B=%d H=%d W=%d (even sizes required)" % (b, h, w))
+        row(f(dp, 1, 8, 8, dp, N, N, 2, dq, N), INVALID, "stem: activation must be 0 or 1")
+        row(f(dp, 16, 2048, 2048, dp, N, N, 1, dq, N), INVALID, "stem: tensor too large (32-bit buffer byte offsets)")
+        row(f(N, 1, 7, 8, dp, N, N, 2, dq, N), INVALID, "stem: null pointer")                                     # first check wins
+        row(f(dp, 1, 7, 8, dp, N, N, 2, dq, N), INVALID, "stem: B=1 H=7 W=8 (even sizes required)")
+        row(f(dp, 16, 2048, 2048, dp, N, N, 2, dq, N), INVALID, "stem: activation must be 0 or 1")
+    # ---- the stem + pool: (x, B, H, W, w, scale, shift, y, stream); each form with its own size limit
+    for f, who, b_over, note in ((lib.mrcnn_stem_conv7x7_s2_pool_f16, "stem_pool", 86, ""),
+                                 (lib.mrcnn_stem_conv7x7_s2_pool_f32, "stem_pool_f32", 32, ": B*H*W < 2^27 pixels")):
+        row(f(N, 1, 8, 8, dp, N, N, dq, N), INVALID, who + ": null pointer")
+        row(f(dp, 1, 8, 8, N, N, N, dq, N), INVALID, who + ": null pointer")
+        row(f(dp, 1, 8, 8, dp, N, N, N, N), INVALID, who + ": null pointer")
+        for b, h, w in ((0, 8, 8), (1, 6, 8), (1, 8, 10), (1, 0, 8)):
+            row(f(dp, b, h, w, dp, N, N, dq, N), INVALID, who + ": B=%d H=%d W=%d (multiples of 4 required)" % (b, h, w))
+        too_large = who + ": tensor too large (32-bit buffer byte offsets%s)" % note
+        row(f(dp, b_over, 2048, 2048, dp, N, N, dq, N), INVALID, too_large)
+        row(f(N, 1, 6, 8, dp, N, N, dq, N), INVALID, who + ": null pointer")                                      # first check wins
+        row(f(dp, b_over, 2046, 2048, dp, N, N, dq, N), INVALID, who + ": B=%d H=2046 W=2048 (multiples of 4 required)" % b_over)
+
+
 def test_refine_stage_entry_points_refuse_bad_arguments():
     """Argument validation of the selection / glue / RoIAlign entry points runs before any HIP call (dummy pointers, never
     touched): each refusal with its message."""

@@ -21,6 +21,22 @@ def dev():
     return torch.device("cuda:0")
 
 
+def _over_the_clamp(per_cu=1, multiple_of=1):
+    """The persistent launchers start min(units, per_cu * CUs) workgroups (CUs rounded down to whole XCDs where the launcher
+    says so) and let a workgroup walk the units beyond its own. The small shapes of this file never reach that clamp; each
+    launcher has one case with a width (or RoI count) of 0, which stands for "what puts the launcher just over its clamp on
+    this device": one row of tiles, as many of them as this returns. The count is taken from the device's CU count, lies
+    between one and two times the clamp and is no multiple of 8, so some workgroups walk two units, others one. "Units" are
+    the tiles (work items) of the case; the Winograd and Bottleneck launchers round them up to whole groups of 8 (one per
+    XCD) before they clamp, which only moves the count further over."""
+    clamp = per_cu * torch.cuda.get_device_properties(0).multi_processor_count
+    units = (clamp // multiple_of + 1) * multiple_of
+    while units % 8 == 0 or units < clamp + 4:
+        units += multiple_of
+    assert clamp < units < 2 * clamp, (units, clamp)
+    return units
+
+
 def _ref_conv(x_nchw, w_oihw, scale, shift, stride, pad, relu, residual_nchw=None, res_div=1):
     pt, pl, pb, pr = pad
     y = F.conv2d(F.pad(x_nchw, (pl, pr, pt, pb)), w_oihw, None, stride=stride)
@@ -253,6 +269,8 @@ WINO_CASES = [
     (1, 32, 48, 24, 40, True, True),      # non-square, three k tiles
     (3, 16, 16, 512, 64, True, True),     # long K
     (1, 6, 10, 16, 70, True, True),       # FPN P5 of the 192x320 configuration
+    (1, 8, 0, 8, 64, True, True),         # over the clamp (width 0: _over_the_clamp), 4 positions high: always linear tiles
+    (1, 16, 0, 8, 64, True, True),        # over the clamp, 8 positions high: one row of 8 x 8 blocks (or as many linear tiles)
 ]
 
 
@@ -260,6 +278,9 @@ WINO_CASES = [
 def test_conv3x3_winograd_vs_torch_cpu(dev, case):
     from maskrcnn_amd import ops
     b, h, w, cin, cout, relu, affine = case
+    if w == 0:   # 64 positions per M tile either way: 4 x 16 (linear) or 8 x 8 (a block, or 64 consecutive positions of 8 rows)
+        w = (32 if h == 8 else 16) * _over_the_clamp()
+        case = (b, h, w, cin, cout, relu, affine)
     g = torch.Generator().manual_seed(hash(case) % (2 ** 31))
     x = torch.randn(b, cin, h, w, generator=g)
     wt = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
@@ -392,7 +413,9 @@ def test_stem_kernel_vs_generic_and_torch(dev):
     inside a tap differs, so equality is to rounding) and against torch CPU (1e-4), incl. ragged tiles and batch > 1."""
     from maskrcnn_amd import ops
     g = torch.Generator().manual_seed(41)
-    for (b, h, w) in ((2, 64, 64), (1, 38, 70), (3, 32, 16), (1, 2, 2)):
+    for (b, h, w) in ((2, 64, 64), (1, 38, 70), (3, 32, 16), (1, 2, 2), (1, 32, 0)):
+        if w == 0:   # one row of 16 x 16-output tiles, over the clamp of two workgroups per CU
+            w = 32 * _over_the_clamp(per_cu=2)
         x = torch.randn(b, h, w, 4, generator=g)
         x[..., 3] = 0
         wt = torch.randn(64, 7, 7, 4, generator=g) * math.sqrt(2.0 / 147)
@@ -451,7 +474,7 @@ def _ref_bottleneck(x, sd):
     return F.relu(y + x)
 
 
-@pytest.mark.parametrize("shape", [(2, 32, 48), (1, 16, 16), (3, 64, 16), (1, 256, 256)],
+@pytest.mark.parametrize("shape", [(2, 32, 48), (1, 16, 16), (3, 64, 16), (1, 256, 256), (1, 16, 0)],
                          ids=lambda s: "x".join(str(v) for v in s))
 def test_bottleneck_fused_whole_block(dev, shape):
     """One launch for conv1 → conv2 → conv3 + residual (C2 identity blocks): bit-identical to the three-launch path
@@ -459,6 +482,8 @@ def test_bottleneck_fused_whole_block(dev, shape):
     border and in the interior, at sizes from one tile to the full C2 resolution of a 1024^2 image."""
     from maskrcnn_amd import modules, ops
     b, h, w = shape
+    if w == 0:   # one row of 16 x 16-pixel tiles, over the clamp
+        w = 16 * _over_the_clamp()
     g = torch.Generator().manual_seed(900 + h + w)
     sd = _identity_block_sd(g)
     x = torch.randn(b, 256, h, w, generator=g)
@@ -611,7 +636,7 @@ def test_bottleneck_native_call_equals_launch_by_launch(dev, blk):
 
 # (batch, H, W, first block?): the C2 stage in the plain-fp16 mode — one launch per block (csrc/bottleneck_f16.hip)
 F16_C2_BLOCKS = [(2, 64, 64, False), (2, 64, 64, True), (1, 8, 16, False), (1, 8, 16, True), (3, 21, 37, False), (3, 21, 37, True),
-                 (1, 5, 3, False), (2, 208, 336, False), (2, 208, 336, True)]
+                 (1, 5, 3, False), (2, 208, 336, False), (2, 208, 336, True), (1, 8, 0, False)]
 
 
 @pytest.mark.parametrize("blk", F16_C2_BLOCKS, ids=lambda c: "x".join(str(int(v)) for v in c))
@@ -624,6 +649,8 @@ def test_bottleneck_c2_f16_one_launch(dev, blk):
     a batch == image i alone, a repeat == bit for bit. Ragged tiles (8 x 16 pixels), one-tile and sub-tile maps, configs[4]'s size."""
     from maskrcnn_amd import modules, ops
     b, h, w, first = blk
+    if w == 0:   # one row of 8 x 16-pixel tiles, over the clamp
+        w = 16 * _over_the_clamp()
     cin = 64 if first else 256
     g = torch.Generator().manual_seed(2000 + h * 7 + w + cin)
     sd = _block_sd(g, cin, 64, first)
@@ -672,8 +699,8 @@ def test_bottleneck_c2_f16_rejects_other_blocks(dev):
                               c2.shift, f3, c3.scale, c3.shift)
 
 
-@pytest.mark.parametrize("shape", [(3, 14, 14, 81), (1, 5, 3, 81), (400, 14, 14, 81), (7, 14, 14, 2), (2, 9, 14, 96)],
-                         ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("shape", [(3, 14, 14, 81), (1, 5, 3, 81), (400, 14, 14, 81), (7, 14, 14, 2), (2, 9, 14, 96),
+                                   (0, 16, 16, 81)], ids=lambda s: "x".join(str(v) for v in s))
 def test_mask_tail_f16_one_launch(dev, shape):
     """The "f16" mode's mask-head tail — deconv 2x2 s2 + bias + ReLU -> conv5 1x1 + bias -> sigmoid (model.py:906-914) — as ONE
     launch (mrcnn_mask_tail_f16: the deconv's fp16 map is conv5's MFMA operand in registers) against (a) the two launches it
@@ -683,6 +710,8 @@ def test_mask_tail_f16_one_launch(dev, shape):
     Ragged pixel sets (256 pixels per work item), 400 RoIs (configs[4]), 2 and 96 classes (the store tails)."""
     from maskrcnn_amd import modules, ops
     r, h, w, classes = shape
+    if r == 0:   # a RoI of 16 x 16 pixels is one set of 256 pixels, four work items: over the clamp
+        r = _over_the_clamp(multiple_of=4) // 4
     g = torch.Generator().manual_seed(3000 + r + classes)
     xi = torch.randn(r, 256, h, w, generator=g).half()
     wt = torch.randn(256, 256, 2, 2, generator=g) * math.sqrt(2.0 / 256)     # [Cin, Cout, 2, 2]
@@ -733,10 +762,12 @@ def test_bottleneck_fused_rejects_other_shapes(dev):
 # --------------------------------------------------------------------------------------------------
 # RPN heads inside the Winograd kernel (conv3x3_wino8_f32<heads>)
 # --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(1, 16, 16, 64, 128), (2, 32, 48, 256, 512), (3, 14, 18, 32, 64), (1, 128, 128, 256, 512)],
-                         ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("shape", [(1, 16, 16, 64, 128), (2, 32, 48, 256, 512), (3, 14, 18, 32, 64), (1, 128, 128, 256, 512),
+                                   (1, 16, 0, 8, 64)], ids=lambda s: "x".join(str(v) for v in s))
 def test_winograd_fused_rpn_heads(dev, shape):
     from maskrcnn_amd import ops as _ops
+    if shape[2] == 0:   # one row of 8 x 8-position blocks, over the clamp
+        shape = (shape[0], shape[1], 16 * _over_the_clamp()) + shape[3:]
     if min(shape[1], shape[2]) < 16 and not _ops.HAVE_ABLATIONS:
         # maps under 8 x 8 tile positions would need the linear-tile heads variant: an MRCNN_ABLATIONS build
         xk = torch.zeros(shape[3] // 8, shape[0], shape[1], shape[2], 8, device=dev)
@@ -1042,9 +1073,11 @@ def test_deconv_scatter_ragged_tiles_keep_their_guard_bands(dev):
     (2, 20, 28, 24, 64, True),      # ragged blocks: 5 x 7 positions
     (1, 4, 4, 8, 64, False),        # a single position
     (3, 64, 64, 256, 256, True),    # the FPN smoothing shape at P4 size
+    (1, 4, 0, 8, 64, True),         # over the clamp (width 0: _over_the_clamp): one row of M tiles, 4 of their 16 rows used
 ])
 def test_conv3x3_winograd4_vs_torch_cpu(dev, b, h, w, cin, cout, relu):
     from maskrcnn_amd import ops
+    w = w or 32 * _over_the_clamp()
     g = torch.Generator().manual_seed(b * 1000 + h + cin)
     x = torch.randn(b, h, w, cin, generator=g).clamp_(min=0)          # post-ReLU activations, unit scale
     wt = torch.randn(cout, 3, 3, cin, generator=g) / (9 * cin * 0.5) ** 0.5
@@ -1066,11 +1099,13 @@ def test_conv3x3_winograd4_vs_torch_cpu(dev, b, h, w, cin, cout, relu):
 
 
 @pytest.mark.parametrize("b,h,w,cout", [(1, 16, 32, 128), (2, 32, 64, 128), (2, 20, 28, 128), (1, 64, 64, 128),
-                                        (1, 16, 32, 64), (2, 36, 40, 256)])   # one, two and four N tiles
+                                        (1, 16, 32, 64), (2, 36, 40, 256),    # one, two and four N tiles
+                                        (1, 4, 0, 64)])                       # over the clamp: one row of M tiles
 def test_winograd4_fused_rpn_heads(dev, b, h, w, cout):
     """F(4x4) shared conv + both 1x1 heads in one launch (model.py:605-641) against torch-CPU, then through the
     scores/deltas kernel in its input form 3 against the NHWC form."""
     from maskrcnn_amd import ops
+    w = w or 32 * _over_the_clamp()
     g = torch.Generator().manual_seed(h * 7 + w + cout)
     cin = 64
     x = torch.randn(b, h, w, cin, generator=g).clamp_(min=0)
@@ -1099,13 +1134,14 @@ def test_winograd4_fused_rpn_heads(dev, b, h, w, cout):
 
 
 @pytest.mark.parametrize("b,h,w,cin,c3", [(1, 16, 32, 64, 256), (2, 32, 64, 64, 256), (1, 20, 44, 32, 96), (3, 64, 64, 64, 256),
-                                          (1, 256, 256, 64, 256)])
+                                          (1, 256, 256, 64, 256), (1, 4, 0, 32, 64)])     # the last: over the clamp, one row of M tiles
 def test_winograd4_fused_conv3(dev, b, h, w, cin, c3):
     """conv2 (F(4x4) Winograd, 64 output channels) + conv3 (1x1 expansion + affine + residual + ReLU) in one launch
     (model.py:197-209): the 64-channel map stays in the kernel's epilogue. Bit-identical to conv3x3_winograd4 followed by
     the direct kernel's conv_bn_act with the same residual — one M tile, ragged position blocks (20 x 44), several images,
     the full C2 size — and within 1e-4 abs of torch-CPU; run to run identical."""
     from maskrcnn_amd import ops
+    w = w or 32 * _over_the_clamp()
     g = torch.Generator().manual_seed(4000 + h + w + c3)
     x = torch.randn(b, cin, h, w, generator=g)
     w2 = torch.randn(64, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
@@ -1167,8 +1203,8 @@ def test_streaming_1x1_kernel_bit_identical_to_tiled(dev, cin, cout, relu, kbloc
     assert (y_nhwc.permute(0, 3, 1, 2).cpu() - want).abs().max().item() <= TOL
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 96), (1, 256, 256), (1, 72, 40), (3, 16, 16), (1, 4, 4), (1, 832, 1344)],
-                         ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("shape", [(2, 64, 96), (1, 256, 256), (1, 72, 40), (3, 16, 16), (1, 4, 4), (1, 832, 1344),
+                                   (1, 4, 0)], ids=lambda s: "x".join(str(v) for v in s))
 def test_stem_pool_f16_one_launch(shape):
     """Round 4, the "f16" mode's stem: conv 7x7 s2 + affine + ReLU + SamePad(3,2) + MaxPool(3,2) (model.py:223-229) as ONE launch
     on the fp16 MFMA (stem7x7_s2_pool_f16). Against torch-CPU on the SAME fp16-rounded image and weights (fp32 accumulation,
@@ -1179,6 +1215,7 @@ def test_stem_pool_f16_one_launch(shape):
     from maskrcnn_amd import ops
     dev = torch.device("cuda:0")
     b, h, w = shape
+    w = w or 64 * _over_the_clamp()   # width 0: one row of tiles (16 pooled pixels wide), over the clamp
     g = torch.Generator().manual_seed(h * 7 + w)
     img = torch.randint(0, 256, (b, 3, h, w), generator=g).float() - torch.tensor([123.7, 116.8, 103.9]).view(1, 3, 1, 1)
     wt = torch.randn(64, 3, 7, 7, generator=g) * 0.05
@@ -1212,7 +1249,7 @@ def test_stem_pool_f16_one_launch(shape):
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 96), (1, 256, 256), (1, 72, 40), (3, 16, 16), (1, 4, 4), (1, 60, 132), (2, 1024, 1024),
-                                   (1, 832, 1344)], ids=lambda s: "x".join(str(v) for v in s))
+                                   (1, 832, 1344), (1, 4, 0)], ids=lambda s: "x".join(str(v) for v in s))
 def test_stem_pool_f32_one_launch(shape):
     """Round 5, the exact-fp32 stem: conv 7x7 s2 + affine + ReLU + SamePad(3,2) + MaxPool(3,2) (model.py:223-229) as ONE launch on
     the fp32 MFMA with K = 7 x 21 real values (stem7x7_s2_pool_f32). Against the two launches it replaces (stem7x7_s2_f32 +
@@ -1224,6 +1261,7 @@ def test_stem_pool_f32_one_launch(shape):
     from oracle import oracle
     dev = torch.device("cuda:0")
     b, h, w = shape
+    w = w or 64 * _over_the_clamp()   # width 0: one row of tiles (16 pooled pixels wide), over the clamp
     g = torch.Generator().manual_seed(h * 7 + w)
     img = torch.randint(0, 256, (b, 3, h, w), generator=g).float() - torch.tensor([123.7, 116.8, 103.9]).view(1, 3, 1, 1)
     wt = torch.randn(64, 3, 7, 7, generator=g) * 0.05
