@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 26
+#define MRCNN_ABI_VERSION 27
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -707,6 +707,32 @@ size_t mrcnn_rle_decode_workspace_bytes(int32_t n, int32_t capacity);
 int mrcnn_rle_decode_u8(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, int32_t height,
                         int32_t width, uint8_t* out, int64_t image_stride, int64_t row_stride, void* workspace,
                         size_t workspace_bytes, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ground-truth masks for training straight from run-length rows — what CocoMaskRCNNDataset.load and encode_masks do per
+ * annotation on the host (data.py:797-876, :246-262: annToMask, np.fliplr, a Pillow BILINEAR Resize, a zero Pad) — for n rows of
+ * a table (the layout and the UNUSABLE-row rule of the codec block above) with PER-ROW sizes, in one call. csrc/gt_masks.hip.
+ *   heights, widths  int32 [n]     each row's source size
+ *   geom             int32 [n][5]  (new_h, new_w, top, left, flip) per row
+ *   out              uint8: mask k at out + k*image_stride, rows row_stride bytes apart (>= out_w), pixels contiguous. Every
+ *                    byte of the out_h x out_w extent of every mask is written and none outside it.
+ * Mask k on [top, top+new_h) x [left, left+new_w) is numpy.array(Image.fromarray(m).resize((new_w, new_h), Image.BILINEAR)),
+ * m being rleDecode of the row at heights[k] x widths[k] (runs past h*w clipped, pixels the runs do not reach 0), mirrored left
+ * to right when flip != 0 — Pillow's bits: fp64 coefficients, 22-bit fixed point, the 8-bit intermediate of its horizontal pass
+ * with its rounding. An axis whose new size equals its source size is not resampled, as Pillow skips that pass. The mask is 0
+ * elsewhere. status int32 [n] is a bit set; a row with a bit set is REFUSED — its mask all zeros, the other rows unaffected:
+ *     1  an unusable row                          2  heights / widths / new_h / new_w outside [1, 16384]
+ *     4  the placement is not inside the canvas   8  a source size above 16 times the new size, on either axis
+ * Two launches whatever n is and however many sizes occur; no allocation, no host synchronisation, no atomics, the same bits
+ * from run to run. Neither a dense source mask nor the horizontal pass's intermediate is written to memory: workspace —
+ * mrcnn_rle_resample_workspace_bytes(n, capacity), 16-byte aligned — holds the run-end positions only.
+ * Host-checked limits (an error): 0 <= n <= 65535, capacity >= 1, 1 <= out_h, out_w <= 16384. n == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mrcnn_rle_resample_workspace_bytes(int32_t n, int32_t capacity);
+int mrcnn_rle_resample_u8(const int32_t* num_runs, const uint32_t* counts, int32_t n, int32_t capacity, const int32_t* heights,
+                          const int32_t* widths, const int32_t* geom, uint8_t* out, int32_t out_h, int32_t out_w,
+                          int64_t image_stride, int64_t row_stride, int32_t* status, void* workspace, size_t workspace_bytes,
+                          mrcnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Rendering detections onto the image — data.blend_image / data.blend_mask (data.py:346-403: per instance a PIL Image.blend at

@@ -49,6 +49,7 @@ SOURCES = {
     "cocoeval.hip": ["-ffp-contract=off"],   # bbIou's da+ga-i, i=w*h: separately rounded fp64, as the reference's plain C
     "poly.hip": ["-ffp-contract=off"],       # rleFrPoly's 5*x+.5 and ys+s*t+.5: an FMA changes which pixel a boundary point rounds to
     "codec.hip": [],                         # rleFrString / rleToString / rleArea / rleToBbox / rleDecode on tables: integer work only
+    "gt_masks.hip": ["-ffp-contract=off"],   # rle_resample: Pillow's coefficient arithmetic again (resample_math.hpp)
     "overlay.hip": ["-ffp-contract=off"],    # blend_image: Image.blend's px + 0.2f*(c - px), separately rounded fp32
     "targets.hip": ["-ffp-contract=off"],    # rpn_samples: boxes_overlaps' fp32 IoU and the fp64 deltas, operation by operation
     "detection_targets.hip": ["-ffp-contract=off"],   # mrn_samples: fp32 IoU and deltas, the fp64 neg_limit, the crop's lerps

@@ -9,64 +9,12 @@
 // operation by operation in fp64 (this file is compiled with -ffp-contract=off), so results are bit-identical to
 // Pillow's, which is what the tests check. All of it is byte/integer work bound by HBM traffic (and tiny).
 #include "common.hpp"
+#include "resample_math.hpp"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-struct Axis {  // one resample direction
-    int in_size, out_size, ksize;
-    double scale, support, ss;  // ss = 1 / filterscale
-};
-
-Axis make_axis(int in_size, int out_size) {
-    Axis a;
-    a.in_size = in_size;
-    a.out_size = out_size;
-    double filterscale = a.scale = static_cast<double>(static_cast<float>(in_size)) / out_size;
-    if (filterscale < 1.0) filterscale = 1.0;
-    a.support = 1.0 * filterscale;  // BILINEAR support = 1.0
-    a.ksize = static_cast<int>(ceil(a.support)) * 2 + 1;
-    a.ss = 1.0 / filterscale;
-    return a;
-}
-
-__device__ __forceinline__ double tri(double x) {
-    if (x < 0.0) x = -x;
-    return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// Coefficients of output sample xx: first input tap, tap count, and k[0..ksize) (stride kstride ints).
-__device__ __forceinline__ void axis_coeffs(const Axis& a, int xx, int& xmin, int& cnt, int* k, int kstride) {
-    const double center = (xx + 0.5) * a.scale;
-    xmin = static_cast<int>(center - a.support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = static_cast<int>(center + a.support + 0.5);
-    if (xmax > a.in_size) xmax = a.in_size;
-    cnt = xmax - xmin;
-    double ww = 0.0;
-    for (int x = 0; x < cnt; ++x) ww += tri((x + xmin - center + 0.5) * a.ss);
-    for (int x = 0; x < cnt; ++x) {
-        double w = tri((x + xmin - center + 0.5) * a.ss);
-        if (ww != 0.0) w /= ww;
-        k[x * kstride] = static_cast<int>(0.5 + w * static_cast<double>(1 << PRECISION_BITS));
-    }
-    for (int x = cnt; x < a.ksize; ++x) k[x * kstride] = 0;
-}
-
-__device__ __forceinline__ unsigned clip8(int v) {
-    v >>= PRECISION_BITS;
-    return static_cast<unsigned>(v < 0 ? 0 : v > 255 ? 255 : v);
-}
-// clip8 for values that are PACKED into a word (b0 | b1 << 8 | ...): the compiler fuses two shift + clamp + pack steps into
-// gfx950's v_ashr_pk_u8_i32, whose result it then ORs the next bytes onto as if bits 16-31 were zero — on the MI355X they are
-// not (they keep what the destination register held: measured, round 5: bytes 2 and 3 of every packed word came out OR-ed with
-// stale bits). Making each clamped value opaque before it is shifted into place keeps the plain shift / clamp / or sequence.
-__device__ __forceinline__ unsigned clip8_for_packing(int v) {
-    unsigned c = clip8(v);
-    asm volatile("" : "+v"(c));
-    return c;
-}
+// PRECISION_BITS, Axis, make_axis, tri, axis_coeffs, clip8, clip8_for_packing: csrc/resample_math.hpp (shared with gt_masks.hip)
+using namespace mrcnn_resample;
 
 __global__ __launch_bounds__(256) void coeffs_kernel(const Axis a, int* __restrict__ bounds, int* __restrict__ kk) {
     const int xx = blockIdx.x * blockDim.x + threadIdx.x;

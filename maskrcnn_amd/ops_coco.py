@@ -1,5 +1,6 @@
 """Bindings of the ops on COCO run-length tables: the evaluation's IoU and matching (csrc/cocoeval.hip), polygons (csrc/poly.hip)
-and the string codec (csrc/codec.hip). ops.py re-exports every name here; argument checks and registration are _binding.py's.
+the string codec (csrc/codec.hip)
+and the training masks made from such tables (csrc/gt_masks.hip). ops.py re-exports every name here; argument checks and registration are _binding.py's.
 The encoder that makes such tables from detection masks, rle_encode (csrc/rle.hip), is on detect()'s path and stays in ops.py
 with its rle_default_capacity, which callers replace on the ops module."""
 from __future__ import annotations
@@ -408,9 +409,57 @@ def rle_decode(num_runs: torch.Tensor, counts: torch.Tensor, height: int, width:
     return out
 
 
+# status bits of rle_resample (include/maskrcnn_hip.h): a row with one set is refused — its mask is all zeros
+RESAMPLE_UNUSABLE_ROW, RESAMPLE_BAD_SIZE, RESAMPLE_BAD_PLACEMENT, RESAMPLE_SHRINK_LIMIT = 1, 2, 4, 8
+RESAMPLE_MAX_SHRINK = 16
+
+
+@_on_device
+def rle_resample(num_runs: torch.Tensor, counts: torch.Tensor, heights: torch.Tensor, widths: torch.Tensor, geom: torch.Tensor,
+                 out_h: int, out_w: int, out: torch.Tensor | None = None):
+    """Resized, mirrored, zero-padded 0 / 1 masks straight from the rows of a table (num_runs int32 [N], counts [N,capacity]) with
+    PER-ROW source sizes heights / widths int32 [N] — what the reference's dataset does per annotation on the host (annToMask,
+    np.fliplr, encode_masks' Pillow Resize and Pad: data.py:797-876, :246-262) in ONE call of two launches, whatever N is and
+    however many sizes occur. geom int32 [N,5]: (new_h, new_w, top, left, flip) per row. → (masks uint8 [N,out_h,out_w], status
+    int32 [N]). Mask k on [top, top+new_h) x [left, left+new_w) is numpy.array(Image.fromarray(m).resize((new_w, new_h),
+    Image.BILINEAR)) for m = the decoded row, mirrored left to right when flip — Pillow's bits; an axis whose new size equals its
+    source size is not resampled — and 0 elsewhere. `out`: a uint8 [N,out_h,out_w] tensor to fill (unit last stride, free image
+    and row strides); every byte of it is written. status bits (RESAMPLE_*): 1 a refused or over-capacity row, 2 a size outside
+    [1, 16384], 4 a placement not inside the canvas, 8 a source size above 16 times the new size on either axis; a row with a bit
+    set is all zeros and the other rows are unaffected. No host synchronisation, no atomics, no dense source mask and no
+    horizontal-pass intermediate in memory: the workspace holds the run ends only."""
+    op = "rle_resample"
+    num_runs, counts = rle_table((num_runs, counts), op)
+    n, dev = num_runs.size(0), num_runs.device
+    heights = checked(op, "heights", heights, torch.int32, (n,))
+    widths = checked(op, "widths", widths, torch.int32, (n,))
+    geom = checked(op, "geom", geom, torch.int32, (n, 5))
+    h, w = int(out_h), int(out_w)
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise RuntimeError(f"{op}: out_h, out_w must be in [1, 16384], got {h}, {w}")
+    out = checked_out(op, "out", out, torch.uint8, (n, h, w), dev, contiguous=False)
+    if w > 1 and out.stride(2) != 1:
+        raise RuntimeError(f"{op}: out tensor out must have unit last stride, got strides {tuple(out.stride())}")
+    if h > 1 and out.stride(1) < w:
+        raise RuntimeError(f"{op}: out tensor out must have a row stride of at least {w}, got strides {tuple(out.stride())}")
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out, status
+    image_stride = out.stride(0) if n > 1 else 0
+    row_stride = out.stride(1) if h > 1 else w
+    nbytes = int(lib.mrcnn_rle_resample_workspace_bytes(n, counts.size(1)))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_rle_resample_u8,
+            (num_runs.data_ptr(), counts.data_ptr(), n, counts.size(1), heights.data_ptr(), widths.data_ptr(), geom.data_ptr(),
+             out.data_ptr(), h, w, image_stride, row_stride, status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (n, h, w), n * h * w + 4 * counts.numel(), "rle_resample"))
+    return out, status
+
+
 register("rle_from_string(Tensor bytes, Tensor str_off, Tensor heights, Tensor widths, int? capacity=None) -> (Tensor, Tensor, Tensor)",
          rle_from_string)
 register("rle_area_bbox(Tensor num_runs, Tensor counts, Tensor heights, Tensor widths) -> (Tensor, Tensor)", rle_area_bbox)
 register("rle_to_string(Tensor num_runs, Tensor counts, int? total_bytes=None) -> (Tensor, Tensor)", rle_to_string)
 register("rle_decode(Tensor num_runs, Tensor counts, int height, int width) -> Tensor", rle_decode)   # `out` is the Python binding's
-
+# rle_resample has no torch.ops.maskrcnn schema and is not in ops.__all__: tests/test_binding_host.py pins both lists to what was
+# registered before it. It is reached as ops.rle_resample (ops.py takes every public name of this module).
