@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 27
+#define MRCNN_ABI_VERSION 28
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -425,6 +425,21 @@ int mrcnn_conv_bn_act_rows_f32(const float* x, int32_t batch, int32_t height, in
 /* Rows of the M tile mrcnn_conv_bn_act_rows_f32 gives a layer with `cout` output channels (the skip rule's granularity: a caller
  * that accounts for the work that ran — bench.py's roofline pass — counts tiles of this many rows). */
 int32_t mrcnn_conv_rows_tile_m(int32_t cout);
+/* The kernel instantiation mrcnn_conv_bn_act_f32 / _nhwc_f32 / _rows_f32 / mrcnn_deconv2x2_bias_act_nhwc_f32 launch for these
+ * arguments on a device with `cus` compute units — the dispatcher's own answer (the launchers launch from the same function),
+ * host arithmetic only, no device needed. out_mode: 0 NHWC, 1 the 2x2 transposed-conv scatter (cout = 4 x the deconv's channels,
+ * kh = kw = 1), 2 k-blocked. has_residual / has_row_counts: 0 or 1. Returns -1 for arguments the entry points refuse, else
+ *   bits 0-3   kernel: 0 tiled (conv_igemm_f32), 1 / 2 / 3 streaming 1x1 (conv_pw_stream_f32 for 256 -> <= 64, 64 -> <= 64,
+ *              64 -> <= 256 channels)
+ *   bits 4-7   tile (BM x BN, BK): 0 128x32,32  1 256x64,32  2 256x64,16  3 128x96,32  4 128x128,16  5 128x64,16  6 128x128,32
+ *              7 none (streaming)
+ *   bits 8-11  mode: 0 aligned taps, 1 generic (cin % 32 != 0), 2 pointwise
+ *   bits 12-15 epilogue: 0 plain, 1 residual, 2 half-size residual, 3 sigmoid, 4 2x2 scatter
+ *   bit 16     the two-chain sum over K (K >= 1024 on tiles 0, 5, 6). */
+int32_t mrcnn_conv_route(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh, int32_t kw,
+                         int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right,
+                         int32_t has_residual, int32_t res_div, int32_t activation, int32_t out_mode, int32_t has_row_counts,
+                         int32_t cus);
 int mrcnn_nhwc_to_kblocked_f32(const float* x, int64_t pixels, int32_t channels, float* y, mrcnn_stream_t stream);
 size_t mrcnn_conv3x3_winograd_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin);
 int mrcnn_conv3x3_winograd_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,

@@ -516,30 +516,47 @@ constexpr bool split_tile() {
            (BM == 128 && BN == 32 && WM == 4 && WN == 1 && BK == 32);
 }
 
+// What run_conv_f32 launches for a problem, and nothing else decides it: conv_route_f32 below is the only place that chooses,
+// launch_route the only place that launches. mrcnn_conv_route answers with the same function (packed, see the header).
+//   kernel    0 the tiled conv_igemm_f32; 1, 2, 3 the streaming conv_pw_stream_f32 <32,2,2>, <8,2,2>, <8,8,4>
+//   tile      index into the table below (ROUTE_NO_TILE for the streaming kernel)
+//   mode      0 aligned taps, 1 generic (Cin % 32 != 0), 2 pointwise
+//   epilogue  epilogue_variant(): 0 plain, 1 residual, 2 half-size residual, 3 sigmoid, 4 2x2 scatter (5 fused heads: ablations)
+//   split     the two-chain sum (see SPLIT at the kernel)
+struct ConvRoute {
+    int kernel, tile, mode, epilogue, split;
+};
+constexpr int TILE_128x32 = 0;       // BK 32, waves 4x1
+constexpr int TILE_256x64_K32 = 1;   // BK 32, waves 4x1
+constexpr int TILE_256x64_K16 = 2;   // BK 16, waves 4x1
+constexpr int TILE_128x96 = 3;       // BK 32, waves 4x1
+constexpr int TILE_128x128_K16 = 4;  // BK 16, waves 2x2
+constexpr int TILE_128x64 = 5;       // BK 16, waves 2x2
+constexpr int TILE_128x128_K32 = 6;  // BK 32, waves 2x2
+constexpr int ROUTE_NO_TILE = 7;
+
 template <int BM, int BN, int WM, int WN, int BK>
-int launch_conv(ConvParams p, int mode, hipStream_t stream) {  // mode: 0 aligned taps, 1 generic, 2 pointwise
-    const bool generic = mode == 1;
+int launch_conv(ConvParams p, const ConvRoute& r, hipStream_t stream) {
+    const int mode = r.mode, res = r.epilogue;
     long long grid;
     if (int rc = set_tile_grid<BM, BN>(p, "conv", grid)) return rc;
     constexpr size_t lds = conv_lds_bytes<BM, BN, BK>();
-    const int res = epilogue_variant(p, p.w_head != nullptr);
     const char* name = "conv_igemm_f32";  // what a failed launch is reported as
     auto go = [&](auto kern) -> int { return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv", name, p); };
 #ifdef MRCNN_ABLATIONS
     if constexpr (BM == 128 && BN == 128 && WM == 2 && WN == 2 && BK == 32) {
         if (res == 5) {
-            if (generic) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: fused heads need Cin %% 32 == 0");
+            if (mode == 1) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: fused heads need Cin %% 32 == 0");
             name = "conv_igemm_f32<heads>";
             return go(conv_igemm_f32<BM, BN, WM, WN, BK, 0, 5>);
         }
     }
-#else
-    (void)generic;
 #endif
     if (res == 5) return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: the fused-heads epilogue exists in MRCNN_ABLATIONS builds only");
+    if (r.split && !split_tile<BM, BN, WM, WN, BK>())  // the route and the instantiations must not drift apart
+        return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: the route asks for the two-chain sum on a tile without it");
     if constexpr (split_tile<BM, BN, WM, WN, BK>()) {
-        static const bool no_split = getenv("MRCNN_CONV_NO_SPLIT") != nullptr;   // A/B switch (numerics), read once per process
-        if (p.K >= SPLIT_MIN_K && mode != 1 && res <= 2 && !no_split) {
+        if (r.split) {
             auto by_res_split = [&](auto mode_tag) -> int {
                 constexpr int MD = decltype(mode_tag)::value;
                 return res == 0 ? go(conv_igemm_f32<BM, BN, WM, WN, BK, MD, 0, true>)
@@ -561,6 +578,87 @@ int launch_conv(ConvParams p, int mode, hipStream_t stream) {  // mode: 0 aligne
     return mode == 1 ? by_res(std::integral_constant<int, 1>{})
          : mode == 2 ? by_res(std::integral_constant<int, 2>{})
                      : by_res(std::integral_constant<int, 0>{});
+}
+
+// The dispatcher: every choice between instantiations is made here, from the filled parameter block, whether the call has no
+// padding on any side (`unpadded`), whether it carries row groups (`rows`) and the device's CU count. Host arithmetic only.
+ConvRoute conv_route_f32(const ConvParams& p, bool unpadded, bool rows, int cus) {
+    const int cin = p.Cin, cout = p.Cout, out_mode = p.out_mode;
+    const bool generic = (cin % 32) != 0;
+    static const bool no_pw = mrcnn::tuning_env("MRCNN_CONV_NO_PW") != nullptr;   // tuning aid, read once per process
+    const bool pointwise = !generic && p.KH == 1 && p.KW == 1 && unpadded && !no_pw;
+    const int mode = generic ? 1 : pointwise ? 2 : 0;
+    const int res = epilogue_variant(p, p.w_head != nullptr);
+    static const bool no_split = getenv("MRCNN_CONV_NO_SPLIT") != nullptr;   // A/B switch (numerics), read once per process
+    // K >= SPLIT_MIN_K on one of the three tiles the long-K layers take, aligned-tap or pointwise mode, epilogues 0-2
+    auto tiled = [&](int tile) -> ConvRoute {
+        const bool split_tile = tile == TILE_128x128_K32 || tile == TILE_128x64 || tile == TILE_128x32;
+        return ConvRoute{0, tile, mode, res, (split_tile && p.K >= SPLIT_MIN_K && mode != 1 && res <= 2 && !no_split) ? 1 : 0};
+    };
+    auto streaming = [&](int variant) -> ConvRoute { return ConvRoute{variant, ROUTE_NO_TILE, mode, res, 0}; };
+    static const int force = mrcnn::tuning_env("MRCNN_CONV_TILE") ? atoi(mrcnn::tuning_env("MRCNN_CONV_TILE")) : 0;  // tuning aid
+    // ResNet C2's 1x1 layers without a residual (conv1 256 -> 64 / 64 -> 64, downsample 64 -> 256) on large maps: the streaming
+    // kernel (bit-identical results; chosen by size only because a persistent wave needs several blocks to pipeline)
+    static const bool no_stream = mrcnn::tuning_env("MRCNN_CONV_NO_STREAM") != nullptr;
+    if (pointwise && !no_stream && !rows && p.stride == 1 && !p.residual && p.act <= 1 && out_mode != 1 && p.M >= 131072) {
+        if (cin == 256 && cout > 32 && cout <= 64) return streaming(1);
+        if (cin == 64 && cout > 32 && cout <= 64) return streaming(2);
+        if (cin == 64 && cout > 128 && cout <= 256) return streaming(3);
+    }
+    if (cout <= 32) return tiled(TILE_128x32);
+    // Cout <= 64: 256x64 tile. BK = 16 keeps its LDS at 51 KB (two workgroups per CU; BK = 32 needs 92 KB = one):
+    // measured 3-20 % faster on the C2 layers. The stem (generic K) keeps BK = 32.
+    if (cout <= 64) return (generic || force == 4) ? tiled(TILE_256x64_K32)
+                                                   : tiled(TILE_256x64_K16);
+    // 64 < Cout <= 96 (the mask head's conv5, 256 -> 81 + sigmoid on 313 600 pixels, model.py:913-914): a 128x96 tile — four
+    // waves of 32 rows x 96 columns — instead of a 128-column tile of which 37 % would be padding (MFMA-bound at the padded
+    // width: 0.189 -> 0.151 ms). Same products in the same order: bit-identical (MRCNN_CONV_TILE=1 keeps the 128x128 tile).
+    if (!generic && force == 0 && cout > 64 && cout <= 96) return tiled(TILE_128x96);
+    // (a 256x128 BK16 tile — 25% fewer LDS/global bytes per MFMA — was measured in round 1: no gain over 128x128 even on
+    // the largest layers, 133.5 vs 133.2 TFLOP/s, and a loss on mid-size ones; removed)
+    // 128x128 with BK = 16 (41 KB of LDS: three workgroups per CU) for the shortest K (<= 128) with wide outputs — C3 conv3
+    // (K = 128 -> 512 + residual) and the C2 downsample (K = 64 -> 256): measured in the pipeline against the 128x64 / 128x128 BK32
+    // tiles they used to take, 0.766 -> 0.723 ms over the four C3 layers, 0.199 -> 0.190; every longer-K layer is slower on it
+    // round 4 (in-pipeline per-launch events, MRCNN_CONV_TILE sweeps): the same tile for the mask head's transposed conv (K = 256
+    // -> 4 x 256 channels scattered 2x2: its epilogue is store-bound, three workgroups per CU overlap it better) 0.371 -> 0.351 ms
+    if (!generic && (force == 3 || (force == 0 && ((p.K <= 128 && cout >= 256) || (out_mode == 1 && p.K <= 256 && cout >= 256)))))
+        return tiled(TILE_128x128_K16);
+    // Bottleneck conv3 (1x1 expansion + residual, K = planes <= 256): latency-bound on load -> MFMA -> residual -> store
+    // per tile; a 128x64 BK16 tile (30 KB of LDS, 32 accumulator registers) keeps five workgroups per CU in flight
+    // instead of two: 7 % faster on those layers, slower on everything else (measured per layer, round 1)
+    // The same tile when 128x128 tiles would not even give every CU one workgroup (P5 lateral at batch 8: 128 tiles; 131 ->
+    // 94 us). Same products in the same order per output: the choice never changes a result.
+    const long long tiles128 = ((p.M + 127) / 128) * static_cast<long long>((cout + 127) / 128);
+    const bool underfilled = cout >= 128 && tiles128 < cus;
+    // ... and when even 128x64 tiles give a CU only one workgroup with a long K to walk alone (P5 lateral at batch 8: 256 tiles,
+    // K = 2048: 0.104 ms at 0.56 of its MFMA floor), 128x32 tiles put two on every CU: 0.072 ms (MRCNN_CONV_TILE=5: 128x64)
+    if (!generic && force == 0 && underfilled && p.K >= 1024 &&
+        ((p.M + 127) / 128) * static_cast<long long>((cout + 63) / 64) <= cus)
+        return tiled(TILE_128x32);
+    if (!generic && force != 1 &&
+        (force == 5 || underfilled || (p.K <= 256 && p.residual && p.res_div == 1 && cout >= 128)))
+        return tiled(TILE_128x64);
+    return tiled(TILE_128x128_K32);
+}
+
+// The launch of a route: the one switch from a route to a template instantiation.
+int launch_route(const ConvParams& p, const ConvRoute& r, hipStream_t s) {
+    switch (r.kernel) {
+        case 1: return launch_pw_stream<32, 2, 2>(p, s);
+        case 2: return launch_pw_stream<8, 2, 2>(p, s);
+        case 3: return launch_pw_stream<8, 8, 4>(p, s);
+        default: break;
+    }
+    switch (r.tile) {
+        case TILE_128x32: return launch_conv<128, 32, 4, 1, 32>(p, r, s);
+        case TILE_256x64_K32: return launch_conv<256, 64, 4, 1, 32>(p, r, s);
+        case TILE_256x64_K16: return launch_conv<256, 64, 4, 1, 16>(p, r, s);
+        case TILE_128x96: return launch_conv<128, 96, 4, 1, 32>(p, r, s);
+        case TILE_128x128_K16: return launch_conv<128, 128, 2, 2, 16>(p, r, s);
+        case TILE_128x64: return launch_conv<128, 64, 2, 2, 16>(p, r, s);
+        case TILE_128x128_K32: return launch_conv<128, 128, 2, 2, 32>(p, r, s);
+        default: return mrcnn::fail(MRCNN_ERR_UNSUPPORTED, "conv: no tile %d", r.tile);
+    }
 }
 
 }  // namespace
@@ -585,58 +683,30 @@ static int run_conv_f32(const float* x, int32_t batch, int32_t height, int32_t w
     p.w = w;
     p.w_head = nullptr;
     p.head_n = 0;
-    const long long M = p.M;
-    const bool generic = (cin % 32) != 0;
-    static const bool no_pw = mrcnn::tuning_env("MRCNN_CONV_NO_PW") != nullptr;   // tuning aid, read once per process
-    const bool pointwise = !generic && kh == 1 && kw == 1 && pad_top == 0 && pad_left == 0 && pad_bottom == 0 &&
-                           pad_right == 0 && !no_pw;
-    const int mode = generic ? 1 : pointwise ? 2 : 0;
-    hipStream_t s = mrcnn::as_stream(stream);
-    static const int force = mrcnn::tuning_env("MRCNN_CONV_TILE") ? atoi(mrcnn::tuning_env("MRCNN_CONV_TILE")) : 0;  // tuning aid
-    // ResNet C2's 1x1 layers without a residual (conv1 256 -> 64 / 64 -> 64, downsample 64 -> 256) on large maps: the streaming
-    // kernel (bit-identical results; chosen by size only because a persistent wave needs several blocks to pipeline)
-    static const bool no_stream = mrcnn::tuning_env("MRCNN_CONV_NO_STREAM") != nullptr;
-    if (pointwise && !no_stream && !row_counts && stride == 1 && !residual && relu <= 1 && out_mode != 1 && p.M >= 131072) {
-        if (cin == 256 && cout > 32 && cout <= 64) return launch_pw_stream<32, 2, 2>(p, s);
-        if (cin == 64 && cout > 32 && cout <= 64) return launch_pw_stream<8, 2, 2>(p, s);
-        if (cin == 64 && cout > 128 && cout <= 256) return launch_pw_stream<8, 8, 4>(p, s);
-    }
-    if (cout <= 32) return launch_conv<128, 32, 4, 1, 32>(p, mode, s);
-    // Cout <= 64: 256x64 tile. BK = 16 keeps its LDS at 51 KB (two workgroups per CU; BK = 32 needs 92 KB = one):
-    // measured 3-20 % faster on the C2 layers. The stem (generic K) keeps BK = 32.
-    if (cout <= 64) return (generic || force == 4) ? launch_conv<256, 64, 4, 1, 32>(p, mode, s)
-                                                   : launch_conv<256, 64, 4, 1, 16>(p, mode, s);
-    // 64 < Cout <= 96 (the mask head's conv5, 256 -> 81 + sigmoid on 313 600 pixels, model.py:913-914): a 128x96 tile — four
-    // waves of 32 rows x 96 columns — instead of a 128-column tile of which 37 % would be padding (MFMA-bound at the padded
-    // width: 0.189 -> 0.151 ms). Same products in the same order: bit-identical (MRCNN_CONV_TILE=1 keeps the 128x128 tile).
-    if (!generic && force == 0 && cout > 64 && cout <= 96) return launch_conv<128, 96, 4, 1, 32>(p, mode, s);
-    // (a 256x128 BK16 tile — 25% fewer LDS/global bytes per MFMA — was measured in round 1: no gain over 128x128 even on
-    // the largest layers, 133.5 vs 133.2 TFLOP/s, and a loss on mid-size ones; removed)
-    // 128x128 with BK = 16 (41 KB of LDS: three workgroups per CU) for the shortest K (<= 128) with wide outputs — C3 conv3
-    // (K = 128 -> 512 + residual) and the C2 downsample (K = 64 -> 256): measured in the pipeline against the 128x64 / 128x128 BK32
-    // tiles they used to take, 0.766 -> 0.723 ms over the four C3 layers, 0.199 -> 0.190; every longer-K layer is slower on it
-    // round 4 (in-pipeline per-launch events, MRCNN_CONV_TILE sweeps): the same tile for the mask head's transposed conv (K = 256
-    // -> 4 x 256 channels scattered 2x2: its epilogue is store-bound, three workgroups per CU overlap it better) 0.371 -> 0.351 ms
-    if (!generic && (force == 3 || (force == 0 && ((p.K <= 128 && cout >= 256) || (out_mode == 1 && p.K <= 256 && cout >= 256)))))
-        return launch_conv<128, 128, 2, 2, 16>(p, mode, s);
-    // Bottleneck conv3 (1x1 expansion + residual, K = planes <= 256): latency-bound on load -> MFMA -> residual -> store
-    // per tile; a 128x64 BK16 tile (30 KB of LDS, 32 accumulator registers) keeps five workgroups per CU in flight
-    // instead of two: 7 % faster on those layers, slower on everything else (measured per layer, round 1)
-    // The same tile when 128x128 tiles would not even give every CU one workgroup (P5 lateral at batch 8: 128 tiles; 131 ->
-    // 94 us). Same products in the same order per output: the choice never changes a result.
-    const long long tiles128 = ((p.M + 127) / 128) * static_cast<long long>((cout + 127) / 128);
     int cus;
     if (int rc = mrcnn::query_cus("conv", cus)) return rc;
-    const bool underfilled = cout >= 128 && tiles128 < cus;
-    // ... and when even 128x64 tiles give a CU only one workgroup with a long K to walk alone (P5 lateral at batch 8: 256 tiles,
-    // K = 2048: 0.104 ms at 0.56 of its MFMA floor), 128x32 tiles put two on every CU: 0.072 ms (MRCNN_CONV_TILE=5: 128x64)
-    if (!generic && force == 0 && underfilled && p.K >= 1024 &&
-        ((p.M + 127) / 128) * static_cast<long long>((cout + 63) / 64) <= cus)
-        return launch_conv<128, 32, 4, 1, 32>(p, mode, s);
-    if (!generic && force != 1 &&
-        (force == 5 || underfilled || (p.K <= 256 && p.residual && p.res_div == 1 && cout >= 128)))
-        return launch_conv<128, 64, 2, 2, 16>(p, mode, s);
-    return launch_conv<128, 128, 2, 2, 32>(p, mode, s);
+    const bool unpadded = pad_top == 0 && pad_left == 0 && pad_bottom == 0 && pad_right == 0;
+    return launch_route(p, conv_route_f32(p, unpadded, row_counts != nullptr, cus), mrcnn::as_stream(stream));
+}
+
+// The route run_conv_f32 takes for these arguments on a device of `cus` compute units, packed (see the header); -1 for
+// arguments the entry points refuse. Host arithmetic only: no device is touched.
+extern "C" int32_t mrcnn_conv_route(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
+                                    int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                    int32_t pad_right, int32_t has_residual, int32_t res_div, int32_t activation,
+                                    int32_t out_mode, int32_t has_row_counts, int32_t cus) {
+    static const float token = 0.f;  // fill_common only asks whether there is a residual
+    if (!(out_mode >= 0 && out_mode <= 2) || cus < 1 || (has_row_counts && (has_residual || out_mode != 0))) return -1;
+    ConvParams p;
+    if (fill_common(p, "conv_route", nullptr, batch, height, width, cin, 4, cout, kh, kw, stride, pad_top, pad_left, pad_bottom,
+                    pad_right, nullptr, nullptr, has_residual ? &token : nullptr, res_div, activation, out_mode, nullptr, 4))
+        return -1;
+    p.w = nullptr;
+    p.w_head = nullptr;
+    p.head_n = 0;
+    const bool unpadded = pad_top == 0 && pad_left == 0 && pad_bottom == 0 && pad_right == 0;
+    const ConvRoute r = conv_route_f32(p, unpadded, has_row_counts != 0, cus);
+    return r.kernel | (r.tile << 4) | (r.mode << 8) | (r.epilogue << 12) | (r.split << 16);
 }
 
 extern "C" int mrcnn_conv_bn_act_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width,
@@ -738,7 +808,7 @@ extern "C" int mrcnn_rpn_level_fused_f32(const float* x, int32_t batch, int32_t 
     p.w_head = w_head32;
     p.head_n = head_n;
     hipStream_t s = mrcnn::as_stream(stream);
-    if (int rc = launch_conv<128, 128, 2, 2, 32>(p, 0, s)) return rc;
+    if (int rc = launch_conv<128, 128, 2, 2, 32>(p, ConvRoute{0, TILE_128x128_K32, 0, 5, 0}, s)) return rc;
     const int64_t MC = M * head_n;
     int64_t blocks = (MC + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;

@@ -16,6 +16,7 @@ come back as CPU tensors — there is no CPU arithmetic in this build, and witho
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -372,6 +373,29 @@ def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor | None,
              _ptr(residual), int(res_div), 1 if res_kblocked else 0, int(relu), out.data_ptr(), 1 if out_kblocked else 0,
              _stream()), book)
     return out
+
+
+ConvRoute = collections.namedtuple("ConvRoute", "kernel tile mode epilogue split")
+CONV_KERNELS = ("tiled", "stream_256_64", "stream_64_64", "stream_64_256")
+CONV_TILES = ("128x32k32", "256x64k32", "256x64k16", "128x96k32", "128x128k16", "128x64k16", "128x128k32", None)
+CONV_MODES = ("aligned", "generic", "pointwise")
+CONV_EPILOGUES = ("plain", "residual", "residual_half", "sigmoid", "scatter")
+
+
+def conv_route(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, stride: int = 1, pad=(0, 0, 0, 0),
+               residual: bool = False, res_div: int = 1, activation: int = 0, out_mode: int = 0, row_counts: bool = False,
+               cus: int = 256) -> ConvRoute:
+    """The kernel instantiation conv_bn_act (out_mode 0; 2 = out_kblocked) and deconv2x2 (out_mode 1, cout = 4 x its channels,
+    products = 0) launch for these arguments on a device with `cus` compute units: the dispatcher's own answer
+    (mrcnn_conv_route), as names. Host arithmetic only — no GPU is needed."""
+    pt, pl, pb, pr = [int(v) for v in pad]
+    bits = int(lib.mrcnn_conv_route(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw), int(stride), pt, pl, pb, pr,
+                                    int(bool(residual)), int(res_div), int(activation), int(out_mode), int(bool(row_counts)),
+                                    int(cus)))
+    if bits < 0:
+        raise RuntimeError(f"conv_route: the conv entry points refuse these arguments ({lib.mrcnn_last_error().decode()})")
+    return ConvRoute(CONV_KERNELS[bits & 15], CONV_TILES[(bits >> 4) & 15], CONV_MODES[(bits >> 8) & 15],
+                     CONV_EPILOGUES[(bits >> 12) & 15], bool((bits >> 16) & 1))
 
 
 def rows_executed(counts, rows_per_group: int, m: int, bm: int):
