@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 28
+#define MRCNN_ABI_VERSION 29
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -142,6 +142,40 @@ int mrcnn_roi_align_pyramid_counted_f32(const float* const fm[4], const int32_t 
                                         int32_t depth, const float* rois, const int32_t* roi_batch, int32_t num_rois,
                                         int32_t rois_per_image, const int32_t* roi_counts, int32_t pool, float image_area,
                                         void* out, int32_t out_layout, int32_t* levels_out, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the pyramid RoIAlign to the four maps — what CropFunction.backward -> crop_backward (crop_cpu.cpp:167-265)
+ * amounts to behind roi_align (model.py:276-393), level by level, on channels-last maps and with a FIXED summation order.
+ *
+ *   grad_out   fp32 [num_rois][pool][pool][depth] (NHWC): the gradient of mrcnn_roi_align_pyramid_counted_f32's NHWC output
+ *   grad_fm[l] fp32 [batch][H_l][W_l][depth] (NHWC), l = 0..3 for P2..P5, 16-byte aligned. EVERY byte is written by the call
+ *              (a pixel nothing reaches is +0): the caller does not zero the buffers.
+ *   rois, roi_batch, num_rois, rois_per_image, roi_counts, pool, image_area: exactly as in the forward; the same limits
+ *              (depth % 4 == 0, 1 <= pool <= 1024). The level of a RoI is the forward's (one function, csrc/crop_math.hpp).
+ *   workspace  >= mrcnn_roi_align_pyramid_backward_workspace_bytes(num_rois) bytes of device memory, 16-byte aligned
+ *              (32 bytes per RoI: level, image and footprint). Nothing is allocated by the library.
+ *
+ * The rule, bit for bit. grad_fm[l][b,y,x,c] starts from +0 and is the fp32 sum of the terms crop_cpu_backward
+ * (crop_cpu.cpp:205-263) adds to that element, taken
+ *   1. over the RoIs whose level is l and whose image is b, in ascending RoI index;
+ *   2. within a RoI by bin row, 3. then by bin column,
+ *   4. then by the taps in the order top-left, top-right, bottom-left, bottom-right.
+ * Each term is separately rounded fp32, as the reference computes it: (1 - x_lerp) * ((1 - y_lerp) * g), x_lerp * ((1 - y_lerp) * g),
+ * (1 - x_lerp) * (y_lerp * g), x_lerp * (y_lerp * g). All four taps are replayed, the zero-weight ones of a sample on a grid line
+ * (lo == hi) included: an infinite g gives the reference's NaN there. A bin whose sample lies outside the map (the forward's strict
+ * test) contributes nothing. This is the order of the reference's serial loop over each level's boxes in original order, so the
+ * result equals its CPU backward bit for bit, and it depends neither on the launch geometry, nor on batch, nor on what other
+ * images are in the call: two calls give the same bits.
+ * A RoI in a slot at or past roi_counts[image], or whose roi_batch is outside [0, batch), contributes nothing and its grad_out rows
+ * are never read into the arithmetic (the forward leaves them unwritten: they may hold NaN).
+ * No floating-point atomic, no host synchronisation; two launches whatever num_rois and batch are.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mrcnn_roi_align_pyramid_backward_workspace_bytes(int32_t num_rois);
+int mrcnn_roi_align_pyramid_backward_f32(const float* grad_out, const int32_t fm_h[4], const int32_t fm_w[4], int32_t batch,
+                                         int32_t depth, const float* rois, const int32_t* roi_batch, int32_t num_rois,
+                                         int32_t rois_per_image, const int32_t* roi_counts, int32_t pool, float image_area,
+                                         float* const grad_fm[4], void* workspace, size_t workspace_bytes,
+                                         mrcnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused convolution + bias/BatchNorm affine + residual + ReLU, channels-last, fp32 MFMA implicit

@@ -25,6 +25,8 @@ namespace {
 using mrcnn_crop::Sample;   // crop_math.hpp: make_sample (crop_cpu.cpp:52-61, :82-84) and bilerp (:107-110)
 using mrcnn_crop::make_sample;
 using mrcnn_crop::bilerp;
+using mrcnn_crop::PyramidArgs;
+using mrcnn_crop::roi_level;
 
 // ------------------------------------------------------------------------------------------------
 // NCHW forward (the drop-in signature). grid = (num_boxes, channel slabs), block = 256.
@@ -443,30 +445,7 @@ __global__ __launch_bounds__(256) void crop_backward_nchw(
 // NHWC pyramid forward: grid = num_rois, block = 256 (4 waves). Wave w takes sample points
 // w, w+4, ...; a lane owns 4 consecutive channels (float4), looping over depth in 256-channel steps.
 // ------------------------------------------------------------------------------------------------
-struct PyramidArgs {
-    const float* fm[4];
-    int h[4], w[4];
-};
-
-__device__ __forceinline__ int roi_level(float y1, float x1, float y2, float x2, float image_area) {
-    // model.py:324-338 in fp32: 4 + log2(sqrt(h*w) / (224 / sqrt(area))), round half to even, clamp.
-    // Every fp32 operation of that formula is evaluated CORRECTLY ROUNDED: sqrt, the two divisions and log2 go through
-    // double and are rounded to float once (exact for sqrt and division, 53 >= 2*24 + 2; for log2 up to double's own
-    // error, ~1e-8 of the inputs). torch-CPU's log2 (MKL VML, high-accuracy mode) is correctly rounded on all but
-    // ~1e-4 of its inputs, the device's log2f on far fewer: with log2f 7-11 % of the boxes within a few ulp of a level
-    // boundary k = 2.5 / 3.5 / 4.5 landed one level off (tests/test_gpu_fullsize.py::test_level_boundaries_ulp_sweep).
-    const float h = y2 - y1, w = x2 - x1;
-    const float hw = h * w;
-    const float denom = static_cast<float>(224.0 / static_cast<double>(static_cast<float>(sqrt(static_cast<double>(image_area)))));
-    const float ratio = static_cast<float>(static_cast<double>(static_cast<float>(sqrt(static_cast<double>(hw)))) /
-                                           static_cast<double>(denom));
-    const float k = 4.0f + static_cast<float>(log2(static_cast<double>(ratio)));
-    // NaN (negative area) / -inf (zero area) → the reference's int cast is UB; it lands on level 2
-    if (!(k >= 2.0f)) return 2;
-    if (k >= 5.0f) return 5;
-    return static_cast<int>(rintf(k));
-}
-
+// PyramidArgs and roi_level are crop_math.hpp's: csrc/roi_align_backward.hip assigns levels with the same function.
 __global__ __launch_bounds__(256) void roi_align_pyramid_nhwc(
     PyramidArgs a, int batch, int depth, const float* __restrict__ rois,
     const int* __restrict__ roi_batch, int rois_per_image, int pool, float image_area,

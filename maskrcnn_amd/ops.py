@@ -231,6 +231,33 @@ register("crop(Tensor image, Tensor boxes, Tensor box_index, float extrapolation
          "int crop_height, int crop_width) -> Tensor", crop, cpu=_crop_cpu)
 
 
+class _RoiAlignPyramid(torch.autograd.Function):
+    """roi_align_pyramid's default (fp32 NHWC) output as a function of the four maps: the forward is the one launch of the plain
+    call, the backward is roi_align_pyramid_backward (csrc/roi_align_backward.hip). No gradient for the RoIs: the reference
+    detaches them (model.py:358)."""
+
+    @staticmethod
+    def forward(ctx, rois, pool, image_area, rois_per_image, roi_batch, roi_counts, return_levels, p2, p3, p4, p5):
+        maps = [p2, p3, p4, p5]
+        # grad mode is off in here: the plain call, one launch
+        result = roi_align_pyramid(maps, rois, pool, image_area, rois_per_image, roi_batch, return_levels, roi_counts=roi_counts)
+        ctx.save_for_backward(rois, roi_batch, roi_counts)
+        ctx.call = (int(pool), float(image_area), rois_per_image, p2.size(0), [(m.size(1), m.size(2)) for m in maps])
+        ctx.needs = ctx.needs_input_grad[7:]
+        if return_levels:
+            ctx.mark_non_differentiable(result[1])
+        return result
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, *unused):
+        rois, roi_batch, roi_counts = ctx.saved_tensors
+        pool, image_area, rois_per_image, batch, sizes = ctx.call
+        grads = roi_align_pyramid_backward(grad_out, rois, pool, image_area, batch, sizes, rois_per_image=rois_per_image,  # noqa: F405
+                                           roi_batch=roi_batch, roi_counts=roi_counts)
+        return (None,) * 7 + tuple(g if need else None for g, need in zip(grads, ctx.needs))
+
+
 @_on_device
 def roi_align_pyramid(feature_maps, rois: torch.Tensor, pool: int, image_area: float,
                       rois_per_image: int | None = None, roi_batch: torch.Tensor | None = None,
@@ -244,8 +271,15 @@ def roi_align_pyramid(feature_maps, rois: torch.Tensor, pool: int, image_area: f
     returns the NHWC result rounded to fp16 (the "f16" mode's heads: what their first conv would round the values to).
     roi_counts int32 [images] (with rois_per_image): only the first roi_counts[i] slots of image i hold a RoI; the others are
     skipped and their rows of the output (and of `levels`) are left UNWRITTEN — unspecified values, possibly NaN bit patterns:
-    hand such a tensor only to consumers that skip the same rows (conv_bn_act(row_counts=...))."""
+    hand such a tensor only to consumers that skip the same rows (conv_bn_act(row_counts=...)).
+    Differentiable with respect to the feature maps: with grad mode on, a map that requires grad and the default fp32 NHWC output,
+    the result carries a grad_fn whose backward is roi_align_pyramid_backward — a fixed summation order, the reference's CPU bits,
+    no floating-point atomic. The launch and its result are those of every other call. out_kblocked and out_f16 are inference
+    layouts and stay without a gradient, as do the RoIs (model.py:358)."""
     op = "roi_align_pyramid"
+    if (torch.is_grad_enabled() and not out_kblocked and not out_f16 and len(feature_maps) == 4
+            and any(isinstance(m, torch.Tensor) and m.requires_grad for m in feature_maps)):
+        return _RoiAlignPyramid.apply(rois, pool, image_area, rois_per_image, roi_batch, roi_counts, return_levels, *feature_maps)
     if len(feature_maps) != 4:
         refuse(op, "feature_maps", "the 4 levels P2..P5", len(feature_maps))
     _need_gpu(rois, roi_batch, *feature_maps)

@@ -1,14 +1,14 @@
-"""Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip) and the five
-losses, forward and backward (csrc/losses.hip). ops.py re-exports every name here; argument checks and registration are
-_binding.py's."""
+"""Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip), the five
+losses, forward and backward (csrc/losses.hip), and the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip). ops.py
+re-exports every name here; argument checks and registration are _binding.py's."""
 from __future__ import annotations
 
 import ctypes
 
 import torch
 
-from ._binding import _launch, _on_device, _ptr0, _stream, checked, checked_out, register, workspace
-from ._lib import lib
+from ._binding import _launch, _on_device, _ptr, _ptr0, _stream, checked, checked_out, refuse, register, workspace
+from ._lib import c_i32, c_vp, lib
 
 _I32, _F32 = torch.int32, torch.float32
 _ANCHORS_HINT = " (anchors.pyramid_anchors(cfg, dtype=torch.float64))"
@@ -313,3 +313,66 @@ register("head_loss(Tensor target_class_ids, Tensor num_rois, Tensor target_delt
 register("head_loss_backward(Tensor target_class_ids, Tensor num_rois, Tensor target_deltas, Tensor target_mask, Tensor logits, "
          "Tensor pred_bbox, Tensor pred_masks, Tensor counts, Tensor grad_out) -> (Tensor, Tensor, Tensor)", head_loss_backward)
 
+
+
+# --------------------------------------------------------------------------------------------------
+# Backward of the pyramid RoIAlign to the four FPN maps (csrc/roi_align_backward.hip)
+# --------------------------------------------------------------------------------------------------
+def _map_sizes(who, map_sizes):
+    """Four (H, W) pairs, or the same eight numbers in a row → [(H, W)] * 4."""
+    try:
+        flat = [int(v) for s in map_sizes for v in (s if isinstance(s, (list, tuple, torch.Size)) else (s,))]
+    except TypeError:
+        flat = []
+    if len(flat) != 8 or min(flat) < 1:
+        refuse(who, "map_sizes", "the (H, W) of the 4 levels P2..P5, each >= 1", map_sizes)
+    return list(zip(flat[0::2], flat[1::2]))
+
+
+@_on_device
+def roi_align_pyramid_backward(grad_out: torch.Tensor, rois: torch.Tensor, pool: int, image_area: float, batch: int, map_sizes,
+                               rois_per_image: int | None = None, roi_batch: torch.Tensor | None = None,
+                               roi_counts: torch.Tensor | None = None, out=None):
+    """The gradient of roi_align_pyramid's default output with respect to the four maps; the rule is stated at
+    mrcnn_roi_align_pyramid_backward_f32 in include/maskrcnn_hip.h: per element the reference's crop_backward terms in a fixed
+    order (RoI index, bin row, bin column, tap), so the bits equal the reference's CPU backward and two calls agree.
+    grad_out float32 [R,pool,pool,C] (NHWC), rois float32 [R,4]; pool, image_area, rois_per_image, roi_batch int32 [R] and
+    roi_counts int32 [R / rois_per_image] as the forward took them; batch and map_sizes = [(H_l, W_l)] * 4: the maps' shape →
+    [grad_P2, .., grad_P5], each float32 [batch,H_l,W_l,C] with every element written (+0 where nothing lands). out: the four
+    tensors to write into. Two launches, no floating-point atomic, no host synchronisation."""
+    who = "roi_align_pyramid_backward"
+    sizes = _map_sizes(who, map_sizes)
+    pool, batch = int(pool), int(batch)
+    if not 1 <= pool <= 1024:
+        refuse(who, "pool", "in 1 .. 1024", pool)
+    if batch < 1:
+        refuse(who, "batch", ">= 1", batch)
+    grad_out = checked(who, "grad_out", grad_out, _F32, ("R", pool, pool, "C"), align16=True)
+    r, c, dev = grad_out.size(0), grad_out.size(3), grad_out.device
+    if c < 4 or c % 4:
+        refuse(who, "grad_out", f"float32 [R,{pool},{pool},C] with C a multiple of 4", grad_out)
+    rois = checked(who, "rois", rois, _F32, (r, 4))
+    roi_batch = checked(who, "roi_batch", roi_batch, _I32, (r,), optional=True)
+    rpi = int(rois_per_image or 0)
+    if roi_batch is None and rpi < 1:
+        refuse(who, "rois_per_image", ">= 1 without roi_batch", rois_per_image)
+    if roi_counts is not None:
+        if roi_batch is not None or rpi < 1 or r % rpi:
+            refuse(who, "roi_counts", f"None with roi_batch, or with R ({r}) no multiple of rois_per_image ({rois_per_image})", roi_counts)
+        roi_counts = checked(who, "roi_counts", roi_counts, _I32, (r // rpi,))
+    if out is not None and len(out) != 4:
+        raise RuntimeError(f"{who}: out must hold 4 tensors (the gradients of P2..P5), got {len(out)}")
+    grads = [checked_out(who, f"grad_P{l + 2}", None if out is None else out[l], _F32, (batch, h, w, c), dev)
+             for l, (h, w) in enumerate(sizes)]
+    nbytes = int(lib.mrcnn_roi_align_pyramid_backward_workspace_bytes(r))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_roi_align_pyramid_backward_f32,
+            (_ptr0(grad_out), (c_i32 * 4)(*[h for h, _ in sizes]), (c_i32 * 4)(*[w for _, w in sizes]), batch, c, _ptr0(rois),
+             _ptr(roi_batch), r, rpi, _ptr(roi_counts), pool, float(image_area), (c_vp * 4)(*[g.data_ptr() for g in grads]),
+             ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (r, pool * pool, c), 4 * c * (r * pool * pool + batch * sum(h * w for h, w in sizes)), "roi_align_pyramid_backward"))
+    return grads
+
+
+# roi_align_pyramid_backward has no torch.ops.maskrcnn schema and is not in ops.__all__, as rle_resample: tests/test_binding_host.py
+# pins both lists to what was registered before it. It is reached as ops.roi_align_pyramid_backward.
