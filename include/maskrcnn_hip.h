@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 29
+#define MRCNN_ABI_VERSION 30
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -475,6 +475,73 @@ int32_t mrcnn_conv_route(int32_t batch, int32_t height, int32_t width, int32_t c
                          int32_t has_residual, int32_t res_div, int32_t activation, int32_t out_mode, int32_t has_row_counts,
                          int32_t cus);
 int mrcnn_nhwc_to_kblocked_f32(const float* x, int64_t pixels, int32_t channels, float* y, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Backward of the stride-1 fp32 NHWC convolution with a FROZEN affine and an activation — the layers train_model(layers="heads")
+ * trains (model.py:1010-1016, :1218: fpn.P*, rpn.*, classifier.*, mask.*, BatchNorm in eval mode): gradients for the input, the
+ * weight, the shift and the residual. No gradient of `scale` is produced: BatchNorm is frozen in that stage, and its statistics
+ * are not this library's business. The reference has no kernel for any of this (autograd of nn.Conv2d / BatchNorm2d / ReLU).
+ *
+ * The forward is  pre = scale[co] * conv(x, w) + shift[co] (+ residual),  y = act(pre),  stride 1, pads (pt, pl, pb, pr),
+ * x [B][H][W][Cin], w [Cout][KH][KW][Cin], y [B][OH][OW][Cout]  (mrcnn_conv_bn_act_nhwc_f32). Given dy of y's shape:
+ *
+ *   g       the gradient of pre; every operation a separately rounded fp32 operation:
+ *             activation 0   g = dy          1 (ReLU)   g = y > 0 ? dy : 0          2 (sigmoid)   t = 1 - y; u = y * t; g = dy * u
+ *           g is the residual's gradient at res_div = 1; at res_div = 2 (the FPN's nearest-upsample add) the residual's gradient
+ *           is (g00 + g01) + (g10 + g11) of the 2 x 2 block, in fp32.
+ *   z       g * scale[co] in fp32, or g where scale is NULL, stored with a channel pitch of Cout4 = roundup(Cout, 4), pad channels
+ *           +0. Where no activation, no scale, no row counts and no scatter are involved and Cout % 4 == 0, z is dy itself: pass
+ *           z = NULL and hand dy to the two calls below.
+ *   dshift  [co] = the sum of g over the contributing output pixels, accumulated in fp64 in a fixed order that depends on the
+ *           shape only (a thread's pixels in ascending order, then the threads' partials in index order, in a second launch),
+ *           narrowed to fp32 last. No atomic, no last-block protocol.
+ *   dx      [b,iy,ix,ci] = sum over (ky,kx,co) of z[b, iy+pt-ky, ix+pl-kx, co] * w[co,ky,kx,ci]. It IS the forward:
+ *           mrcnn_conv_bn_act_nhwc_f32 on z as the input [B][OH][OW][Cout4] with the weight
+ *           w'[ci][ky'][kx'][co] = w[co][KH-1-ky'][KW-1-kx'][ci] (co >= Cout: zero), pads (KH-1-pt, KW-1-pl, KH-1-pb, KW-1-pr), no
+ *           affine, no residual, activation 0; a transform kernel writes w' into the workspace on every call (the weights change
+ *           every step). dx equals that forward call on those operands bit for bit: it has the forward's routes and limits, and
+ *           image i does not depend on the rest of the batch. A pad larger than K - 1 is refused.
+ *   dw      [co,ky,kx,ci] = sum over (b,oy,ox) of z[b,oy,ox,co] * x[b, oy+ky-pt, ox+kx-pl, ci], taps outside the image contributing
+ *           nothing. The pixel axis M = B*OH*OW is cut into chunks of L = mrcnn_conv_backward_weights_chunk(...) pixels — a function
+ *           of the shape only, chosen as for a 256-CU part, so the bits do not depend on the device. Inside a chunk an element is
+ *           an fp32 fmaf chain over the chunk's pixels in ascending order (v_mfma_f32_32x32x2_f32); a second launch adds the
+ *           ceil(M / L) chunks' sums in ascending chunk order in fp64 and narrows last. Two calls give the same bits.
+ *   rows    row_counts / rows_per_group as in mrcnn_conv_bn_act_rows_f32: an output row at or past its group's count contributes
+ *           nothing to dw and dshift, its z and g rows are written as zero, and its rows of dy and y — and the x values of its taps
+ *           in dw — are never read into the arithmetic (the forward leaves such rows unwritten: they may hold NaN). dx is then
+ *           zero wherever only such rows land. Not with a residual or the scatter.
+ *   scatter (mrcnn_deconv2x2_bias_act_nhwc_f32): dy and y are [B][2*out_h][2*out_w][cout / 4]; GEMM column (dy*2+dx)*C + co of
+ *           row (b,i,j) is pixel (2i+dy, 2j+dx). mrcnn_conv_act_backward_f32 gathers; after it z [M][cout] is an ordinary 1 x 1
+ *           case and dshift is [cout] = [4*C] (the caller adds the four taps for the bias). Activation 0 or 1.
+ *
+ * mrcnn_conv_act_backward_f32: dy, y (read only with an activation) -> z, g, dresidual2, dshift; each output pointer may be NULL
+ *   (not wanted). out_h, out_w, cout: the GEMM's row map and column count (with scatter: the deconv's input map and 4 * C).
+ *   g fp32 [B][out_h][out_w][cout] (dense pitch, no scatter), dresidual2 fp32 [B][out_h/2][out_w/2][cout] (res_div = 2 only; out_h
+ *   and out_w even). Two launches with dshift, one without, none when every output is NULL.
+ * mrcnn_conv_backward_data_f32: z [B][OH][OW][Cout4] -> dx [B][H][W][Cin]. Two launches.
+ * mrcnn_conv_backward_weights_f32: x, z -> dw [Cout][KH][KW][Cin]. Two launches.
+ * workspace: >= mrcnn_conv_backward_workspace_bytes(...) bytes of device memory, 16-byte aligned, shared by the three calls of a
+ *   layer on one stream (the larger of: the dshift partials, w', ceil(M / L) * Cout * KH*KW*Cin floats of chunk sums, which are
+ *   addressed with 64-bit offsets). The library allocates nothing and never synchronises; the launch counts do not depend on B.
+ * Limits: stride 1, fp32, NHWC, Cin % 4 == 0, Cout >= 1, activation 0 / 1 / 2 in the forward's combinations, every tensor — z
+ *   included — within the forward's 32-bit byte offsets (<= 0xFFFFFFF0 bytes). Outside them: an error before any launch.
+ *   mrcnn_conv_backward_weights_chunk and _workspace_bytes return 0 for arguments the entry points refuse.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_conv_act_backward_f32(const float* dy, const float* y, int32_t batch, int32_t out_h, int32_t out_w, int32_t cout,
+                                const float* scale, int32_t activation, int32_t res_div, int32_t scatter,
+                                const int32_t* row_counts, int32_t rows_per_group, float* z, float* g, float* dresidual2,
+                                float* dshift, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+int mrcnn_conv_backward_data_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* w,
+                                 int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                 int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* z,
+                                    int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                    int32_t pad_right, const int32_t* row_counts, int32_t rows_per_group, float* dw,
+                                    void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_conv_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
+                                           int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
+int32_t mrcnn_conv_backward_weights_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
+                                          int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
 size_t mrcnn_conv3x3_winograd_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin);
 int mrcnn_conv3x3_winograd_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
                                     const float* u, int32_t cout, const float* scale, const float* shift,

@@ -32,6 +32,7 @@ SOURCES = {
     "nms_general.hip": ["-ffp-contract=off"],
     "crop.hip": ["-ffp-contract=off"] + (["-DMRCNN_CROP_STAMPS"] if os.environ.get("MRCNN_CROP_STAMPS") else []),
     "roi_align_backward.hip": ["-ffp-contract=off"],   # crop_backward's terms: w * (v * g) and the running sum, separately rounded fp32
+    "conv_backward.hip": ["-ffp-contract=off"],   # g = dy * (y * (1 - y)) and z = g * scale: separately rounded fp32, as the rule states
     "conv.hip": ABL,
     "conv_f16.hip": [],
     "conv_f16p.hip": [],

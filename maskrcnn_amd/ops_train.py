@@ -1,8 +1,10 @@
 """Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip), the five
-losses, forward and backward (csrc/losses.hip), and the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip). ops.py
-re-exports every name here; argument checks and registration are _binding.py's."""
+losses, forward and backward (csrc/losses.hip), the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip) and the backward
+of the stride-1 conv + frozen affine + activation (csrc/conv_backward.hip). ops.py re-exports every name here; argument checks and
+registration are _binding.py's."""
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import torch
@@ -376,3 +378,119 @@ def roi_align_pyramid_backward(grad_out: torch.Tensor, rois: torch.Tensor, pool:
 
 # roi_align_pyramid_backward has no torch.ops.maskrcnn schema and is not in ops.__all__, as rle_resample: tests/test_binding_host.py
 # pins both lists to what was registered before it. It is reached as ops.roi_align_pyramid_backward.
+
+
+# --------------------------------------------------------------------------------------------------
+# Backward of the stride-1 conv + frozen affine + activation (csrc/conv_backward.hip)
+# --------------------------------------------------------------------------------------------------
+ConvBackward = collections.namedtuple("ConvBackward", "dx dw dshift dresidual z")
+
+
+def conv_backward_chunk(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, pad=(0, 0, 0, 0)) -> int:
+    """The chunk length L of the weight gradient of this layer (mrcnn_conv_backward_weights_chunk): its pixel axis M = B*OH*OW is
+    summed in ceil(M / L) fp32 chains that a second launch adds in fp64. A function of the shape only; host arithmetic."""
+    pt, pl, pb, pr = [int(v) for v in pad]
+    got = int(lib.mrcnn_conv_backward_weights_chunk(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw), pt, pl, pb, pr))
+    if got < 1:
+        raise RuntimeError(f"conv_backward_chunk: the conv backward refuses these arguments ({lib.mrcnn_last_error().decode()})")
+    return got
+
+
+@_on_device
+def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tensor, y: torch.Tensor | None,
+                         scale: torch.Tensor | None = None, pad=(0, 0, 0, 0), act: int = 0, res_div: int = 0, scatter: bool = False,
+                         row_counts: torch.Tensor | None = None, rows_per_group: int = 0, needs=(True, True, True, False)):
+    """The gradients of y = act(scale * conv(x, w) + shift (+ residual)) — conv_bn_act at stride 1, or deconv2x2 with scatter=True
+    (w [4*C,1,1,Cin], grad_out and y [B,2H,2W,C]) — for a FROZEN scale; the rule is stated at mrcnn_conv_act_backward_f32 in
+    include/maskrcnn_hip.h. grad_out and y float32 in the output's shape (y is read only with an activation and may be None without),
+    x float32 [B,H,W,Cin], w float32 [Cout,KH,KW,Cin], scale float32 [Cout] or None; pad, act (0 none, 1 ReLU, 2 sigmoid), row_counts
+    and rows_per_group as the forward took them; res_div 0 (no residual), 1 or 2. needs = (dx, dw, dshift, dresidual) →
+    ConvBackward(dx [B,H,W,Cin], dw as w, dshift [Cout], dresidual [B,OH/res_div,OW/res_div,Cout], z [B,OH,OW,roundup(Cout,4)]);
+    entries not asked for are None (z: when neither dx nor dw is). No gradient of scale: BatchNorm is frozen. dx is the forward
+    kernel on z bit for bit; dw is summed in chunks of conv_backward_chunk(...) pixels, then in fp64; dshift in fp64. Two calls give
+    the same bits. Two launches per gradient, no floating-point atomic, no host synchronisation."""
+    who = "conv_bn_act_backward"
+    act, res_div, scatter, rpg = int(act), int(res_div), bool(scatter), int(rows_per_group)
+    if len(needs) != 4:
+        raise RuntimeError(f"{who}: needs must hold 4 flags (dx, dw, dshift, dresidual), got {len(needs)}")
+    need_dx, need_dw, need_dshift, need_dres = [bool(v) for v in needs]
+    if act not in (0, 1, 2):
+        refuse(who, "act", "0 (none), 1 (ReLU) or 2 (sigmoid)", act)
+    if res_div not in (0, 1, 2):
+        refuse(who, "res_div", "0 (no residual), 1 or 2", res_div)
+    if (res_div or scatter) and act == 2 or res_div and scatter:
+        refuse(who, "act", "0 or 1 with a residual or the scatter, which do not combine either", act)
+    if need_dres and not res_div:
+        refuse(who, "needs", "without dresidual where res_div is 0", tuple(needs))
+    x = checked(who, "x", x, _F32, (("B", 1), ("H", 1), ("W", 1), ("Cin", 4)), align16=True)
+    b, h, wd, cin = x.shape
+    if cin % 4:
+        refuse(who, "x", "float32 [B,H,W,Cin] with Cin a multiple of 4", x)
+    w = checked(who, "w", w, _F32, (("Cout", 1), ("KH", 1), ("KW", 1), cin), align16=True)
+    cout, kh, kw, _ = w.shape
+    pt, pl, pb, pr = [int(v) for v in pad]
+    if scatter and (kh != 1 or kw != 1 or cout % 4 or (pt, pl, pb, pr) != (0, 0, 0, 0)):
+        refuse(who, "w", f"float32 [4*C,1,1,{cin}] without padding for the scatter", w)
+    if min(pt, pl, pb, pr) < 0 or max(pt, pb) > kh - 1 or max(pl, pr) > kw - 1:
+        refuse(who, "pad", f"(top, left, bottom, right) in 0 .. kernel size - 1 = ({kh - 1}, {kw - 1})", (pt, pl, pb, pr))
+    oh, ow = h + pt + pb - kh + 1, wd + pl + pr - kw + 1
+    if oh < 1 or ow < 1:
+        refuse(who, "x", f"float32 [B,H,W,Cin] no smaller than the {kh} x {kw} kernel with its padding", x)
+    out_shape = (b, 2 * h, 2 * wd, cout // 4) if scatter else (b, oh, ow, cout)
+    grad_out = checked(who, "grad_out", grad_out, _F32, out_shape, align16=True)
+    y = checked(who, "y", y, _F32, out_shape, optional=act == 0, align16=True)
+    scale = checked(who, "scale", scale, _F32, (cout,), optional=True)
+    m = b * oh * ow
+    if row_counts is not None:
+        if res_div or scatter or rpg < 1 or m % rpg:
+            refuse(who, "row_counts", f"None with a residual or the scatter, or with rows_per_group ({rows_per_group}) not dividing the "
+                   f"{m} output rows", row_counts)
+        row_counts = checked(who, "row_counts", row_counts, _I32, (m // rpg,))
+    if res_div == 2 and (oh % 2 or ow % 2):
+        refuse(who, "res_div", f"1 for an odd output size ({oh} x {ow})", res_div)
+    shape_args = (b, h, wd, cin, cout, kh, kw, pt, pl, pb, pr)
+    nbytes = int(lib.mrcnn_conv_backward_workspace_bytes(*shape_args))
+    if nbytes < 1:
+        raise RuntimeError(f"{who}: {lib.mrcnn_last_error().decode()}")
+    dev, cout4, n = x.device, -(-cout // 4) * 4, kh * kw * cin
+    ws = workspace(nbytes, dev)
+    need_z = need_dx or need_dw
+    alias = act == 0 and scale is None and row_counts is None and not scatter and cout % 4 == 0     # z is grad_out itself
+    g_is_dy = act == 0 and row_counts is None
+    z = g = dres2 = dshift = None
+    if need_z:
+        z = grad_out if alias else torch.empty(b, oh, ow, cout4, dtype=_F32, device=dev)
+    if need_dres and res_div == 1:
+        g = grad_out if g_is_dy else torch.empty(b, oh, ow, cout, dtype=_F32, device=dev)
+    if need_dres and res_div == 2:
+        dres2 = torch.empty(b, oh // 2, ow // 2, cout, dtype=_F32, device=dev)
+    if need_dshift:
+        dshift = torch.empty(cout, dtype=_F32, device=dev)
+    z_out, g_out = (None if alias else z), (None if g_is_dy else g)
+    if z_out is not None or g_out is not None or dres2 is not None or dshift is not None:
+        _launch(lib.mrcnn_conv_act_backward_f32,
+                (grad_out.data_ptr(), _ptr(y), b, oh, ow, cout, _ptr(scale), act, 2 if dres2 is not None else min(res_div, 1),
+                 int(scatter), _ptr(row_counts), rpg, _ptr(z_out), _ptr(g_out), _ptr(dres2), _ptr(dshift), ws.data_ptr(), nbytes,
+                 _stream()),
+                lambda: (0, (m, cout, 1), 4 * m * (2 * cout + cout4), "conv_act_backward"))
+    dx = dw = None
+    if need_dx:
+        dx = torch.empty(b, h, wd, cin, dtype=_F32, device=dev)
+        _launch(lib.mrcnn_conv_backward_data_f32,
+                (z.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, pt, pl, pb, pr, dx.data_ptr(), ws.data_ptr(), nbytes,
+                 _stream()),
+                lambda: (2.0 * m * n * cout, (b * h * wd, cin, kh * kw * cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()),
+                         "conv_backward_data"))
+    if need_dw:
+        dw = torch.empty(cout, kh, kw, cin, dtype=_F32, device=dev)
+        chunks = -(-m // int(lib.mrcnn_conv_backward_weights_chunk(*shape_args)))
+        _launch(lib.mrcnn_conv_backward_weights_f32,
+                (x.data_ptr(), b, h, wd, cin, z.data_ptr(), cout, kh, kw, pt, pl, pb, pr, _ptr(row_counts), rpg, dw.data_ptr(),
+                 ws.data_ptr(), nbytes, _stream()),
+                lambda: (2.0 * m * n * cout, (cout, n, m), 4 * (x.numel() + m * cout4 + (2 * chunks + 1) * n * cout),
+                         "conv_backward_weights"))
+    return ConvBackward(dx, dw, dshift, dres2 if res_div == 2 else g, z)
+
+
+# conv_bn_act_backward has no torch.ops.maskrcnn schema and is not in ops.__all__ either, for the same reason. The differentiable
+# front end is maskrcnn_amd.layers.
