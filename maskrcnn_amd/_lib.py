@@ -19,8 +19,6 @@ PKG =os.path.dirname(os.path.abspath(__file__))
 # which never overwrites the product file). Same ABI check, same no-fallback rule.
 LIB_PATH = os.environ.get("MRCNN_LIB") or os.path.join(PKG, "libmaskrcnn_hip.so")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "maskrcnn_hip.h")
-# Entry points of MRCNN_ABLATIONS builds only: bound when the loaded library has them.
-ABLATIONS_HEADER = os.path.join(os.path.dirname(PKG), "include", "maskrcnn_hip_ablations.h")
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -90,10 +88,6 @@ def _load() -> ctypes.CDLL:
         except AttributeError as e:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in header_prototypes(ABLATIONS_HEADER).items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype, fn.argtypes = res, args
     # a stale .so with the same symbol names but older argument lists would be called with mismatched ctypes
     # arguments (memory corruption / GPU fault): MRCNN_ABI_VERSION is bumped on every signature change
     built, want = int(lib.mrcnn_abi_version()), header_abi_version()

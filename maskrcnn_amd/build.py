@@ -21,9 +21,6 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libmaskrcnn_hip.so")
 ARCH = "gfx950"
 
-# MRCNN_ABLATIONS=1: also build the kernels that lost their A/B measurements (four-wave F(2x2) Winograd kernel, linear-tile
-# heads variant, direct-kernel fused RPN level: include/maskrcnn_hip_ablations.h) and the F(4x4) kernel's timing variants
-ABL = ["-DMRCNN_ABLATIONS"] if os.environ.get("MRCNN_ABLATIONS") else []
 # per-source extra flags. nms/crop reproduce the reference's separately-rounded fp32 arithmetic:
 # never let the compiler contract a*b+c into an FMA there.
 SOURCES = {
@@ -33,11 +30,12 @@ SOURCES = {
     "crop.hip": ["-ffp-contract=off"] + (["-DMRCNN_CROP_STAMPS"] if os.environ.get("MRCNN_CROP_STAMPS") else []),
     "roi_align_backward.hip": ["-ffp-contract=off"],   # crop_backward's terms: w * (v * g) and the running sum, separately rounded fp32
     "conv_backward.hip": ["-ffp-contract=off"],   # g = dy * (y * (1 - y)) and z = g * scale: separately rounded fp32, as the rule states
-    "conv.hip": ABL,
+    "conv.hip": [],
     "conv_f16.hip": [],
     "conv_f16p.hip": [],
-    "conv_wino.hip": ABL,
-    "conv_wino4.hip": (["-DMRCNN_W4_ABLATIONS"] if (os.environ.get("MRCNN_W4_ABLATIONS") or os.environ.get("MRCNN_ABLATIONS")) else [])
+    "conv_wino.hip": [],
+    # MRCNN_W4_ABLATIONS=1: also build the F(4x4) kernel's timing variants
+    "conv_wino4.hip": (["-DMRCNN_W4_ABLATIONS"] if os.environ.get("MRCNN_W4_ABLATIONS") else [])
                       + ([f"-DMRCNN_W4_WALK_SHIFT={int(os.environ['MRCNN_W4_WALK_SHIFT'])}"] if os.environ.get("MRCNN_W4_WALK_SHIFT") else []),
     "stem.hip": [],
     "bottleneck.hip": [],

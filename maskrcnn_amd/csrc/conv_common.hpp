@@ -7,6 +7,27 @@ namespace mrcnn_conv {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+// Two-lane packed fp32 add / subtract / fma (the Winograd kernels' transforms): ONE VALU issue for both channels of a pair (the
+// compiler scalarises a float2 subtraction into two v_add_f32 with a negate modifier; beside the fp32 MFMA every VALU instruction
+// in the loop is paid for).
+__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {  // a * b + c
+    f32x2 r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 
 constexpr unsigned OOB = 0xFFFFFFF0u;  // byte offset beyond every buffer descriptor's num_records
 // The largest byte size of a tensor addressed through one buffer descriptor. A descriptor's num_records must not pass OOB, or a
@@ -61,9 +82,9 @@ __device__ __forceinline__ bool tile_has_rows(const ConvCommon& p, int m0, int B
 
 // Epilogue variants (template parameter RES of the kernels):
 //   0 plain, 1 residual of the output's size, 2 residual at half size (FPN nearest-upsample-add),
-//   3 sigmoid (no residual), 4 2x2 stride-2 transposed-conv scatter (no residual), 5 fused 1x1 heads (conv.hip)
-inline int epilogue_variant(const ConvCommon& p, bool fused_heads) {
-    return fused_heads ? 5 : p.out_mode == 1 ? 4 : (p.act == 2 ? 3 : (p.residual ? p.res_div : 0));
+//   3 sigmoid (no residual), 4 2x2 stride-2 transposed-conv scatter (no residual)
+inline int epilogue_variant(const ConvCommon& p) {
+    return p.out_mode == 1 ? 4 : (p.act == 2 ? 3 : (p.residual ? p.res_div : 0));
 }
 
 // Output pixel m -> (image b, row oy, column ox). Every layer of the 1024^2 / 832x1344 pyramids has power-of-two or small
@@ -219,7 +240,7 @@ template <int TM, int TN, int WTM, int WTN, int RES>
 __device__ __forceinline__ void epilogue(const ConvCommon& p, f32x16 (&acc)[TM][TN],
                                          const ResidualRegs<TM, TN, RES>& rv, int m0, int n0, int wm, int wn,
                                          int lane, const AffineRegs<TN>* pre = nullptr) {
-    static_assert(RES >= 0 && RES <= 4, "variant 5 (fused heads) lives in conv.hip");
+    static_assert(RES >= 0 && RES <= 4, "epilogue variants 0-4 (epilogue_variant())");
     const int ln = lane & 31, lh = lane >> 5;
     const int ohw = p.OH * p.OW;
     const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);

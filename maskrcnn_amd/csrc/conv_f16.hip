@@ -389,7 +389,7 @@ int launch(ConvParamsH p, bool generic, hipStream_t stream) {
     long long grid;
     if (int rc = set_tile_grid<BM, BN>(p, "conv_f16", grid)) return rc;
     constexpr size_t lds = lds_bytes<BM, BN, PRODUCTS>();
-    const int res = epilogue_variant(p, false);
+    const int res = epilogue_variant(p);
     auto go = [&](auto kern) -> int { return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv_f16", "conv_igemm_f16", p); };
     if (generic)
         return res == 0 ? go(conv_igemm_f16<BM, BN, WM, WN, PRODUCTS, true, 0>)
@@ -411,7 +411,7 @@ int launch16(ConvParamsH p, bool generic, bool in16, bool out16, hipStream_t str
     long long grid;
     if (int rc = set_tile_grid<BM, BN>(p, "conv_f16", grid)) return rc;
     constexpr size_t lds = lds_bytes<BM, BN, 1>();
-    const int res = epilogue_variant(p, false);
+    const int res = epilogue_variant(p);
     auto go = [&](auto kern) -> int {
         return mrcnn::launch_kernel(kern, grid, 256, lds, stream, "conv_f16", "conv_igemm_f16<io16>", p);
     };

@@ -8,12 +8,12 @@
 //
 //   GEMM view   16 independent products, one per transform component xi: M_xi[T x N] = V_xi[T x C] U_xi[C x N],
 //               T = B*(H/2)*(W/2) tile positions, N = Cout, C = Cin. U is transformed once by wino_weights_kernel.
-//   tile        a workgroup owns 64 consecutive tile positions x 64 output channels (128 KB of LDS: V and U, 16 component
-//               planes each, double-buffered; one workgroup per CU). Two kernels share everything but the wave layout:
-//               conv3x3_wino8_f32 (default): 512 threads, wave w owns components 2w, 2w+1 for the whole tile (128
-//               accumulator registers, two waves per SIMD), persistent workgroups;
-//               conv3x3_wino_f32 (MRCNN_WINO_WAVES=4): 256 threads, wave w owns components 4w..4w+3 (256 accumulator
-//               registers in AGPRs, one wave per SIMD).
+//   tile        a workgroup owns 64 tile positions x 64 output channels (128 KB of LDS, double-buffered; one persistent
+//               workgroup per CU): 512 threads, wave w owns components 2w, 2w+1 for the whole tile (128 accumulator
+//               registers, two waves per SIMD). Two kernels with the same tile walk, MFMA order and epilogue, hence the same
+//               bits: conv3x3_wino8_f32 takes 64 consecutive positions and stages the transformed input V (described
+//               here; maps under 16 x 16); conv3x3_wino8s_f32 takes an 8 x 8 block of one image and stages the raw input
+//               (described at the kernel; everything else, and the RPN's fused heads).
 //   layouts     both operands are k-blocked: x as [Cin/8][B*H*W][8] (an NHWC input costs one kblock_kernel pass; producers
 //               can write it directly), U as [Cin/8][16][Cout][8], so that a k tile's loads use whole cache lines.
 //   staging     per k tile of 8 input channels a thread fetches a position's 4x4 patch for one channel pair (16 x 8-byte
@@ -46,7 +46,7 @@ struct WinoParams {
     unsigned x_plane, u_plane, yk_plane;  // bytes per 8-channel plane of x / u / the k-blocked output
     int tiles_m, tiles_n;
     unsigned x_bytes, u_bytes, y_bytes;
-    // fused 1x1 heads (conv3x3_wino8_f32<true>): w_head [32][Cout] (rows >= the real head count are zero);
+    // fused 1x1 heads (conv3x3_wino8s_f32<true>): w_head [32][Cout] (rows >= the real head count are zero);
     // head_part [2 k halves][tiles_m * 256 pixel rows in position-major order][32] partial sums
     const float* w_head;
     float* head_part;
@@ -60,290 +60,14 @@ constexpr int PLANE = WT * WK;  // floats per component plane (V and U alike: WT
 constexpr size_t WINO_LDS = sizeof(float) * 2 * 2 * 16 * PLANE;  // {V,U} x 2 buffers x 16 components = 128 KiB
 constexpr size_t WINO_HEADS_LDS = WINO_LDS + sizeof(float) * 128 * WN;  // + the transposed tile of a round: 160 KiB
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// Two-lane packed fp32 add / subtract: ONE VALU issue for both channels of the pair (the compiler scalarises a float2
-// subtraction into two v_add_f32 with a negate modifier; on this MFMA every VALU instruction in the loop is paid for).
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-#ifdef MRCNN_ABLATIONS   // the four-wave kernel of round 1 (one wave per SIMD): an ablation build only (MRCNN_WINO_WAVES=4)
-__global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const WinoParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Vs = smem;                    // [2 buffers][16 components][2 quads][WT][4]
-    float* Us = smem + 2 * 16 * PLANE;   // [2 buffers][16 components][2 quads][WN][4]
-
-    ConvCommon tc;  // only the fields tile_origin reads
-    tc.tiles_m = p.tiles_m;
-    tc.tiles_n = p.tiles_n;
-    int m0, n0, nt;
-    if (!tile_origin(tc, WT, WN, m0, n0, nt)) return;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ln = lane & 31, lh = lane >> 5;
-
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.u_bytes, 0x00020000);
-
-    // ---- staging bookkeeping. On this MFMA every VALU instruction costs its four issue cycles on top of the MFMA
-    // time (measured: tools/mfma_valu_probe.hip — no co-execution, within a wave or across waves), so the loop
-    // carries no address arithmetic at all: per-thread byte offsets are fixed for the whole tile (voffset, out of
-    // range where the load must return zeros), the k tile's plane is the scalar soffset, LDS addresses are one base
-    // register plus instruction-immediate offsets, and the transform is spread evenly over all four waves.
-    //   V: thread = (position tid >> 2, channel pair tid & 3): sixteen 8-byte patch loads; a wave-level load covers 16
-    //      pixels x 32 contiguous bytes = 8 cache lines (a position per lane would touch 32)
-    //   U: eight 16-byte slots of the 16 x 64 x 8 block
-    unsigned voff[16], uoff[8];
-    {
-        const int pos = tid >> 2, pair = tid & 3;  // four lanes = the 32 contiguous bytes of one pixel's k tile
-        const int P = m0 + pos;
-        const bool pv = P < p.T;
-        const int PP = pv ? P : 0;
-        const int b = PP / (p.TH * p.TW), rem = PP - b * p.TH * p.TW;
-        const int ty = rem / p.TW, tx = rem - ty * p.TW;
-        const int iy0 = 2 * ty - 1, ix0 = 2 * tx - 1;
-#pragma unroll
-        for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 4; ++dx) {
-                const int iy = iy0 + dy, ix = ix0 + dx;
-                const bool ok = pv && static_cast<unsigned>(iy) < static_cast<unsigned>(p.H) &&
-                                static_cast<unsigned>(ix) < static_cast<unsigned>(p.W);
-                voff[dy * 4 + dx] = ok ? static_cast<unsigned>(((b * p.H + iy) * p.W + ix) * WK + pair * 2) * 4u : OOB;
-            }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int id = tid + 256 * i;  // float4 id inside the 16 x 64 x 8 block
-            const int xi = id >> 7, r = id & 127, q = r >> 6, ch = r & 63;
-            const int n = n0 + ch;
-            uoff[i] = n < p.Cout ? static_cast<unsigned>((xi * p.Cout + n) * WK + q * 4) * 4u : OOB;
-        }
-    }
-    // LDS float offsets inside a buffer: V component xi at v_lds + xi*PLANE; U slot i at u_lds + i*2*PLANE
-    // (id = tid + 256*i: xi = 2i + (tid >> 7), so consecutive slots are two planes apart)
-    const int v_lds = ((tid & 3) >> 1) * (WT * 4) + (tid >> 2) * 4 + (tid & 1) * 2;
-    const int u_lds = (tid >> 7) * PLANE + ((tid & 127) >> 6) * (WN * 4) + (tid & 63) * 4;
-
-    const int nk = (p.Cin + WK - 1) / WK;
-    f32x2 vl[16];  // raw patch of the k tile in flight
-    u32x4 ul[8];
-    auto plane_of = [&](int kt) { return static_cast<unsigned>(kt < nk ? kt : nk - 1); };  // past the end: reload, unused
-    auto v_load = [&](int i, int kt) {
-        const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, static_cast<int>(voff[i]),
-                                                             static_cast<int>(plane_of(kt) * p.x_plane), 0);
-        vl[i] = f32x2{__uint_as_float(r.x), __uint_as_float(r.y)};
-    };
-    auto u_load = [&](int i, int kt) {
-        ul[i] = __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, static_cast<int>(uoff[i]),
-                                                      static_cast<int>(plane_of(kt) * p.u_plane), 0);
-    };
-    // V = B^T d B on two channels at a time, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: first down the columns
-    // (t), then along the rows (one output component at a time)
-    f32x2 t[4][4];
-    auto column_pass = [&](int dx) {
-        const f32x2 d0 = vl[0 * 4 + dx], d1 = vl[1 * 4 + dx], d2 = vl[2 * 4 + dx], d3 = vl[3 * 4 + dx];
-        t[0][dx] = pk_sub(d0, d2);
-        t[1][dx] = pk_add(d1, d2);
-        t[2][dx] = pk_sub(d2, d1);
-        t[3][dx] = pk_sub(d1, d3);
-    };
-    auto v_comp = [&](int xi) {
-        const int i = xi >> 2, j = xi & 3;
-        return j == 0 ? pk_sub(t[i][0], t[i][2]) : j == 1 ? pk_add(t[i][1], t[i][2])
-             : j == 2 ? pk_sub(t[i][2], t[i][1]) : pk_sub(t[i][1], t[i][3]);
-    };
-    auto v_store = [&](int xi, float* vbuf) { *reinterpret_cast<f32x2*>(vbuf + xi * PLANE) = v_comp(xi); };
-    f32x2 vv[16];   // main loop: the 16 components, computed in one go (see the slot comment there)
-    auto u_store = [&](int i, float* ubuf) { *reinterpret_cast<u32x4*>(ubuf + i * 2 * PLANE) = ul[i]; };
-
-    // wave w owns transform row i = w: components xi = 4w + j, j = 0..3, for the WHOLE 64 x 64 workgroup tile
-    // (2 x 2 MFMA tiles per component: an operand fragment is reused twice, 0.25 LDS reads per MFMA as in conv.hip)
-    f32x16 acc[4][2][2];  // [j][position half][channel half]
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][a][c][r] = 0.f;
-
-    // prologue: k tile 0 into buffer 0, loads of k tile 1 in flight
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v_load(i, 0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u_load(i, 0);
-#pragma unroll
-    for (int dx = 0; dx < 4; ++dx) column_pass(dx);
-#pragma unroll
-    for (int xi = 0; xi < 16; ++xi) v_store(xi, Vs + v_lds);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u_store(i, Us + u_lds);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v_load(i, 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u_load(i, 1);
-    __syncthreads();
-
-    // a component plane is [2 channel quads][64 rows][4 channels]: staging writes (a lane per row) and operand reads
-    // (a lane per row, lane half = quad) are both contiguous 16-byte runs across lanes — no LDS bank conflicts
-    const float* Aw = Vs + (wave * 4) * PLANE + lh * (WT * 4) + ln * 4;
-    const float* Bw = Us + (wave * 4) * PLANE + lh * (WN * 4) + ln * 4;
-    float4 fa[2][2], fb[2][2];  // [slot][half]
-    auto read_frags = [&](int slot, int buf, int j) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            fa[slot][h] = *reinterpret_cast<const float4*>(Aw + buf * 16 * PLANE + j * PLANE + h * 32 * 4);
-            fb[slot][h] = *reinterpret_cast<const float4*>(Bw + buf * 16 * PLANE + j * PLANE + h * 32 * 4);
-        }
-    };
-    read_frags(0, 0, 0);
-    // ---- main loop: 64 MFMAs per k tile and wave (4 components x 2 x 2 tiles x 4 k steps), order pinned. Staging of
-    // k tile kt+1 (its loads were issued during k tile kt-1) is spread over MFMA slots 8..39 of every wave; the barrier
-    // sits before the last component, whose operands are already in registers, so that the first operands of k tile
-    // kt+1 are fetched behind it, not after it.
-    //   slot 8-11 column passes | 12-27 reissue the patch loads for k tile kt+2 | 16-31 one V component out each
-    //   slot 32-39 one U slot to LDS + reissue its load
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        float* vnext = Vs + (buf ^ 1) * 16 * PLANE + v_lds;
-        float* unext = Us + (buf ^ 1) * 16 * PLANE + u_lds;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int cur = j & 1;
-            if (j + 1 < 4) {
-                read_frags(cur ^ 1, buf, j + 1);
-            } else {
-                __syncthreads();  // k tile kt+1 is complete in buf^1; everyone is done reading buf
-                read_frags(cur ^ 1, buf ^ 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const float4 fav = fa[cur][a], fbv = fb[cur][c];
-                        const float av = st == 0 ? fav.x : st == 1 ? fav.y : st == 2 ? fav.z : fav.w;
-                        const float bv = st == 0 ? fbv.x : st == 1 ? fbv.y : st == 2 ? fbv.z : fbv.w;
-                        acc[j][a][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[j][a][c], 0, 0, 0);
-                        const int m = j * 16 + st * 4 + a * 2 + c;  // MFMA slot 0..63
-                        if (m >= 8 && m < 12) column_pass(m - 8);
-                        if (m >= 12 && m < 28) v_load(m - 12, kt + 2);
-                        if (m >= 16 && m < 32) v_store(m - 16, vnext);
-                        if (m >= 32 && m < 40) {
-                            u_store(m - 32, unext);
-                            u_load(m - 32, kt + 2);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1] ---------------------------------------------------------
-    // The wave holds row i = wave of M (4 columns j): the column combination (M A) happens in registers, the row
-    // combination crosses waves through LDS: Z[i][c][position][channel], 4 x 2 x 64 x 64 floats = the 128 KB the
-    // operand buffers occupied. Then every wave finishes 16 positions: affine, ReLU, 256-byte channel runs.
-    __syncthreads();  // (the behind-the-barrier operand prefetch of a k tile that does not exist is still in flight)
-    // Z[i][c][position / 4][channel][position % 4]: an accumulator's registers r..r+3 are four consecutive positions
-    // of one channel, so writer and reader both move 16 bytes per lane, contiguous across lanes
-    float* Z = smem;
-    constexpr int ZP = (WT / 4) * WN * 4;  // floats per (i, c) plane
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const int pq = a * 8 + 2 * rq + lh, ch = c * 32 + ln;  // positions 4*pq .. 4*pq+3
-                float4 z0, z1;
-                float* z0p = &z0.x;
-                float* z1p = &z1.x;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = rq * 4 + e;
-                    const float m0v = acc[0][a][c][r], m1v = acc[1][a][c][r], m2v = acc[2][a][c][r], m3v = acc[3][a][c][r];
-                    z0p[e] = m0v + m1v + m2v;
-                    z1p[e] = m1v - m2v - m3v;
-                }
-                *reinterpret_cast<float4*>(Z + (wave * 2 + 0) * ZP + (pq * WN + ch) * 4) = z0;
-                *reinterpret_cast<float4*>(Z + (wave * 2 + 1) * ZP + (pq * WN + ch) * 4) = z1;
-            }
-    __syncthreads();
-    const int ch = lane, n = n0 + ch;
-    const bool n_ok = n < p.Cout;
-    const float sc = (n_ok && p.scale) ? p.scale[n] : 1.0f, sh = (n_ok && p.shift) ? p.shift[n] : 0.0f;
-    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const unsigned ncol = n_ok ? static_cast<unsigned>(n) * 4u : OOB;
-    const __amdgpu_buffer_rsrc_t yk_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.yk, 0, p.y_bytes, 0x00020000);
-    const unsigned kcol = static_cast<unsigned>(n >> 3) * p.yk_plane + static_cast<unsigned>(n & 7) * 4u;
-#pragma unroll 1
-    for (int g = 0; g < 4; ++g) {  // this wave finishes positions 16*wave + 4*g .. +3
-        const int pq = wave * 4 + g;
-        float4 z[4][2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) z[i][c] = *reinterpret_cast<const float4*>(Z + (i * 2 + c) * ZP + (pq * WN + ch) * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int P = __builtin_amdgcn_readfirstlane(m0 + pq * 4 + e);
-            const bool pv = P < p.T;
-            const int PP = pv ? P : 0;
-            const int b = PP / (p.TH * p.TW), rem = PP - b * p.TH * p.TW;
-            const int ty = rem / p.TW, tx = rem - ty * p.TW;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const float z0 = (&z[0][c].x)[e], z1 = (&z[1][c].x)[e], z2 = (&z[2][c].x)[e], z3 = (&z[3][c].x)[e];
-                const float yv[2] = {z0 + z1 + z2, z1 - z2 - z3};
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-                    float v = yv[a] * sc + sh;
-                    if (p.act) v = v > 0.f ? v : 0.f;
-                    const unsigned px = static_cast<unsigned>((b * p.H + 2 * ty + a) * p.W + 2 * tx + c);
-                    if (p.y) {
-                        const unsigned o = (pv && n_ok) ? px * (static_cast<unsigned>(p.Cout) * 4u) + ncol : OOB;
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), y_rsrc, static_cast<int>(o), 0, 0);
-                    }
-                    if (p.yk) {  // the layout the next Winograd conv reads: no transposition pass in between
-                        const unsigned o = (pv && n_ok) ? kcol + px * 32u : OOB;
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yk_rsrc, static_cast<int>(o), 0, 0);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-#endif  // MRCNN_ABLATIONS
-
-// Eight-wave variant: the same workgroup tile (64 positions x 64 channels, 128 KB of LDS) and k-blocked operands, but
-// 512 threads — wave w owns TWO components (2w, 2w+1) for the whole tile: 128 accumulator registers, so TWO waves per
+// Linear tiles: 64 consecutive tile positions x 64 channels, V and U staged in LDS (16 component planes each, double-buffered:
+// 128 KB). 512 threads — wave w owns TWO components (2w, 2w+1) for the whole tile: 128 accumulator registers, so TWO waves per
 // SIMD. With one wave per SIMD every LDS / VMEM / scalar instruction and every wait sits on the MFMA critical path
 // (there is nobody else to issue); with two, one wave's staging and stalls overlap the other's MFMAs (VALU still does
 // not: tools/mfma_valu_probe.hip). Waves 0-3 stage V (patch loads + input transform), waves 4-7 stage U; wave w and
 // w+4 share a SIMD, so each SIMD carries one of each. The output transform needs all 16 components of a position:
 // M.A is split into partial sums per wave (columns j = 0,1 or 2,3), exchanged through LDS in two rounds of 32
 // positions (8 waves x 2 partials x 32 x 64 floats = the 128 KB the operand buffers occupied).
-// HEADS = true (the RPN's conv_shared, model.py:605-607,624-641): the ReLU'd 64-channel output tile is not stored;
-// it is transposed through LDS and multiplied by the [32][Cout] weights of both 1x1 heads while on chip. A workgroup
-// then owns whole M tiles and walks their N tiles itself, adding each N tile's contribution to the M tile's
-// [256 pixels][32] head sums (a read-modify-write of 32 KB that stays in its XCD's L2; waves w and w + 4 split K and
-// keep separate sums). The 512-channel activation (1.43 GB written and read back per step) never reaches HBM.
-template <bool HEADS>
 __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Vs = smem;
@@ -356,28 +80,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) 
     // tiles at any time; this saves a workgroup launch (128 KB of LDS, eight waves) per tile.
     const int total_tiles = 8 * ((p.tiles_m + 7) / 8) * p.tiles_n;
     for (int it = 0;; ++it) {
-    int m0, n0, nt;
+    int m0, n0;
     {
-        // plain: virtual tile b, b + grid, ... in the XCD-aware (M tile, N tile) order. HEADS: M-tile units b, b + grid,
-        // ..., each walked over all its N tiles by this workgroup
-        const int tile = HEADS ? (blockIdx.x + (it / p.tiles_n) * gridDim.x) * p.tiles_n + it % p.tiles_n
-                               : blockIdx.x + it * gridDim.x;
+        // virtual tile b, b + grid, ... in the XCD-aware (M tile, N tile) order
+        const int tile = blockIdx.x + it * gridDim.x;
         if (tile >= total_tiles) break;
-        int xcd, seq;
-        if constexpr (HEADS) {
-            const int unit = tile / p.tiles_n;
-            xcd = unit & 7;
-            seq = (unit >> 3) * p.tiles_n + (tile - unit * p.tiles_n);
-        } else {
-            xcd = tile & 7;
-            seq = tile >> 3;
-        }
+        const int xcd = tile & 7, seq = tile >> 3;
         const int mt_lo = (xcd * p.tiles_m) >> 3, mt_hi = ((xcd + 1) * p.tiles_m) >> 3;
         const int mt = mt_lo + seq / p.tiles_n;
         if (mt >= mt_hi) continue;  // uniform
         m0 = mt * WT;
-        nt = seq % p.tiles_n;
-        n0 = nt * WN;
+        n0 = (seq % p.tiles_n) * WN;
     }
     const int ln = lane & 31, lh = lane >> 5;
     const bool v_role = wave < 4;
@@ -386,7 +99,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) 
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.u_bytes, 0x00020000);
 
-    // fixed per-thread byte offsets (see the four-wave kernel): V role 16 patch taps, U role 8 slots (in off[0..7])
+    // fixed per-thread byte offsets, out of range where a load must return zeros:
+    //   V role: thread = (position st >> 2, channel pair st & 3), sixteen 8-byte patch taps; a wave-level load covers 16
+    //           pixels x 32 contiguous bytes = 8 cache lines (a position per lane would touch 32)
+    //   U role: eight 16-byte slots of the 16 x 64 x 8 block (in off[0..7])
     unsigned off[16];
     if (v_role) {
         const int pos = st >> 2, pair = st & 3;
@@ -561,21 +277,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) 
     float* Z = smem;  // [wave][2 partials][8 position quads][64 channels][4 positions]
     constexpr int ZQ = 8 * WN * 4;  // floats per (wave, partial) plane
     const int jh = wave & 1;
-    // HEADS: the round's 128 pixels x 64 channels, transposed for the head MFMA; 16-byte chunks XOR-swizzled by the pixel
-    // (a 64-float pitch would put every row on the same banks), exactly the 32 KB above the operand buffers
-    float* Tt = smem + 2 * 2 * 16 * PLANE;
-    const int hrt = wave & 3, hkh = wave >> 2;  // head MFMA: pixel rows 32 hrt .. +31 of the round, channels 32 hkh .. +31
-    float4 wh[4];
-    // opaque copies of the lane coordinates: everything the heads epilogue derives from them (LDS and global offsets,
-    // the head-weight loads) stays behind the main loop — hoisted out of the tile loop those ~25 values spill inside it
-    int ln_e = ln, lh_e = lh, tid_e = tid;
-    if constexpr (HEADS) {
-        asm volatile("" : "+v"(ln_e), "+v"(lh_e), "+v"(tid_e));
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            wh[j] = *reinterpret_cast<const float4*>(p.w_head + static_cast<int64_t>(ln_e) * p.Cout + n0 + hkh * 32 + j * 8 + lh_e * 4);
-    }
-    const __amdgpu_buffer_rsrc_t hp_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.head_part, 0, HEADS ? p.head_bytes : 0u, 0x00020000);
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {  // position half
         __syncthreads();  // operand buffers (or the previous round's Z) are no longer read
@@ -627,11 +328,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) 
                 for (int a = 0; a < 2; ++a) {
                     float v = yv[a] * sc + sh;
                     if (p.act) v = v > 0.f ? v : 0.f;
-                    if constexpr (HEADS) {
-                        const int pxl = ((tid_e >> 6) * 4 + e) * 4 + a * 2 + c;  // position-major pixel of the round
-                        Tt[pxl * WN + ((tid_e & 63) ^ ((pxl & 15) << 2))] = v;
-                        continue;
-                    }
                     const unsigned px = static_cast<unsigned>((b * p.H + 2 * ty + a) * p.W + 2 * tx + c);
                     if (p.y) {
                         const unsigned o = (pv && n_ok) ? px * (static_cast<unsigned>(p.Cout) * 4u) + ncol : OOB;
@@ -643,37 +339,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8_f32(const WinoParams p) 
                     }
                 }
             }
-        }
-        if constexpr (HEADS) {
-            // [128 pixels x 32 channels of this wave] x [32 channels x 32 head outputs] on top of the M tile's running
-            // sums (N tile 0 starts them): 16 MFMAs per wave and round
-            __syncthreads();
-            const int row0 = (m0 * 4 + h * 128 + hrt * 32 + 4 * lh_e);  // + (r & 3) + 8 (r >> 2)
-            const unsigned hbase = (static_cast<unsigned>(hkh) * static_cast<unsigned>(p.tiles_m) * 256u + static_cast<unsigned>(row0)) * 128u +
-                                   static_cast<unsigned>(ln_e) * 4u;
-            f32x16 hacc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                hacc[r] = 0.f;
-                if (nt != 0)
-                    hacc[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                        hp_rsrc, static_cast<int>(hbase + static_cast<unsigned>((r & 3) + 8 * (r >> 2)) * 128u), 0, 0));
-            }
-            const int pxl = hrt * 32 + ln_e;
-            const float* trow = Tt + pxl * WN;
-            const int swz = (pxl & 15) << 2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 a4 = *reinterpret_cast<const float4*>(trow + ((hkh * 32 + j * 8 + lh_e * 4) ^ swz));
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, wh[j].x, hacc, 0, 0, 0);
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, wh[j].y, hacc, 0, 0, 0);
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, wh[j].z, hacc, 0, 0, 0);
-                hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, wh[j].w, hacc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hacc[r]), hp_rsrc,
-                                                      static_cast<int>(hbase + static_cast<unsigned>((r & 3) + 8 * (r >> 2)) * 128u), 0, 0);
         }
     }
     __syncthreads();  // Z is read out: the next tile may overwrite the operand buffers
@@ -704,8 +369,12 @@ struct WinoSParams : WinoParams {
     int tyb, txb;  // 8 x 8-position blocks per image along y / x
 };
 
-// HEADS as in conv3x3_wino8_f32<true>: the output tile feeds the 1x1 heads on chip; a workgroup owns whole M tiles (8 x 8
-// position blocks) and walks their N tiles; head sums in M-tile-major rows: row = mt * 256 + (py * 8 + px) * 4 + a * 2 + c.
+// HEADS = true (the RPN's conv_shared, model.py:605-607,624-641): the ReLU'd 64-channel output tile is not stored; it is
+// transposed through LDS and multiplied by the [32][Cout] weights of both 1x1 heads while on chip. A workgroup then owns whole
+// M tiles (8 x 8 position blocks) and walks their N tiles itself, adding each N tile's contribution to the M tile's
+// [256 pixels][32] head sums, row = mt * 256 + (py * 8 + px) * 4 + a * 2 + c (a read-modify-write of 32 KB that stays in its
+// XCD's L2; waves w and w + 4 split K and keep separate sums). The 512-channel activation (1.43 GB written and read back per
+// step) never reaches HBM.
 template <bool HEADS>
 __global__ __launch_bounds__(512, 1) void conv3x3_wino8s_f32(const WinoSParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -815,11 +484,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8s_f32(const WinoSParams p
         const f32x2 rs2 = {rs, rs};
         auto lo2 = [](const float4& v) { return f32x2{v.x, v.y}; };
         auto hi2 = [](const float4& v) { return f32x2{v.z, v.w}; };
-        auto pk_fma = [](f32x2 a, f32x2 b, f32x2 c) {
-            f32x2 r;
-            asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-            return r;
-        };
         auto join = [](f32x2 lo, f32x2 hi) { return make_float4(lo.x, lo.y, hi.x, hi.y); };
         auto row_pass = [&](int cc) {  // l[cc] = dA + rs * dB, in place of d[cc]
             d[cc] = join(pk_fma(lo2(d[3 + cc]), rs2, lo2(d[cc])), pk_fma(hi2(d[3 + cc]), rs2, hi2(d[cc])));
@@ -914,11 +578,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8s_f32(const WinoSParams p
         const unsigned kcol = static_cast<unsigned>(n >> 3) * p.yk_plane + static_cast<unsigned>(n & 7) * 4u;
         float* Z = smem;  // [wave][2 partials][8 position quads][64 channels][4 positions]
         constexpr int ZQ = 8 * WN * 4;
-        // HEADS (see conv3x3_wino8_f32<true>): the round's 128 pixels x 64 channels transposed above the Z exchange
+        // HEADS: the round's 128 pixels x 64 channels, transposed for the head MFMA; 16-byte chunks XOR-swizzled by the pixel
+        // (a 64-float pitch would put every row on the same banks), exactly the 32 KB above the Z exchange
         float* Tt = smem + 2 * 2 * 16 * PLANE;
-        const int hrt = wave & 3, hkh = wave >> 2;
+        const int hrt = wave & 3, hkh = wave >> 2;  // head MFMA: pixel rows 32 hrt .. +31 of the round, channels 32 hkh .. +31
         float4 wh[4];
-        int ln_e = ln, lh_e = lh, tid_e = tid;  // opaque copies: keep the heads epilogue's address arithmetic behind the loop
+        // opaque copies of the lane coordinates: everything the heads epilogue derives from them (LDS and global offsets,
+        // the head-weight loads) stays behind the main loop — hoisted out of the tile loop those ~25 values spill inside it
+        int ln_e = ln, lh_e = lh, tid_e = tid;
         if constexpr (HEADS) {
             asm volatile("" : "+v"(ln_e), "+v"(lh_e), "+v"(tid_e));
 #pragma unroll
@@ -992,6 +659,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino8s_f32(const WinoSParams p
                 }
             }
             if constexpr (HEADS) {
+                // [128 pixels x 32 channels of this wave] x [32 channels x 32 head outputs] on top of the M tile's running
+                // sums (N tile 0 starts them): 16 MFMAs per wave and round
                 __syncthreads();
                 const int row0 = mt * 256 + h * 128 + hrt * 32 + 4 * lh_e;  // + (r & 3) + 8 (r >> 2)
                 const unsigned hbase = (static_cast<unsigned>(hkh) * static_cast<unsigned>(p.tiles_m) * 256u + static_cast<unsigned>(row0)) * 128u +
@@ -1176,15 +845,10 @@ extern "C" int mrcnn_conv3x3_winograd_f32(const float* x, int32_t x_layout, int3
         p.x = t;
     }
     if (!spatial) {
-#ifdef MRCNN_ABLATIONS
-        static const bool four_waves = mrcnn::tuning_env("MRCNN_WINO_WAVES") && atoi(mrcnn::tuning_env("MRCNN_WINO_WAVES")) == 4;
-        if (four_waves)
-            return mrcnn::launch_kernel(conv3x3_wino_f32, grid, 256, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
-#endif
         static const bool persistent = !(mrcnn::tuning_env("MRCNN_WINO_PERSISTENT") && atoi(mrcnn::tuning_env("MRCNN_WINO_PERSISTENT")) == 0);
         if (!persistent)
-            return mrcnn::launch_kernel(conv3x3_wino8_f32<false>, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
-        return mrcnn::launch_one_per_cu(conv3x3_wino8_f32<false>, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
+            return mrcnn::launch_kernel(conv3x3_wino8_f32, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
+        return mrcnn::launch_one_per_cu(conv3x3_wino8_f32, grid, 512, WINO_LDS, st, "conv3x3_winograd", "conv3x3_wino_f32", p);
     }
     return mrcnn::launch_one_per_cu(conv3x3_wino8s_f32<false>, grid, 512, WINOS_LDS, st, "conv3x3_winograd", "conv3x3_wino8s_f32", p);
 }
@@ -1211,28 +875,18 @@ extern "C" int mrcnn_conv3x3_winograd_heads_f32(const float* x_kblocked, int32_t
     if (int rc = fill_wino(p, "conv3x3_winograd_heads", true, false, x_kblocked, batch, height, width, cin, u, cout, scale, shift,
                            activation))
         return rc;
-#ifdef MRCNN_ABLATIONS
-    MRCNN_REQUIRE(tile_mode == 1 || (tile_mode == 2 && height / 2 >= 8 && width / 2 >= 8),
-                  "conv3x3_winograd_heads: tile_mode must be 1, or 2 on maps of at least 8 x 8 tile positions");
-#else   // the linear-tile heads variant (tile_mode 1) exists in MRCNN_ABLATIONS builds only: same numbers, slower
     MRCNN_REQUIRE(tile_mode == 2 && height / 2 >= 8 && width / 2 >= 8,
                   "conv3x3_winograd_heads: tile_mode must be 2 (8 x 8 position blocks), on maps of at least 8 x 8 tile positions");
-#endif
     const long long px = 1LL * batch * height * width;
     const long long rows = mrcnn_conv3x3_winograd_heads_rows(batch, height, width, tile_mode);
     MRCNN_REQUIRE(4 * px * cin <= MAX_BUFFER_BYTES && 64LL * cin * cout <= MAX_BUFFER_BYTES &&
                       8 * rows * 32 <= MAX_BUFFER_BYTES,
                   "conv3x3_winograd_heads: tensor too large (32-bit buffer byte offsets)");
-    if (tile_mode == 2) p.tiles_m = batch * p.tyb * p.txb;
+    p.tiles_m = batch * p.tyb * p.txb;
     p.w_head = w_head32; p.head_part = head_part;
     p.head_bytes = static_cast<unsigned>(4LL * 2 * rows * 32);
     const long long units = 8LL * ((p.tiles_m + 7) / 8);  // M-tile units; a workgroup walks the N tiles of its units
     hipStream_t st = mrcnn::as_stream(stream);
-#ifdef MRCNN_ABLATIONS
-    if (tile_mode != 2)
-        return mrcnn::launch_one_per_cu(conv3x3_wino8_f32<true>, units, 512, WINO_HEADS_LDS, st, "conv3x3_winograd_heads",
-                                        "conv3x3_wino8_f32<heads>", p);
-#endif
     return mrcnn::launch_one_per_cu(conv3x3_wino8s_f32<true>, units, 512, WINO_HEADS_LDS, st, "conv3x3_winograd_heads",
                                     "conv3x3_wino8s_f32<heads>", p);
 }

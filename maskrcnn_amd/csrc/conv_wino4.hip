@@ -39,8 +39,6 @@ namespace {
 
 using namespace mrcnn_conv;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // LDS pointers stay in their address space: arithmetic on generic pointers costs a null check per conversion (and the
 // LDS-DMA destination / asm read addresses are 32-bit LDS offsets anyway)
 typedef __attribute__((address_space(3))) float lds_f32;
@@ -118,21 +116,7 @@ constexpr size_t WINO4_CONV3_LDS = sizeof(float) * (W4_W3_OFF + W4_W3_FLOATS + W
 static_assert(WINO4_CONV3_LDS <= 160 * 1024 && W4_Z_FLOATS <= W4_W3_OFF, "CONV3 LDS map");
 static_assert(W4_Z_FLOATS <= W4_RS_FLOATS + 2 * W4_UBUF, "the exchange buffer aliases the staging buffers");
 
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-    f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {  // a * b + c
-    f32x2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
+// pk_add / pk_sub / pk_fma: conv_common.hpp
 __device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
     f32x2 r;
     asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));

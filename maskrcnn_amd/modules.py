@@ -579,34 +579,21 @@ class FusedRPN:
         w = torch.cat([sd[prefix + "conv_class.weight"], sd[prefix + "conv_bbox.weight"]], 0)
         self.b_head = torch.cat([sd[prefix + "conv_class.bias"], sd[prefix + "conv_bbox.bias"]]).float() \
             .contiguous().to(device)
-        # MRCNN_WINOGRAD=0 in an MRCNN_ABLATIONS build: the direct-kernel fused level; otherwise separate launches
-        self.fused_level = precision == "f32" and not WINOGRAD and ops.HAVE_ABLATIONS
-        if self.fused_level:
-            # fused level kernel: the 512-channel shared activation never leaves the chip (ops.rpn_level_fused)
-            self.w_shared = pack_weight(sd[prefix + "conv_shared.weight"], device)
-            self.b_shared = sd[prefix + "conv_shared.bias"].float().contiguous().to(device)
+        self.shared = FusedConv(sd, prefix + "conv_shared", None, device, relu=True, same_pad_kernel=3,
+                                precision=precision, winograd4=True)
+        self.w_head = ConvWeight(pack_weight(w, device), precision)
+        if precision == "f32" and self.shared.w.u is not None:   # heads inside the Winograd kernel (large levels)
             w32 = torch.zeros(32, w.size(1), dtype=torch.float32)
             w32[:w.size(0)] = w.float().view(w.size(0), -1)
             self.w_head32 = w32.contiguous().to(device)
-            self.head_n = w.size(0)
-        else:
-            self.shared = FusedConv(sd, prefix + "conv_shared", None, device, relu=True, same_pad_kernel=3,
-                                    precision=precision, winograd4=True)
-            self.w_head = ConvWeight(pack_weight(w, device), precision)
-            if precision == "f32" and self.shared.w.u is not None:   # heads inside the Winograd kernel (large levels)
-                w32 = torch.zeros(32, w.size(1), dtype=torch.float32)
-                w32[:w.size(0)] = w.float().view(w.size(0), -1)
-                self.w_head32 = w32.contiguous().to(device)
-            if precision == "f16" and F16_PIPELINED and RPN_FUSED_HEADS and w.size(1) == 512:
-                # "f16" mode: heads inside the pipelined fp16 kernel's epilogue (levels whose map arrives as fp16)
-                w16 = torch.zeros(32, w.size(1), dtype=torch.float16)
-                w16[:w.size(0)] = w.float().view(w.size(0), -1).to(torch.float16)
-                self.w_head16 = w16.contiguous().to(device)
+        if precision == "f16" and F16_PIPELINED and RPN_FUSED_HEADS and w.size(1) == 512:
+            # "f16" mode: heads inside the pipelined fp16 kernel's epilogue (levels whose map arrives as fp16)
+            w16 = torch.zeros(32, w.size(1), dtype=torch.float16)
+            w16[:w.size(0)] = w.float().view(w.size(0), -1).to(torch.float16)
+            self.w_head16 = w16.contiguous().to(device)
 
     def __call__(self, p, p_kblocked=None):
         """p: a pyramid level NHWC; p_kblocked: the same map k-blocked, when the producer wrote it (f32 Winograd mode)."""
-        if self.fused_level:
-            return ops.rpn_level_fused(p, self.w_shared, self.b_shared, self.w_head32, self.b_head, self.head_n)
         if p_kblocked is not None and self.shared.takes_winograd(p.size(1), p.size(2)):
             b, h, w = p.size(0), p.size(1), p.size(2)
             sw = self.shared.w
@@ -618,7 +605,7 @@ class FusedRPN:
             if (RPN_FUSED_HEADS and getattr(self, "w_head32", None) is not None
                     and not sw.takes_winograd4(h, w, 1, (1, 1, 1, 1), None, True, b)
                     and -(-((h // 2) * (w // 2)) // 64) >= RPN_HEADS_MIN_TILES and self.shared.w.shape[0] % 64 == 0
-                    and (min(h, w) >= 16 or ops.HAVE_ABLATIONS)):
+                    and min(h, w) >= 16):
                 return ops.conv3x3_winograd_heads(p_kblocked, self.shared.w.u, self.shared.scale, self.shared.shift,
                                                   self.w_head32, True, self.shared.algo_cin)
             p = p_kblocked

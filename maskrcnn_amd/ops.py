@@ -35,7 +35,7 @@ __all__ = ["nms_batched", "nms_general", "crop", "roi_align_pyramid", "MaskrcnnH
            "conv_bn_act", "conv_bn_act_f16mfma", "split_f16", "same_pad", "maxpool", "nchw_to_nhwc", "nhwc_to_nchw",
            "bottleneck_forward", "bottleneck_fused", "bottleneck_fused_supported", "bottleneck_native", "bottleneck_plan",
            "rpn_scores_deltas", "proposal_decode", "conv3x3_winograd_heads", "HeadSums",
-           "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2", "rpn_level_fused",
+           "detection_decode", "topk_desc", "proposal_select", "detection_select", "deconv2x2",
            "rle_encode", "rle_iou", "bbox_iou", "coco_match", "rle_from_poly", "rle_merge",
            "rle_from_string", "rle_area_bbox", "rle_to_string", "rle_decode", "blend_instances",
            "anchor_match", "sample_by_key", "rpn_deltas", "detection_targets", "mask_targets",
@@ -897,9 +897,9 @@ def conv3x3_winograd_heads(x_kblocked: torch.Tensor, u: torch.Tensor, scale, shi
     if not (w_head32.is_contiguous() and tuple(w_head32.shape) == (32, cout)):
         refuse(op, "w_head32", f"contiguous [32,{cout}]", w_head32)
     mode = int(lib.mrcnn_conv3x3_winograd_heads_tile_mode(h, w)) if tile_mode is None else int(tile_mode)
-    if mode != 2 and not HAVE_ABLATIONS:
+    if mode != 2:
         raise RuntimeError("conv3x3_winograd_heads: maps of at least 16 x 16 pixels (8 x 8 tile positions) and the spatial-tile "
-                           "kernel are required; the linear-tile heads variant is an MRCNN_ABLATIONS build")
+                           "kernel (tile_mode 2) are required")
     rows = int(lib.mrcnn_conv3x3_winograd_heads_rows(b, h, w, mode))
     part = torch.empty(2, rows, 32, dtype=torch.float32, device=x_kblocked.device)
 
@@ -1088,38 +1088,6 @@ def deconv2x2(x: torch.Tensor, w, bias4: torch.Tensor, activation: int = 0, prod
         _launch(lib.mrcnn_deconv2x2_bias_act_nhwc_f16mfma,
                 (x.data_ptr(), b, h, wd, cin, w_hi.data_ptr(), _ptr(w_lo), cout, bias4.data_ptr(), int(activation), int(products),
                  y.data_ptr(), _stream()), book)
-    return y
-
-
-HAVE_ABLATIONS = hasattr(lib, "mrcnn_rpn_level_fused_f32")   # an MRCNN_ABLATIONS build of the library is loaded
-
-
-@_on_device
-def rpn_level_fused(x, w_shared, b_shared, w_head32, b_head, head_n: int = 18) -> torch.Tensor:
-    """RPN.forward on one level (model.py:609-649) with the shared 512-channel activation kept on chip:
-    x [B,H,W,Cin] NHWC → [B,H,W,head_n] (class logits then box deltas). fp32 MFMA path, direct kernel. MRCNN_ABLATIONS
-    builds only (the default library fuses the heads into the Winograd kernels instead)."""
-    if not HAVE_ABLATIONS:
-        raise RuntimeError("rpn_level_fused: built only with MRCNN_ABLATIONS=1 python maskrcnn_amd/build.py")
-    _need_gpu(x, w_shared, b_shared, w_head32, b_head)
-    _contiguous("rpn_level_fused", x=(x, None), w_shared=(w_shared, None), w_head32=(w_head32, None))
-    b, h, wd, cin = x.shape
-    cout = w_shared.size(0)
-    if tuple(w_shared.shape[1:]) != (3, 3, cin):
-        refuse("rpn_level_fused", "w_shared", f"[Cout,3,3,{cin}]", w_shared)
-    if tuple(w_head32.shape) != (32, cout):
-        refuse("rpn_level_fused", "w_head32", f"[32,{cout}]", w_head32)
-    ws_bytes = int(lib.mrcnn_rpn_level_workspace_bytes(b, h, wd, cout, head_n))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    y = torch.empty(b, h, wd, head_n, dtype=torch.float32, device=x.device)
-
-    def book():
-        m = b * h * wd
-        flops = 2.0 * m * (9 * cin * cout + cout * head_n)  # shared 3x3 conv + both 1x1 heads
-        return flops, (m, cout, 9 * cin), 4 * (x.numel() + w_shared.numel() + cout * head_n + y.numel()), "rpn_fused"
-    _launch(lib.mrcnn_rpn_level_fused_f32,
-            (x.data_ptr(), b, h, wd, cin, w_shared.data_ptr(), cout, _ptr(b_shared), w_head32.data_ptr(), _ptr(b_head),
-             int(head_n), ws.data_ptr(), ws_bytes, y.data_ptr(), _stream()), book)
     return y
 
 

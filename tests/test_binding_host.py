@@ -162,7 +162,7 @@ PUBLIC = ['HeadSums', 'MaskrcnnHipError', 'anchor_match', 'bbox_iou', 'blend_ins
           'conv_bn_act_f16mfma', 'crop', 'deconv2x2', 'detection_decode', 'detection_select', 'detection_targets', 'head_loss',
           'head_loss_backward', 'mask_targets', 'maxpool', 'nchw_to_nhwc', 'nhwc_to_nchw', 'nms_batched', 'nms_general', 'proposal_decode',
           'proposal_select', 'rle_area_bbox', 'rle_decode', 'rle_encode', 'rle_from_poly', 'rle_from_string', 'rle_iou', 'rle_merge',
-          'rle_to_string', 'roi_align_pyramid', 'rpn_deltas', 'rpn_level_fused', 'rpn_loss', 'rpn_loss_backward', 'rpn_scores_deltas',
+          'rle_to_string', 'roi_align_pyramid', 'rpn_deltas', 'rpn_loss', 'rpn_loss_backward', 'rpn_scores_deltas',
           'same_pad', 'sample_by_key', 'split_f16', 'topk_desc']
 
 
@@ -175,7 +175,7 @@ def test_registered_schemas_and_public_names_are_the_parents():
     assert set(ops.__all__) == set(PUBLIC) and len(ops.__all__) == len(PUBLIC)
     for name in PUBLIC + ["RLE_BAD_BYTE", "RLE_LONG_TOKEN", "RLE_OPEN_TOKEN", "RLE_BAD_SIZE", "RLE_BAD_OFFSETS", "RLE_EMPTY_RUN",
                           "RLE_PIXEL_SUM", "POLY_MAX_DIM", "POLY_MAX_PART_POINTS", "poly_host_bounds", "rle_string_tokens", "rle_table",
-                          "CONV_PROFILE", "BOTTLENECK_OP_FUSED", "HAVE_ABLATIONS", "NMS_MAX_BOXES"]:
+                          "CONV_PROFILE", "BOTTLENECK_OP_FUSED", "NMS_MAX_BOXES"]:
         assert hasattr(ops, name), name
 
 

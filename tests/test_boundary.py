@@ -61,9 +61,6 @@ def test_header_parser_yields_the_hand_written_signatures():
         assert len(args) == len(hargs), f"{name}: {len(args)} arguments vs {len(hargs)} in the header"
         for i, (a, h) in enumerate(zip(args, hargs)):
             assert a == h, f"{name}: argument {i} is {a} by hand, {h} from the header"
-    ablations = _lib.header_prototypes(_lib.ABLATIONS_HEADER)
-    assert sorted(ablations) == ["mrcnn_rpn_level_fused_f32", "mrcnn_rpn_level_workspace_bytes"]
-    assert ablations["mrcnn_rpn_level_workspace_bytes"] == (c_size, [c_i32] * 5)
 
 
 def test_unknown_type_in_the_header_is_an_import_error(tmp_path, monkeypatch):
@@ -317,10 +314,6 @@ def test_entry_points_refuse_the_first_shape_past_their_limit():
     # F(2x2) heads (the RPN's shared conv + heads): 4 B H W Cin <= OOB; B16 x 512 x 510 x 256 accepted
     assert 4 * 16 * 512 * 510 * 256 <= OOB < 4 * 16 * 512 * 512 * 256
     refused(lib.mrcnn_conv3x3_winograd_heads_f32(dp, 16, 512, 512, 256, dp, 512, None, None, 1, dp, 2, dq, None), "wino heads")
-    # the direct-kernel RPN level (exported by MRCNN_ABLATIONS builds only): 4 M Cin <= OOB; 2048 x 2040 x 256 accepted
-    if hasattr(lib, "mrcnn_rpn_level_fused_f32"):
-        assert 4 * 2048 * 2040 * 256 <= OOB < 4 * 2048 * 2048 * 256
-        refused(lib.mrcnn_rpn_level_fused_f32(dp, 1, 2048, 2048, 256, dp, 512, dp, dp, dp, 18, dq, big, dp, None), "rpn level")
     # the fused fp32 bottleneck: 4 px 256 <= OOB; B4 x 1024 x 1008 accepted
     assert 4 * 4 * 1024 * 1008 * 256 <= OOB < 4 * 4 * 1024 * 1024 * 256
     refused(lib.mrcnn_bottleneck_fused_f32(dp, 4, 1024, 1024, 256, dp, None, None, dp, None, None, dp, None, None, 64, dq, None),
@@ -458,9 +451,7 @@ def test_conv_entry_points_with_a_shared_fill_keep_every_refusal():
     # ---- F(2x2) heads: (x, B, H, W, Cin, u, Cout, scale, shift, act, w_head, tile_mode, head_part, stream)
     w2h = lib.mrcnn_conv3x3_winograd_heads_f32
     who = "conv3x3_winograd_heads"
-    # (a library built with MRCNN_ABLATIONS — it exports the direct-kernel RPN level — also takes tile_mode 1)
-    bad_mode = who + (": tile_mode must be 1, or 2 on maps of at least 8 x 8 tile positions" if hasattr(lib, "mrcnn_rpn_level_fused_f32")
-                      else ": tile_mode must be 2 (8 x 8 position blocks), on maps of at least 8 x 8 tile positions")
+    bad_mode = who + ": tile_mode must be 2 (8 x 8 position blocks), on maps of at least 8 x 8 tile positions"
     row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 1, N, 2, dq, N), INVALID, who + ": null pointer")
     row(w2h(dp, 1, 16, 16, 8, dp, 64, N, N, 1, dp, 2, N, N), INVALID, who + ": null pointer")
     row(w2h(dp, 1, 15, 16, 8, dp, 64, N, N, 1, dp, 2, dq, N), INVALID, who + ": B=1 H=15 W=16 (even sizes required)")

@@ -229,32 +229,6 @@ def test_bottleneck_module_dropin(dev):
         blk(x)
 
 
-def test_rpn_level_fused_vs_torch_cpu(dev):
-    """3x3 shared conv + ReLU + both 1x1 heads in one pass (shared activation kept on chip) vs torch CPU. The direct-kernel
-    form of it is an MRCNN_ABLATIONS build (include/maskrcnn_hip_ablations.h); the default library refuses loudly."""
-    from maskrcnn_amd import ops
-    if not ops.HAVE_ABLATIONS:
-        with pytest.raises(RuntimeError, match="MRCNN_ABLATIONS"):
-            ops.rpn_level_fused(torch.zeros(1, 4, 4, 256, device=dev), torch.zeros(512, 3, 3, 256, device=dev),
-                                torch.zeros(512, device=dev), torch.zeros(32, 512, device=dev), torch.zeros(18, device=dev))
-        return
-    g = torch.Generator().manual_seed(12)
-    for (b, h, w) in [(2, 16, 12), (1, 5, 7), (1, 32, 32)]:
-        x = torch.randn(b, 256, h, w, generator=g)
-        ws = (torch.rand(512, 256, 3, 3, generator=g) * 2 - 1) * math.sqrt(6.0 / (256 * 9 + 512 * 9))
-        bs = torch.randn(512, generator=g) * 0.1
-        wh = torch.randn(18, 512, generator=g) * 0.05
-        bh = torch.randn(18, generator=g) * 0.1
-        t = F.relu(F.conv2d(F.pad(x, (1, 1, 1, 1)), ws, bs))
-        want = F.conv2d(t, wh.view(18, 512, 1, 1), bh).permute(0, 2, 3, 1)
-        w32 = torch.zeros(32, 512)
-        w32[:18] = wh
-        got = ops.rpn_level_fused(x.permute(0, 2, 3, 1).contiguous().to(dev),
-                                  ws.permute(0, 2, 3, 1).contiguous().to(dev), bs.to(dev), w32.to(dev), bh.to(dev))
-        err = (got.cpu() - want).abs().max().item()
-        assert err <= TOL, (b, h, w, err)
-
-
 # --------------------------------------------------------------------------------------------------
 # Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip): same 1e-4 bar against torch CPU, x ~ N(0,1), Xavier weights
 # --------------------------------------------------------------------------------------------------
@@ -760,7 +734,7 @@ def test_bottleneck_fused_rejects_other_shapes(dev):
 
 
 # --------------------------------------------------------------------------------------------------
-# RPN heads inside the Winograd kernel (conv3x3_wino8_f32<heads>)
+# RPN heads inside the Winograd kernel (conv3x3_wino8s_f32<heads>)
 # --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(1, 16, 16, 64, 128), (2, 32, 48, 256, 512), (3, 14, 18, 32, 64), (1, 128, 128, 256, 512),
                                    (1, 16, 0, 8, 64)], ids=lambda s: "x".join(str(v) for v in s))
@@ -768,11 +742,11 @@ def test_winograd_fused_rpn_heads(dev, shape):
     from maskrcnn_amd import ops as _ops
     if shape[2] == 0:   # one row of 8 x 8-position blocks, over the clamp
         shape = (shape[0], shape[1], 16 * _over_the_clamp()) + shape[3:]
-    if min(shape[1], shape[2]) < 16 and not _ops.HAVE_ABLATIONS:
-        # maps under 8 x 8 tile positions would need the linear-tile heads variant: an MRCNN_ABLATIONS build
+    if min(shape[1], shape[2]) < 16:
+        # maps under 8 x 8 tile positions have no spatial tiles, and the heads exist in the spatial-tile kernel only
         xk = torch.zeros(shape[3] // 8, shape[0], shape[1], shape[2], 8, device=dev)
         u = _ops.winograd_weights(torch.zeros(shape[4], 3, 3, shape[3], device=dev))
-        with pytest.raises(RuntimeError, match="MRCNN_ABLATIONS"):
+        with pytest.raises(RuntimeError, match=r"at least 16 x 16 pixels .* \(tile_mode 2\) are required"):
             _ops.conv3x3_winograd_heads(xk, u, None, None, torch.zeros(32, shape[4], device=dev), True)
         return
     _winograd_fused_rpn_heads(dev, shape)
@@ -797,7 +771,7 @@ def _winograd_fused_rpn_heads(dev, shape):
     w32 = torch.zeros(32, cout)
     w32[:18] = wh.view(18, cout)
     sums = ops.conv3x3_winograd_heads(xk, u, None, bs.to(dev), w32.to(dev), True)
-    assert sums.tile_mode == (2 if min(h, w) >= 16 else 1)
+    assert sums.tile_mode == 2
     got = sums.to_nhwc(bh.to(dev)).cpu()
     err = (got - want).abs().max().item()
     assert err <= TOL, f"max abs err {err:.3e} (|ref|max {want.abs().max().item():.2f})"
@@ -807,10 +781,6 @@ def _winograd_fused_rpn_heads(dev, shape):
     assert (got - un).abs().max().item() <= 2e-5
     again = ops.conv3x3_winograd_heads(xk, u, None, bs.to(dev), w32.to(dev), True)
     assert torch.equal(again.to_nhwc(bh.to(dev)).cpu(), got)                          # deterministic
-    # both tile shapes give the same sums bit for bit (same transforms, MFMA order and head accumulation order)
-    if ops.HAVE_ABLATIONS:
-        lin = ops.conv3x3_winograd_heads(xk, u, None, bs.to(dev), w32.to(dev), True, tile_mode=1)
-        assert torch.equal(lin.to_nhwc(bh.to(dev)).cpu(), got)
     # the consumer: scores / deltas from head sums == from NHWC heads of the same values
     lv = [got.to(dev)] + [torch.randn(b, max(h >> i, 1), max(w >> i, 1), 18, generator=g).to(dev) for i in (1, 2, 3, 4)]
     s0, d0 = ops.rpn_scores_deltas(lv)
