@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 30
+#define MRCNN_ABI_VERSION 31
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -1126,6 +1126,53 @@ int mrcnn_head_loss_backward(const int32_t* target_class_ids, const int32_t* num
                              const int32_t* counts, const float* grad_out, int32_t per_image, int32_t batch, int32_t count,
                              int32_t num_classes, int32_t mask_height, int32_t mask_width, float* grad_logits, float* grad_bbox,
                              float* grad_masks, mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Clipped SGD (csrc/optim.hip): what the reference does after every loss.backward() (model.py:1542-1557, 1632-1637) —
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm), then on every BATCH_SIZE-th iteration optim.SGD(momentum, weight decay on
+ * the non-BN group only).step() and zero_grad() — on a table of T tensors in three launches, whatever T is.
+ *
+ * The rule. Tensor t has an fp32 parameter p, an fp32 gradient g, an fp32 momentum buffer b, all of numel_t elements, and an fp64
+ * weight decay wd_t; lr, momentum and max_norm are fp64 and shared.
+ *   1. S = the sum over every element of every tensor that has a gradient of double(g) * double(g). A product is exact in fp64. S
+ *      is summed in fp64 in a FIXED order, a function of the sizes and their order in the table alone (neither of the grid nor of
+ *      timing), by store-and-sum as the losses above: tensor t is cut into tiles of TILE = mrcnn_optim_tile() consecutive elements,
+ *      the last one short; a tile's 256 threads each add their elements — thread k owns elements (256 i + k) 4 + j of the tile,
+ *      i = 0 .. TILE / 1024 - 1 outer, j = 0 .. 3 inner, in that order from +0 —, the thread sums are added per wave by the shuffle
+ *      scan of csrc/workgroup.hpp (lane 63's value: the balanced tree over the 64 lanes) and the wave sums in wave order; the tile
+ *      sum is stored. A finishing launch of one workgroup of 256 threads adds the tile sums in index order: thread k the run
+ *      [k chunk, (k + 1) chunk), chunk = ceil(tiles / 256), then the runs by the same scan. No floating-point atomic, no ticket.
+ *   2. norm = sqrt(S), c = min(1, max_norm / (norm + 1e-6)), both in fp64: clip_grad_norm_'s formula.
+ *   3. DEVIATION: if S is not finite (NaN or +Inf), bit 0 of status is set and the apply launch leaves parameters, momentum buffers
+ *      and (modes clip and step) gradients untouched; a requested zeroing of the gradients still happens. In the reference the NaN
+ *      flows into every weight.
+ *   4. Otherwise, per element in fp64 from the fp32 inputs, each operation rounded on its own, narrowed last:
+ *        d = c g + wd_t p,  B = momentum b + d,  b' = fp32(B),  p' = fp32(p - lr B) (from the unrounded B),  g' = fp32(c g).
+ *      torch's SGD with dampening 0 and nesterov False; a zero buffer gives B = d, torch's clone on the first step.
+ * mode 0 (clip) writes g' only; 1 (step) writes p', b' and g'; 2 (step_zero) writes p', b' and +0 into g. A store of g' that would
+ * not change a bit (c == 1) is left out. A tensor whose gradient address is 0 is skipped entirely — no decay, no momentum update, no
+ * term in S —, as torch skips grad is None. A tensor of 0 elements is legal.
+ *
+ * The tensor table lives in device memory: table int64 [T][4] = (address of p, address of g or 0, address of b, numel), wd fp64
+ * [T], tile_off int64 [T + 1] = the exclusive prefix sum of ceil(numel_t / TILE) (a skipped tensor keeps its tiles: tile_off
+ * depends on the sizes only), tiles = tile_off[T]. A workgroup finds its tile's tensor by a uniform binary search in tile_off.
+ * Tensors whose three addresses are 16-byte aligned are read and written with 16-byte accesses, the others element by element;
+ * both forms give the same bits. Element offsets are 64-bit.
+ *
+ * mrcnn_optim_clip_coef: steps 1-3 in two launches → info fp64 [3] = (S, norm, c), status int32 [1]. workspace: tiles doubles of
+ *   device memory, 8-byte aligned.
+ * mrcnn_optim_sgd_apply: step 4 in one launch; c and status are read from device memory (info, status: as clip_coef wrote them,
+ *   on the same stream; null: c = 1 and no non-finite check — max_norm None).
+ * Limits, checked before any launch: T in [1, 65535], tiles in [0, 2^24], max_norm > 0, lr finite, momentum in [0, 1), mode in
+ * 0 .. 2. What only the table's builder can see — numel_t < 2^31, wd_t finite, tile_off as defined — is the builder's to check.
+ * No call synchronises with the host or allocates.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t mrcnn_optim_tile(void);
+int mrcnn_optim_clip_coef(const int64_t* table, const int64_t* tile_off, int32_t num_tensors, int64_t tiles, double max_norm,
+                          double* workspace, double* info, int32_t* status, mrcnn_stream_t stream);
+int mrcnn_optim_sgd_apply(const int64_t* table, const double* wd, const int64_t* tile_off, int32_t num_tensors, int64_t tiles,
+                          const double* info, const int32_t* status, double lr, double momentum, int32_t mode,
+                          mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

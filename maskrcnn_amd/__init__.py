@@ -9,6 +9,7 @@ from . import _lib  # noqa: F401  (fails loudly if the HIP library is missing)
 from . import ops  # noqa: F401  (registers torch.ops.maskrcnn.*)
 from . import losses  # noqa: F401  (the training losses on the targets' padded outputs)
 from . import layers  # noqa: F401  (the head layers' conv / transposed conv with a grad_fn)
+from . import optim  # noqa: F401  (ClippedSGD: gradient norm, clip and momentum step in three launches)
 
 
 class _RoiAlignNCHW(_torch.autograd.Function):
@@ -60,4 +61,4 @@ def roi_align(inputs, pool_size, image_shape):
     return ops.nhwc_to_nchw(pooled)
 
 
-__all__ = ["ops", "roi_align", "losses", "layers"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)
+__all__ = ["ops", "roi_align", "losses", "layers", "optim"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)

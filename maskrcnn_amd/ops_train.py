@@ -494,3 +494,90 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
 
 # conv_bn_act_backward has no torch.ops.maskrcnn schema and is not in ops.__all__ either, for the same reason. The differentiable
 # front end is maskrcnn_amd.layers.
+
+
+# --------------------------------------------------------------------------------------------------
+# Clipped SGD on a table of tensors (csrc/optim.hip)
+# --------------------------------------------------------------------------------------------------
+SGD_MODES = ("clip", "step", "step_zero")
+_MAX_TENSORS, _MAX_TILES = 65535, 1 << 24
+
+
+def _optim_table(who, table, tile_off, tiles):
+    """table int64 [T,4] and tile_off int64 [T+1] of one call, T and the tile count. tiles=None reads tile_off[T] back from the
+    device (a host synchronisation: the front end passes the number it built the table with)."""
+    table = checked(who, "table", table, torch.int64, (("T", 1), 4), strides="refuse")
+    t = table.size(0)
+    if t > _MAX_TENSORS:
+        refuse(who, "table", f"int64 [T,4] with T in 1 .. {_MAX_TENSORS}", table)
+    tile_off = checked(who, "tile_off", tile_off, torch.int64, (t + 1,), strides="refuse", hint=f" for the {t} tensors of table")
+    tiles = int(tile_off[-1]) if tiles is None else int(tiles)
+    if not 0 <= tiles <= _MAX_TILES:
+        refuse(who, "tiles", f"in 0 .. 2^24 (tile_off[T], {int(lib.mrcnn_optim_tile())} elements a tile)", tiles)
+    return table, tile_off, t, tiles
+
+
+def _finite(who, name, value, want="a finite number", ok=lambda v: True):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        refuse(who, name, want, value)
+    if v != v or v in (float("inf"), float("-inf")) or not ok(v):
+        refuse(who, name, want, value)
+    return v
+
+
+@_on_device
+def grad_clip_coef(table: torch.Tensor, tile_off: torch.Tensor, max_norm: float, tiles: int | None = None):
+    """Steps 1-3 of the clipped-SGD rule (stated at mrcnn_optim_clip_coef in include/maskrcnn_hip.h) on a device-resident tensor
+    table: table int64 [T,4] = (address of p, address of g or 0, address of b, numel), tile_off int64 [T+1] = the prefix sum of
+    ceil(numel / optim.TILE) → (info float64 [3] = (S, norm, c) with S the fp64 sum of g*g in a fixed order, norm = sqrt(S),
+    c = min(1, max_norm / (norm + 1e-6)); status int32 [1], bit 0: S is not finite). tiles: tile_off[T] as the table's builder knows
+    it (None reads it back from the device). The addresses must be live fp32 tensors of numel elements on this device: nothing here
+    can check that (maskrcnn_amd.optim.ClippedSGD does, before every call). Two launches, no host synchronisation."""
+    who = "grad_clip_coef"
+    table, tile_off, t, tiles = _optim_table(who, table, tile_off, tiles)
+    if not (isinstance(max_norm, (int, float)) and max_norm > 0):
+        refuse(who, "max_norm", "a number above 0", max_norm)
+    dev = table.device
+    info = torch.empty(3, dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = workspace(8 * tiles, dev)
+    _launch(lib.mrcnn_optim_clip_coef,
+            (table.data_ptr(), tile_off.data_ptr(), t, tiles, float(max_norm), ws.data_ptr(), info.data_ptr(), status.data_ptr(),
+             _stream()),
+            lambda: (0, (t, tiles, 1), 4 * tiles * int(lib.mrcnn_optim_tile()), "optim_clip_coef"))
+    return info, status
+
+
+@_on_device
+def sgd_apply(table: torch.Tensor, wd: torch.Tensor, tile_off: torch.Tensor, info: torch.Tensor | None, status: torch.Tensor | None,
+              lr: float, momentum: float, mode, tiles: int | None = None) -> None:
+    """Step 4 of the clipped-SGD rule in place on the table's tensors: per element in fp64 d = c g + wd p, B = momentum b + d,
+    b' = fp32(B), p' = fp32(p - lr B), g' = fp32(c g). table and tile_off as for grad_clip_coef, wd float64 [T]; info and status as
+    grad_clip_coef returned them (c and the non-finite flag are read on the device), or both None: c = 1 and no check. mode: "clip"
+    (writes g'), "step" (p', b', g') or "step_zero" (p', b' and +0 into g), or 0 / 1 / 2. With status bit 0 set nothing is written
+    but step_zero's zeros. The table lives on the device, so what it holds is the caller's to guarantee, as the addresses are:
+    numel below 2^31 per tensor, every wd finite, tile_off the prefix sum of ceil(numel / optim.TILE) — optim.build_table checks all
+    three on the host. One launch, no host synchronisation."""
+    who = "sgd_apply"
+    table, tile_off, t, tiles = _optim_table(who, table, tile_off, tiles)
+    wd = checked(who, "wd", wd, torch.float64, (t,), strides="refuse")
+    info = checked(who, "info", info, torch.float64, (3,), optional=True, strides="refuse")
+    status = checked(who, "status", status, _I32, (1,), optional=True, strides="refuse")
+    if (info is None) != (status is None):
+        refuse(who, "status", "None exactly when info is None", status)
+    lr = _finite(who, "lr", lr)
+    momentum = _finite(who, "momentum", momentum, "a number in [0, 1)", lambda v: 0.0 <= v < 1.0)
+    if mode in SGD_MODES:
+        mode = SGD_MODES.index(mode)
+    if type(mode) is not int or not 0 <= mode < len(SGD_MODES):
+        refuse(who, "mode", 'one of "clip", "step", "step_zero" (0, 1, 2)', mode)
+    per_element = (8, 24, 24)[mode]      # bytes read + written per element, worst case: step's store of g' is left out when c == 1
+    _launch(lib.mrcnn_optim_sgd_apply,
+            (table.data_ptr(), wd.data_ptr(), tile_off.data_ptr(), t, tiles, _ptr(info), _ptr(status), lr, momentum, mode, _stream()),
+            lambda: (0, (t, tiles, 1), per_element * tiles * int(lib.mrcnn_optim_tile()), "optim_sgd_apply"))
+
+
+# grad_clip_coef and sgd_apply have no torch.ops.maskrcnn schema and are not in ops.__all__ either, for the same reason. The front
+# end, which builds the table and keeps its pointers current, is maskrcnn_amd.optim.ClippedSGD.
