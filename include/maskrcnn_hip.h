@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 31
+#define MRCNN_ABI_VERSION 32
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -542,6 +542,69 @@ size_t mrcnn_conv_backward_workspace_bytes(int32_t batch, int32_t height, int32_
                                            int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
 int32_t mrcnn_conv_backward_weights_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
                                           int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
+
+/* ------------------------------------------------------------------------------------------------
+ * The backbone's backward: the conv backward above with a stride, and the two gradients that are not convolutions. With them every
+ * layer of the model has a backward (model.py:174-270: conv1 and downsample.0 of the first block of C3, C4 and C5 are 1 x 1 stride
+ * 2; the stem is 7 x 7 stride 2 pad 3 on the image, then SamePad2d(3,2) + MaxPool2d(3,2); P6 = MaxPool2d(1,2) of P5). BatchNorm
+ * stays frozen in every schedule, so there is still no gradient of `scale`. The four mrcnn_conv_*_f32 entry points above keep their
+ * signatures and their stride-1 launches and bits; mrcnn_conv_act_backward_f32 has no stride (it works on the output map).
+ *
+ *   stride  s = 1 or 2; OH = (H + pt + pb - KH) / s + 1, OW likewise, a remainder is legal (a 1 x 1 kernel on odd H uses the last
+ *           row). z is [B][OH][OW][Cout4] as above.
+ *   dw      [co,ky,kx,ci] = sum over (b,oy,ox) of z[b,oy,ox,co] * x[b, oy*s+ky-pt, ox*s+kx-pl, ci], taps outside the image
+ *           contributing nothing; any kernel size the stride-1 path takes. The rule above carries over word for word: an element
+ *           is an fp32 fmaf chain over a chunk's output pixels in ascending order, the chunks' sums are added in fp64 in ascending
+ *           order and narrowed last, two calls give the same bits. The chunk length L = mrcnn_conv_backward_weights_strided_chunk(...)
+ *           is a function of the shape only; it depends on the stride through M = B*OH*OW. No row counts at stride 2.
+ *   dx      at stride 2 for the 1 x 1 kernel without padding only (every strided conv of the model whose input needs a gradient).
+ *           mrcnn_conv_backward_data_strided_f32 writes the COMPACT gradient dxc [B][OH][OW][Cin], dxc[b,i,j,ci] = sum over co of
+ *           z[b,i,j,co] * w[co,0,0,ci]: the forward mrcnn_conv_bn_act_nhwc_f32 on z with w'[ci][co] = w[co][ci], a plain GEMM, bit
+ *           for bit. At stride 1 it is mrcnn_conv_backward_data_f32.
+ *   dilate  mrcnn_dilate2_sum_f32 writes the full gradient from the compact one: dx[b,2i,2j,:] = a[b,i,j,:], or a + b2 as ONE fp32
+ *           add where a second compact tensor is given (conv1 and downsample.0 of a strided block read the same x: the sum of
+ *           their two full-size gradients is a + b2 at the even positions and 0 + 0 elsewhere, bit for bit), and +0 at every other
+ *           element. a, b2 [B][ceil(H/2)][ceil(W/2)][C], dx [B][H][W][C], C % 4 == 0, odd H and W legal. Every byte of dx is
+ *           written exactly once, in 16-byte stores: no memset before it, no atomic. With one operand it is also the backward of
+ *           MaxPool2d(kernel 1, stride 2) (P6): a window of one tap always takes it. One launch.
+ *   pool    mrcnn_maxpool_backward_f32: the backward of the zero-padded max-pool mrcnn_maxpool_f32 computes (F.pad(..., 0) then
+ *           MaxPool2d, model.py:227-228), from the saved input x [B][H][W][C] and dy [B][OH][OW][C] -> dx [B][H][W][C].
+ *             which tap is taken   for every output element the window is walked in (ky, kx) row-major order, taps outside the
+ *                      image reading 0; the walk starts with max = -inf at the first tap and a tap takes over when it is strictly
+ *                      greater than the maximum so far (torch's `val > max`): the first of equal maxima wins.
+ *             a padding tap loses the gradient   where the taken tap lies outside the image its gradient is dropped. That happens
+ *                      when every real value of the window is <= 0 behind an earlier padding zero, or < 0 behind a later one: common
+ *                      behind a ReLU.
+ *             gather form   the thread that owns an input element adds, in fp32 from +0, the gradients of the at most
+ *                      ceil(k/s)^2 windows that take it, in ascending (oy, ox) order. No atomic, every byte of dx is written (+0
+ *                      where no window takes the element), two calls give the same bits.
+ *             no stored indices   the argmax is recomputed from x; the forward stays the unchanged launch and saves nothing.
+ *             NaN      a NaN tap takes over whatever the maximum was (torch's `|| isnan(val)`), so the LAST NaN of a window in walk
+ *                      order receives its gradient. A padding tap is never NaN. (A window of -inf alone keeps its first tap.)
+ *           kernel 1 .. 3, stride 1 .. 2, every pad in 0 .. kernel - 1, C % 4 == 0, fp32 NHWC. One launch.
+ * workspace: >= mrcnn_conv_backward_strided_workspace_bytes(...) bytes, 16-byte aligned, shared with mrcnn_conv_act_backward_f32 as
+ *   above. The chunk and workspace queries return 0 for arguments the entry points refuse. Every tensor <= 0xFFFFFFF0 bytes and on
+ *   a 16-byte boundary. Outside these limits: an error before any launch. Nothing here synchronises with the host.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_conv_backward_weights_strided_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* z,
+                                            int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                            int32_t pad_bottom, int32_t pad_right, float* dw, void* workspace, size_t workspace_bytes,
+                                            mrcnn_stream_t stream);
+int mrcnn_conv_backward_data_strided_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* w,
+                                         int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                         int32_t pad_bottom, int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes,
+                                         mrcnn_stream_t stream);
+size_t mrcnn_conv_backward_strided_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
+                                                   int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                                   int32_t pad_right);
+int32_t mrcnn_conv_backward_weights_strided_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
+                                                  int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                                  int32_t pad_right);
+int mrcnn_dilate2_sum_f32(const float* a, const float* b2, int32_t batch, int32_t height, int32_t width, int32_t channels, float* dx,
+                          mrcnn_stream_t stream);
+int mrcnn_maxpool_backward_f32(const float* dy, const float* x, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                               int32_t kernel, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                               int32_t pad_right, float* dx, mrcnn_stream_t stream);
 size_t mrcnn_conv3x3_winograd_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin);
 int mrcnn_conv3x3_winograd_nhwc_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
                                     const float* u, int32_t cout, const float* scale, const float* shift,

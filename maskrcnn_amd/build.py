@@ -30,6 +30,7 @@ SOURCES = {
     "crop.hip": ["-ffp-contract=off"] + (["-DMRCNN_CROP_STAMPS"] if os.environ.get("MRCNN_CROP_STAMPS") else []),
     "roi_align_backward.hip": ["-ffp-contract=off"],   # crop_backward's terms: w * (v * g) and the running sum, separately rounded fp32
     "conv_backward.hip": ["-ffp-contract=off"],   # g = dy * (y * (1 - y)) and z = g * scale: separately rounded fp32, as the rule states
+    "pool_backward.hip": ["-ffp-contract=off"],   # dilate2_sum's a + b2 and the max-pool backward's running sum: plain fp32 adds
     "conv.hip": [],
     "conv_f16.hip": [],
     "conv_f16p.hip": [],

@@ -1,6 +1,7 @@
-// Backward of the stride-1 fp32 NHWC convolution with a frozen affine and an activation (the layers train_model(layers="heads")
-// trains, model.py:1010-1016): gradients for the input, the weight, the shift and the residual. The rule is stated at
-// mrcnn_conv_act_backward_f32 in include/maskrcnn_hip.h. Built with -ffp-contract=off: g and z are separately rounded operations.
+// Backward of the fp32 NHWC convolution with a frozen affine and an activation (the layers train_model trains, model.py:1010-1016;
+// stride 1 for the heads, stride 2 for the stem and the first block of C3 / C4 / C5): gradients for the input, the weight, the
+// shift and the residual. The rule is stated at mrcnn_conv_act_backward_f32 and, for a stride, at mrcnn_conv_backward_weights_strided_f32
+// in include/maskrcnn_hip.h. Built with -ffp-contract=off: g and z are separately rounded operations.
 //   conv_act_backward   elementwise: dy, y -> z (= g * scale, pitch Cout4), g, the 2 x 2 residual sums, and per (workgroup, thread
 //                       row) fp64 partials of dshift — a thread owns channel quads and walks its pixels in ascending order.
 //   conv_weight_flip    w [Cout][KH][KW][Cin] -> w' [Cin][KH][KW][Cout4], taps mirrored: the data gradient is then the FORWARD
@@ -195,7 +196,7 @@ struct WgradParams {
     float* part;      // [chunks][Cout][N]
     const int* row_counts;
     int rows_per_group;
-    int H, W, Cin, Cout, Cout4, KW, pad_t, pad_l, OH, OW;
+    int H, W, Cin, Cout, Cout4, KW, pad_t, pad_l, OH, OW, stride;
     int M, N, L, tiles_m, tiles_n;
     unsigned x_bytes, z_bytes;
 };
@@ -287,8 +288,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_f32(const WgradParams 
             const int ohw = p.OH * p.OW;
             const int b = mm / ohw, rem = mm - b * ohw, oy = rem / p.OW, ox = rem - oy * p.OW;
             int4 e;
-            e.y = ok ? oy - p.pad_t : -(1 << 24);
-            e.z = ox - p.pad_l;
+            e.y = ok ? oy * p.stride - p.pad_t : -(1 << 24);
+            e.z = ox * p.stride - p.pad_l;
             e.x = ok ? ((b * p.H + e.y) * p.W + e.z) * p.Cin : 0;
             e.w = ok ? static_cast<int>(static_cast<unsigned>(mm) * static_cast<unsigned>(p.Cout4) * 4u) : static_cast<int>(OOB);
             tbl[slot * BK + tid] = e;
@@ -377,13 +378,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_f32(const WgradParams 
 
 // ------------------------------------------------------------------------------------------------ host
 struct BackwardShape {
-    int B, H, W, Cin, Cout, Cout4, KH, KW, pt, pl, pb, pr, OH, OW;
+    int B, H, W, Cin, Cout, Cout4, KH, KW, pt, pl, pb, pr, OH, OW, stride;
     long long M, N;
 };
 
 // The limits of the three entry points, checked before any launch.
 int fill_shape(BackwardShape& s, const char* who, int batch, int height, int width, int cin, int cout, int kh, int kw, int pad_top,
-               int pad_left, int pad_bottom, int pad_right) {
+               int pad_left, int pad_bottom, int pad_right, int stride = 1) {
+    if (!(stride == 1 || stride == 2)) return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: stride must be 1 or 2, got %d", who, stride);
     if (!(batch >= 1 && height >= 1 && width >= 1 && cin >= 4 && cin % 4 == 0 && cout >= 1))
         return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: bad shape B=%d H=%d W=%d Cin=%d (Cin %% 4 == 0 required) Cout=%d", who,
                            batch, height, width, cin, cout);
@@ -393,9 +395,11 @@ int fill_shape(BackwardShape& s, const char* who, int batch, int height, int wid
         return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: a pad larger than the kernel size - 1 (the data gradient's pads are K - 1 - pad)", who);
     s.B = batch; s.H = height; s.W = width; s.Cin = cin; s.Cout = cout; s.KH = kh; s.KW = kw;
     s.pt = pad_top; s.pl = pad_left; s.pb = pad_bottom; s.pr = pad_right;
-    s.OH = height + pad_top + pad_bottom - kh + 1;
-    s.OW = width + pad_left + pad_right - kw + 1;
-    if (!(s.OH >= 1 && s.OW >= 1)) return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: empty output", who);
+    s.stride = stride;
+    if (!(height + pad_top + pad_bottom >= kh && width + pad_left + pad_right >= kw))
+        return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: empty output", who);
+    s.OH = (height + pad_top + pad_bottom - kh) / stride + 1;
+    s.OW = (width + pad_left + pad_right - kw) / stride + 1;
     if (cout > 0x7ffffff0) return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: tensor too large", who);
     s.Cout4 = (cout + 3) / 4 * 4;
     s.M = 1LL * batch * s.OH * s.OW;
@@ -511,14 +515,15 @@ extern "C" int mrcnn_conv_backward_data_f32(const float* z, int32_t batch, int32
                                       kh - 1 - pad_bottom, kw - 1 - pad_right, nullptr, nullptr, nullptr, 1, 0, dx, stream);
 }
 
-extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
-                                               const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left,
-                                               int32_t pad_bottom, int32_t pad_right, const int32_t* row_counts,
-                                               int32_t rows_per_group, float* dw, void* workspace, size_t workspace_bytes,
-                                               mrcnn_stream_t stream) {
-    const char* who = "conv_backward_weights";
+namespace {
+
+// Both weight-gradient entry points: the stride only moves the pixel table's (iy0, ix0) and, through M, the chunk length.
+int backward_weights(const char* who, const float* x, int batch, int height, int width, int cin, const float* z, int cout, int kh,
+                     int kw, int stride, int pad_top, int pad_left, int pad_bottom, int pad_right, const int32_t* row_counts,
+                     int rows_per_group, float* dw, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
     BackwardShape s;
-    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right)) return rc;
+    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, stride)) return rc;
+    MRCNN_REQUIRE(!(row_counts && stride != 1), "%s: row counts need stride 1", who);
     MRCNN_REQUIRE(x && z && dw, "%s: null pointer", who);
     if (row_counts)
         MRCNN_REQUIRE(rows_per_group >= 1 && s.M % rows_per_group == 0, "%s: %lld output rows are not whole groups of %d", who, s.M,
@@ -530,7 +535,7 @@ extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, in
     p.x = x; p.z = z; p.part = static_cast<float*>(workspace); p.row_counts = row_counts;
     p.rows_per_group = row_counts ? rows_per_group : 1;
     p.H = height; p.W = width; p.Cin = cin; p.Cout = cout; p.Cout4 = s.Cout4; p.KW = kw; p.pad_t = pad_top; p.pad_l = pad_left;
-    p.OH = s.OH; p.OW = s.OW; p.M = static_cast<int>(s.M); p.N = static_cast<int>(s.N);
+    p.OH = s.OH; p.OW = s.OW; p.stride = stride; p.M = static_cast<int>(s.M); p.N = static_cast<int>(s.N);
     p.L = wgrad_chunk(s.M, cout, s.N);
     p.x_bytes = static_cast<unsigned>(4LL * batch * height * width * cin);
     p.z_bytes = static_cast<unsigned>(4LL * s.M * s.Cout4);
@@ -542,4 +547,72 @@ extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, in
                             : launch_wgrad<128, 2, 2>(p, chunks, st))
         return rc;
     return launch_reduce(p.part, 1LL * cout * s.N, chunks, 1LL * cout * s.N, dw, st);
+}
+
+}  // namespace
+
+extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
+                                               const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left,
+                                               int32_t pad_bottom, int32_t pad_right, const int32_t* row_counts,
+                                               int32_t rows_per_group, float* dw, void* workspace, size_t workspace_bytes,
+                                               mrcnn_stream_t stream) {
+    return backward_weights("conv_backward_weights", x, batch, height, width, cin, z, cout, kh, kw, 1, pad_top, pad_left, pad_bottom,
+                            pad_right, row_counts, rows_per_group, dw, workspace, workspace_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the entry points with a stride
+extern "C" size_t mrcnn_conv_backward_strided_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
+                                                              int32_t kh, int32_t kw, int32_t stride, int32_t pad_top,
+                                                              int32_t pad_left, int32_t pad_bottom, int32_t pad_right) {
+    BackwardShape s;
+    if (fill_shape(s, "conv_backward_strided_workspace_bytes", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom,
+                   pad_right, stride))
+        return 0;
+    return backward_workspace_bytes(s);
+}
+
+extern "C" int32_t mrcnn_conv_backward_weights_strided_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
+                                                             int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                                             int32_t pad_bottom, int32_t pad_right) {
+    BackwardShape s;
+    if (fill_shape(s, "conv_backward_weights_strided_chunk", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom,
+                   pad_right, stride))
+        return 0;
+    return wgrad_chunk(s.M, s.Cout, s.N);
+}
+
+extern "C" int mrcnn_conv_backward_weights_strided_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
+                                                       const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
+                                                       int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right,
+                                                       float* dw, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
+    return backward_weights("conv_backward_weights_strided", x, batch, height, width, cin, z, cout, kh, kw, stride, pad_top, pad_left,
+                            pad_bottom, pad_right, nullptr, 0, dw, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mrcnn_conv_backward_data_strided_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin,
+                                                    const float* w, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
+                                                    int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right,
+                                                    float* dx, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
+    const char* who = "conv_backward_data_strided";
+    if (stride == 1)
+        return mrcnn_conv_backward_data_f32(z, batch, height, width, cin, w, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, dx,
+                                            workspace, workspace_bytes, stream);
+    BackwardShape s;
+    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, stride)) return rc;
+    MRCNN_REQUIRE(kh == 1 && kw == 1 && pad_top == 0 && pad_left == 0 && pad_bottom == 0 && pad_right == 0,
+                  "%s: the stride-2 data gradient covers the 1 x 1 kernel without padding, got %d x %d with pads (%d, %d, %d, %d)", who,
+                  kh, kw, pad_top, pad_left, pad_bottom, pad_right);
+    MRCNN_REQUIRE(z && w && dx, "%s: null pointer", who);
+    const size_t need = sizeof(float) * static_cast<size_t>(s.N) * s.Cout4;
+    MRCNN_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                  "%s: workspace of %zu bytes, 16-byte aligned, needed (got %zu)", who, need, workspace_bytes);
+    float* wt = static_cast<float*>(workspace);
+    hipStream_t st = mrcnn::as_stream(stream);
+    const long long total = s.N * s.Cout4;
+    hipLaunchKernelGGL(conv_weight_flip, dim3(static_cast<unsigned>((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, w, cout,
+                       s.Cout4, 1, 1, cin, wt);
+    if (int rc = mrcnn::check_launch("conv_weight_flip")) return rc;
+    // the compact gradient [B][OH][OW][Cin]: a plain GEMM of z with w' over the output pixels
+    return mrcnn_conv_bn_act_nhwc_f32(z, batch, s.OH, s.OW, s.Cout4, wt, cin, 1, 1, 1, 0, 0, 0, 0, nullptr, nullptr, nullptr, 1, 0, dx,
+                                      stream);
 }

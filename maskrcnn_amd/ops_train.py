@@ -1,7 +1,8 @@
 """Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip), the five
-losses, forward and backward (csrc/losses.hip), the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip) and the backward
-of the stride-1 conv + frozen affine + activation (csrc/conv_backward.hip). ops.py re-exports every name here; argument checks and
-registration are _binding.py's."""
+losses, forward and backward (csrc/losses.hip), the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip), the backward
+of the conv + frozen affine + activation at stride 1 or 2 (csrc/conv_backward.hip) and the backbone's two other gradients, the
+dilation of a compact stride-2 gradient and the max-pool backward (csrc/pool_backward.hip). ops.py re-exports every name here;
+argument checks and registration are _binding.py's."""
 from __future__ import annotations
 
 import collections
@@ -381,16 +382,27 @@ def roi_align_pyramid_backward(grad_out: torch.Tensor, rois: torch.Tensor, pool:
 
 
 # --------------------------------------------------------------------------------------------------
-# Backward of the stride-1 conv + frozen affine + activation (csrc/conv_backward.hip)
+# Backward of the conv + frozen affine + activation, stride 1 or 2 (csrc/conv_backward.hip)
 # --------------------------------------------------------------------------------------------------
 ConvBackward = collections.namedtuple("ConvBackward", "dx dw dshift dresidual z")
 
 
-def conv_backward_chunk(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, pad=(0, 0, 0, 0)) -> int:
-    """The chunk length L of the weight gradient of this layer (mrcnn_conv_backward_weights_chunk): its pixel axis M = B*OH*OW is
-    summed in ceil(M / L) fp32 chains that a second launch adds in fp64. A function of the shape only; host arithmetic."""
+def _backward_stride(who, stride) -> int:
+    if type(stride) is not int or stride not in (1, 2):
+        refuse(who, "stride", "1 or 2", stride)
+    return stride
+
+
+def conv_backward_chunk(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, pad=(0, 0, 0, 0), stride: int = 1) -> int:
+    """The chunk length L of the weight gradient of this layer (mrcnn_conv_backward_weights_chunk, or _strided_chunk with a stride of
+    2): its pixel axis M = B*OH*OW is summed in ceil(M / L) fp32 chains that a second launch adds in fp64. A function of the shape
+    only (the stride enters through OH and OW); host arithmetic."""
     pt, pl, pb, pr = [int(v) for v in pad]
-    got = int(lib.mrcnn_conv_backward_weights_chunk(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw), pt, pl, pb, pr))
+    shape = (int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw))
+    if _backward_stride("conv_backward_chunk", stride) == 1:
+        got = int(lib.mrcnn_conv_backward_weights_chunk(*shape, pt, pl, pb, pr))
+    else:
+        got = int(lib.mrcnn_conv_backward_weights_strided_chunk(*shape, stride, pt, pl, pb, pr))
     if got < 1:
         raise RuntimeError(f"conv_backward_chunk: the conv backward refuses these arguments ({lib.mrcnn_last_error().decode()})")
     return got
@@ -399,8 +411,9 @@ def conv_backward_chunk(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw
 @_on_device
 def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tensor, y: torch.Tensor | None,
                          scale: torch.Tensor | None = None, pad=(0, 0, 0, 0), act: int = 0, res_div: int = 0, scatter: bool = False,
-                         row_counts: torch.Tensor | None = None, rows_per_group: int = 0, needs=(True, True, True, False)):
-    """The gradients of y = act(scale * conv(x, w) + shift (+ residual)) — conv_bn_act at stride 1, or deconv2x2 with scatter=True
+                         row_counts: torch.Tensor | None = None, rows_per_group: int = 0, needs=(True, True, True, False),
+                         stride: int = 1):
+    """The gradients of y = act(scale * conv(x, w) + shift (+ residual)) — conv_bn_act, or deconv2x2 with scatter=True
     (w [4*C,1,1,Cin], grad_out and y [B,2H,2W,C]) — for a FROZEN scale; the rule is stated at mrcnn_conv_act_backward_f32 in
     include/maskrcnn_hip.h. grad_out and y float32 in the output's shape (y is read only with an activation and may be None without),
     x float32 [B,H,W,Cin], w float32 [Cout,KH,KW,Cin], scale float32 [Cout] or None; pad, act (0 none, 1 ReLU, 2 sigmoid), row_counts
@@ -408,8 +421,13 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
     ConvBackward(dx [B,H,W,Cin], dw as w, dshift [Cout], dresidual [B,OH/res_div,OW/res_div,Cout], z [B,OH,OW,roundup(Cout,4)]);
     entries not asked for are None (z: when neither dx nor dw is). No gradient of scale: BatchNorm is frozen. dx is the forward
     kernel on z bit for bit; dw is summed in chunks of conv_backward_chunk(...) pixels, then in fp64; dshift in fp64. Two calls give
-    the same bits. Two launches per gradient, no floating-point atomic, no host synchronisation."""
+    the same bits. Two launches per gradient, no floating-point atomic, no host synchronisation.
+    stride 1 or 2 as the forward took it (the rule with a stride is stated at mrcnn_conv_backward_weights_strided_f32). At stride 2
+    OH = (H + top + bottom - KH) // 2 + 1; dw and dshift are as above for any kernel size; dx is returned only for a 1x1 kernel
+    without padding and is then the COMPACT gradient [B,OH,OW,Cin] — the values at the even positions of the full one, which
+    ops.dilate2_sum writes out (adding a second compact gradient on the way). No row_counts and no scatter at stride 2."""
     who = "conv_bn_act_backward"
+    stride = _backward_stride(who, stride)
     act, res_div, scatter, rpg = int(act), int(res_div), bool(scatter), int(rows_per_group)
     if len(needs) != 4:
         raise RuntimeError(f"{who}: needs must hold 4 flags (dx, dw, dshift, dresidual), got {len(needs)}")
@@ -433,9 +451,16 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
         refuse(who, "w", f"float32 [4*C,1,1,{cin}] without padding for the scatter", w)
     if min(pt, pl, pb, pr) < 0 or max(pt, pb) > kh - 1 or max(pl, pr) > kw - 1:
         refuse(who, "pad", f"(top, left, bottom, right) in 0 .. kernel size - 1 = ({kh - 1}, {kw - 1})", (pt, pl, pb, pr))
-    oh, ow = h + pt + pb - kh + 1, wd + pl + pr - kw + 1
-    if oh < 1 or ow < 1:
+    if h + pt + pb < kh or wd + pl + pr < kw:
         refuse(who, "x", f"float32 [B,H,W,Cin] no smaller than the {kh} x {kw} kernel with its padding", x)
+    oh, ow = (h + pt + pb - kh) // stride + 1, (wd + pl + pr - kw) // stride + 1
+    if stride == 2:
+        if need_dx and (kh != 1 or kw != 1 or (pt, pl, pb, pr) != (0, 0, 0, 0)):
+            refuse(who, "w", f"float32 [Cout,1,1,{cin}] without padding for a data gradient at stride 2 (needs[0])", w)
+        if row_counts is not None:
+            refuse(who, "row_counts", "None at stride 2", row_counts)
+        if scatter:
+            refuse(who, "scatter", "False at stride 2", scatter)
     out_shape = (b, 2 * h, 2 * wd, cout // 4) if scatter else (b, oh, ow, cout)
     grad_out = checked(who, "grad_out", grad_out, _F32, out_shape, align16=True)
     y = checked(who, "y", y, _F32, out_shape, optional=act == 0, align16=True)
@@ -449,7 +474,9 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
     if res_div == 2 and (oh % 2 or ow % 2):
         refuse(who, "res_div", f"1 for an odd output size ({oh} x {ow})", res_div)
     shape_args = (b, h, wd, cin, cout, kh, kw, pt, pl, pb, pr)
-    nbytes = int(lib.mrcnn_conv_backward_workspace_bytes(*shape_args))
+    strided_args = (b, h, wd, cin, cout, kh, kw, stride, pt, pl, pb, pr)
+    nbytes = int(lib.mrcnn_conv_backward_workspace_bytes(*shape_args) if stride == 1 else
+                 lib.mrcnn_conv_backward_strided_workspace_bytes(*strided_args))
     if nbytes < 1:
         raise RuntimeError(f"{who}: {lib.mrcnn_last_error().decode()}")
     dev, cout4, n = x.device, -(-cout // 4) * 4, kh * kw * cin
@@ -474,14 +501,28 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
                  _stream()),
                 lambda: (0, (m, cout, 1), 4 * m * (2 * cout + cout4), "conv_act_backward"))
     dx = dw = None
-    if need_dx:
+    if need_dx and stride == 2:
+        dx = torch.empty(b, oh, ow, cin, dtype=_F32, device=dev)
+        _launch(lib.mrcnn_conv_backward_data_strided_f32,
+                (z.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, stride, pt, pl, pb, pr, dx.data_ptr(), ws.data_ptr(), nbytes,
+                 _stream()),
+                lambda: (2.0 * m * n * cout, (m, cin, cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()), "conv_backward_data_strided"))
+    elif need_dx:
         dx = torch.empty(b, h, wd, cin, dtype=_F32, device=dev)
         _launch(lib.mrcnn_conv_backward_data_f32,
                 (z.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, pt, pl, pb, pr, dx.data_ptr(), ws.data_ptr(), nbytes,
                  _stream()),
                 lambda: (2.0 * m * n * cout, (b * h * wd, cin, kh * kw * cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()),
                          "conv_backward_data"))
-    if need_dw:
+    if need_dw and stride == 2:
+        dw = torch.empty(cout, kh, kw, cin, dtype=_F32, device=dev)
+        chunks2 = -(-m // int(lib.mrcnn_conv_backward_weights_strided_chunk(*strided_args)))
+        _launch(lib.mrcnn_conv_backward_weights_strided_f32,
+                (x.data_ptr(), b, h, wd, cin, z.data_ptr(), cout, kh, kw, stride, pt, pl, pb, pr, dw.data_ptr(), ws.data_ptr(), nbytes,
+                 _stream()),
+                lambda: (2.0 * m * n * cout, (cout, n, m), 4 * (x.numel() + m * cout4 + (2 * chunks2 + 1) * n * cout),
+                         "conv_backward_weights_strided"))
+    elif need_dw:
         dw = torch.empty(cout, kh, kw, cin, dtype=_F32, device=dev)
         chunks = -(-m // int(lib.mrcnn_conv_backward_weights_chunk(*shape_args)))
         _launch(lib.mrcnn_conv_backward_weights_f32,
@@ -494,6 +535,73 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
 
 # conv_bn_act_backward has no torch.ops.maskrcnn schema and is not in ops.__all__ either, for the same reason. The differentiable
 # front end is maskrcnn_amd.layers.
+
+
+# --------------------------------------------------------------------------------------------------
+# The backbone's other two gradients (csrc/pool_backward.hip)
+# --------------------------------------------------------------------------------------------------
+@_on_device
+def dilate2_sum(a: torch.Tensor, b: torch.Tensor | None = None, height: int | None = None, width: int | None = None,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """The full gradient of a stride-2 1x1 conv (or of MaxPool2d(1, 2): P6) from the compact one; the rule is stated at
+    mrcnn_dilate2_sum_f32 in include/maskrcnn_hip.h. a float32 [B,OH,OW,C] (C % 4 == 0), b the same shape or None, height and width
+    of the full map with OH = ceil(height / 2), OW = ceil(width / 2) → out float32 [B,height,width,C]:
+    out[:, 2i, 2j] = a[:, i, j] (+ b[:, i, j], one fp32 add), +0 everywhere else. Every byte of out is written once: no memset, no
+    atomic. One launch, no host synchronisation."""
+    who = "dilate2_sum"
+    a = checked(who, "a", a, _F32, (("B", 1), ("OH", 1), ("OW", 1), ("C", 4)), align16=True)
+    bb, oh, ow, c = a.shape
+    if c % 4:
+        refuse(who, "a", "float32 [B,OH,OW,C] with C a multiple of 4", a)
+    b = checked(who, "b", b, _F32, (bb, oh, ow, c), optional=True, align16=True)
+    if type(height) is not int or type(width) is not int or (height + 1) // 2 != oh or (width + 1) // 2 != ow:
+        refuse(who, "(height, width)", f"two ints with ceil(height / 2) = {oh} and ceil(width / 2) = {ow}", (height, width))
+    out = checked_out(who, "out", out, _F32, (bb, height, width, c), a.device)
+    if out.data_ptr() % 16:
+        refuse(who, "out", "on a 16-byte boundary", out)
+    _launch(lib.mrcnn_dilate2_sum_f32, (a.data_ptr(), _ptr(b), bb, height, width, c, out.data_ptr(), _stream()),
+            lambda: (0, (bb * height * width, c, 1), 4 * (out.numel() + a.numel() * (1 if b is None else 2)), "dilate2_sum"))
+    return out
+
+
+@_on_device
+def maxpool_backward(grad_out: torch.Tensor, x: torch.Tensor, kernel: int, stride: int, pad=(0, 0, 0, 0),
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """The backward of ops.maxpool (zero padding, then the max) from the saved input; the rule is stated at mrcnn_maxpool_backward_f32
+    in include/maskrcnn_hip.h: a window's gradient goes to its first maximum in (ky, kx) order, padding taps reading 0 — and is
+    dropped where a padding tap is that maximum —, and an input element adds the gradients of its windows in ascending (oy, ox) order
+    in fp32. x float32 [B,H,W,C] (C % 4 == 0), grad_out float32 [B,OH,OW,C], kernel 1 .. 3, stride 1 .. 2, pad = (top, left, bottom,
+    right) each in 0 .. kernel - 1 → out float32 [B,H,W,C], every element written. One launch, no atomic, no host synchronisation."""
+    who = "maxpool_backward"
+    if type(kernel) is not int or not 1 <= kernel <= 3:
+        refuse(who, "kernel", "an int in 1 .. 3", kernel)
+    if type(stride) is not int or not 1 <= stride <= 2:
+        refuse(who, "stride", "1 or 2", stride)
+    try:
+        pt, pl, pb, pr = pads = tuple(int(v) for v in pad)
+    except (TypeError, ValueError):
+        pads = None
+    if pads is None or min(pads) < 0 or max(pads) > kernel - 1:
+        refuse(who, "pad", f"(top, left, bottom, right) in 0 .. kernel - 1 = {kernel - 1}", pad)
+    x = checked(who, "x", x, _F32, (("B", 1), ("H", 1), ("W", 1), ("C", 4)), align16=True)
+    b, h, w, c = x.shape
+    if c % 4:
+        refuse(who, "x", "float32 [B,H,W,C] with C a multiple of 4", x)
+    if h + pt + pb < kernel or w + pl + pr < kernel:
+        refuse(who, "x", f"float32 [B,H,W,C] no smaller than the {kernel} x {kernel} window with its padding", x)
+    oh, ow = (h + pt + pb - kernel) // stride + 1, (w + pl + pr - kernel) // stride + 1
+    grad_out = checked(who, "grad_out", grad_out, _F32, (b, oh, ow, c), align16=True)
+    out = checked_out(who, "out", out, _F32, (b, h, w, c), x.device)
+    if out.data_ptr() % 16:
+        refuse(who, "out", "on a 16-byte boundary", out)
+    _launch(lib.mrcnn_maxpool_backward_f32,
+            (grad_out.data_ptr(), x.data_ptr(), b, h, w, c, kernel, stride, pt, pl, pb, pr, out.data_ptr(), _stream()),
+            lambda: (0, (b * h * w, c, kernel * kernel), 4 * (2 * x.numel() + grad_out.numel()), "maxpool_backward"))
+    return out
+
+
+# dilate2_sum and maxpool_backward have no torch.ops.maskrcnn schema and are not in ops.__all__ either, for the same reason. The
+# differentiable front ends are maskrcnn_amd.layers.conv_bn_act(stride=2), .maxpool and .bottleneck.
 
 
 # --------------------------------------------------------------------------------------------------
