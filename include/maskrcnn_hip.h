@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 32
+#define MRCNN_ABI_VERSION 33
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -1236,6 +1236,53 @@ int mrcnn_optim_clip_coef(const int64_t* table, const int64_t* tile_off, int32_t
 int mrcnn_optim_sgd_apply(const int64_t* table, const double* wd, const int64_t* tile_off, int32_t num_tensors, int64_t tiles,
                           const double* info, const int32_t* status, double lr, double momentum, int32_t mode,
                           mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The RPN's training branch on the sampled anchors alone (csrc/rpn_train.hip). The reference's RPN losses read the anchors with
+ * rpn_match != 0 only (model.py:652-718: torch.nonzero, then gathers), and nothing else carries a gradient into the RPN (the
+ * proposals are made from .data, model.py:1349-1365). So the shared 3x3 conv and the two 1x1 heads are differentiated on those
+ * anchors alone: their 3x3xC input patches are gathered into GEMM rows, and the patch gradients are scattered back into the maps.
+ *
+ * Anchor order is mrcnn_rpn_scores_deltas_v2_f32's: level l has H_l x W_l pixels and apl anchors per pixel, anchor
+ * a = first[l] + (y W_l + x) apl + r with first[0] = 0, first[l+1] = first[l] + H_l W_l apl; A = first[levels].
+ *
+ * mrcnn_anchor_compact: match int32 [batch][num_anchors] -> index int32 [batch][capacity], num int32 [batch], status int32 [batch].
+ *   index[b] holds the anchors of image b with match != 0 in ASCENDING anchor index (so the k-th positive in anchor order is still
+ *   the k-th positive of the compacted row, which is how mrcnn_rpn_loss_forward pairs it with target_bbox[b][k]); num[b] =
+ *   min(capacity, their number); the slots at or past num[b] are -1. status bit 0: the image has more than capacity such anchors
+ *   (the first capacity are kept). One launch of one workgroup per image, whatever batch is; no host synchronisation.
+ *
+ * mrcnn_pyramid_patch_gather_f32: maps[l] fp32 [batch][H_l][W_l][channels] (NHWC) -> patches fp32 [batch * capacity][9 * channels].
+ *   Row (b, k) with anchor index[b][k] on pixel (py, px) of level l holds, at (ky 3 + kx) channels + c, the value
+ *   maps[l][b][py + ky - 1][px + kx - 1][c]: SamePad2d(3, 1) and the 3x3 window, in the order in which an OHWI weight
+ *   [Cout][3][3][channels] flattens, so that weight viewed as [Cout][1][1][9 channels] is the GEMM's. A tap outside the map is +0.
+ *   A slot k >= num[b], or whose index is outside [0, A), is an empty slot: all +0. EVERY byte of patches is written. It is a
+ *   copy: the bits of the map, -0 and NaN payloads included. One launch.
+ *
+ * mrcnn_pyramid_patch_scatter_f32: the gather's backward. dpatch fp32 [batch * capacity][9 * channels] -> grad_maps[l] fp32
+ *   [batch][H_l][W_l][channels]; a null grad_maps[l] means that level's gradient is not needed. The rule, bit for bit:
+ *   grad_maps[l][b][y][x][c] is the fp32 sum, starting from +0, each add separately rounded, in ascending slot k < num[b], over the
+ *   entries index[b][k] of level l whose pixel (py, px) has |py - y| <= 1 and |px - x| <= 1, of dpatch[b][k][y - py + 1][x - px + 1][c].
+ *   The thread that owns a map element takes that sum itself (map-stationary, as mrcnn_roi_align_pyramid_backward_f32): no atomic,
+ *   no memset beforehand — EVERY byte of every requested map is written, +0 where nothing lands —, two calls give the same bits,
+ *   and an image's gradient does not depend on the rest of the batch. The rows of empty slots are never read. index[b][0, num[b])
+ *   must be ascending, as mrcnn_anchor_compact writes it (the entries that can reach a pixel are then three contiguous ranges, one
+ *   per map row, whose ends are the numbers of entries below six keys); a row that is not is memory-safe and its gradient unspecified. One launch (none when
+ *   every grad_maps[l] is null).
+ *
+ * Limits, checked before any launch: levels in [1, 8], every H_l and W_l in [1, 16384], channels % 4 == 0, anchors_per_location in
+ * [1, 16], capacity in [1, 1024], batch in [1, 65535], batch * num_anchors < 2^31 (compact), A < 2^31, every map and the patch
+ * matrix 16-byte aligned and at most 2^30 elements (the 4 GiB range of the conv forward). No call synchronises with the host or
+ * allocates.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_anchor_compact(const int32_t* match, int32_t batch, int32_t num_anchors, int32_t capacity, int32_t* index, int32_t* num,
+                         int32_t* status, mrcnn_stream_t stream);
+int mrcnn_pyramid_patch_gather_f32(const float* const maps[8], const int32_t map_h[8], const int32_t map_w[8], int32_t levels,
+                                   int32_t batch, int32_t channels, int32_t anchors_per_location, const int32_t* index,
+                                   const int32_t* num, int32_t capacity, float* patches, mrcnn_stream_t stream);
+int mrcnn_pyramid_patch_scatter_f32(const float* dpatch, const int32_t map_h[8], const int32_t map_w[8], int32_t levels,
+                                    int32_t batch, int32_t channels, int32_t anchors_per_location, const int32_t* index,
+                                    const int32_t* num, int32_t capacity, float* const grad_maps[8], mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ from . import ops  # noqa: F401  (registers torch.ops.maskrcnn.*)
 from . import losses  # noqa: F401  (the training losses on the targets' padded outputs)
 from . import layers  # noqa: F401  (the head layers' conv / transposed conv with a grad_fn)
 from . import optim  # noqa: F401  (ClippedSGD: gradient norm, clip and momentum step in three launches)
+from . import rpn_train  # noqa: F401  (TrainableRPN: a dense pass without a graph, forward and backward on the sampled anchors)
 
 
 class _RoiAlignNCHW(_torch.autograd.Function):
@@ -61,4 +62,4 @@ def roi_align(inputs, pool_size, image_shape):
     return ops.nhwc_to_nchw(pooled)
 
 
-__all__ = ["ops", "roi_align", "losses", "layers", "optim"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)
+__all__ = ["ops", "roi_align", "losses", "layers", "optim", "rpn_train"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)

@@ -56,6 +56,7 @@ SOURCES = {
     "detection_targets.hip": ["-ffp-contract=off"],   # mrn_samples: fp32 IoU and deltas, the fp64 neg_limit, the crop's lerps
     "losses.hip": ["-ffp-contract=off"],     # the five training losses: every term and derivative in fp64, operation by operation
     "optim.hip": ["-ffp-contract=off"],      # clipped SGD: g*g + acc, c*g + wd*p, momentum*b + d, p - lr*B, each rounded on its own in fp64
+    "rpn_train.hip": ["-ffp-contract=off"],  # the patch scatter's running sum: plain fp32 adds in slot order
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-fast-math",
           "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

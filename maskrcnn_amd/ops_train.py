@@ -1,7 +1,8 @@
 """Bindings of the training side: RPN targets (csrc/targets.hip), detection targets (csrc/detection_targets.hip), the five
 losses, forward and backward (csrc/losses.hip), the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip), the backward
 of the conv + frozen affine + activation at stride 1 or 2 (csrc/conv_backward.hip) and the backbone's two other gradients, the
-dilation of a compact stride-2 gradient and the max-pool backward (csrc/pool_backward.hip). ops.py re-exports every name here;
+dilation of a compact stride-2 gradient and the max-pool backward (csrc/pool_backward.hip), clipped SGD (csrc/optim.hip) and the
+RPN's training branch on the sampled anchors: compaction, patch gather and patch scatter (csrc/rpn_train.hip). ops.py re-exports every name here;
 argument checks and registration are _binding.py's."""
 from __future__ import annotations
 
@@ -689,3 +690,146 @@ def sgd_apply(table: torch.Tensor, wd: torch.Tensor, tile_off: torch.Tensor, inf
 
 # grad_clip_coef and sgd_apply have no torch.ops.maskrcnn schema and are not in ops.__all__ either, for the same reason. The front
 # end, which builds the table and keeps its pointers current, is maskrcnn_amd.optim.ClippedSGD.
+
+
+# --------------------------------------------------------------------------------------------------
+# The RPN's training branch on the sampled anchors: compaction, patch gather, patch scatter (csrc/rpn_train.hip)
+# --------------------------------------------------------------------------------------------------
+_MAX_LEVELS, _MAX_SIDE, _MAX_APL, _MAX_CAPACITY, _MAX_IMAGES, _MAX_ELEMENTS = 8, 16384, 16, 1024, 65535, 1 << 30
+
+
+def _int_in(who, name, value, lo, hi) -> int:
+    if type(value) is not int or not lo <= value <= hi:
+        refuse(who, name, f"an int in {lo} .. {hi}", value)
+    return value
+
+
+def _pyramid_sizes(who, sizes, apl: int):
+    """[(H_l, W_l)] of 1 .. 8 levels, each side in 1 .. 16384 → (the list, A = the number of anchors, below 2^31)."""
+    try:
+        sizes = [(int(h), int(w)) for h, w in sizes]
+    except (TypeError, ValueError):
+        sizes = []
+    if not 1 <= len(sizes) <= _MAX_LEVELS or min(min(s) for s in sizes) < 1 or max(max(s) for s in sizes) > _MAX_SIDE:
+        refuse(who, "map_sizes", f"the (H, W) of 1 .. {_MAX_LEVELS} levels, each side in 1 .. {_MAX_SIDE}", sizes)
+    a = apl * sum(h * w for h, w in sizes)
+    if a >= 1 << 31:
+        refuse(who, "map_sizes", "levels of fewer than 2^31 anchors in all", sizes)
+    return sizes, a
+
+
+def _index_and_num(who, index, num):
+    index = checked(who, "index", index, _I32, (("B", 1), ("K", 1)), hint=" as anchor_compact returned it")
+    b, k = index.shape
+    if b > _MAX_IMAGES or k > _MAX_CAPACITY:
+        refuse(who, "index", f"int32 [B,K] with B in 1 .. {_MAX_IMAGES} and K in 1 .. {_MAX_CAPACITY}", index)
+    return index, checked(who, "num", num, _I32, (b,), hint=" as anchor_compact returned it"), b, k
+
+
+def _level_args(sizes):
+    pad = [1] * (_MAX_LEVELS - len(sizes))
+    return (c_i32 * _MAX_LEVELS)(*[h for h, _ in sizes], *pad), (c_i32 * _MAX_LEVELS)(*[w for _, w in sizes], *pad)
+
+
+def _level_ptrs(tensors):
+    return (c_vp * _MAX_LEVELS)(*[_ptr(t) for t in tensors], *[None] * (_MAX_LEVELS - len(tensors)))
+
+
+@_on_device
+def anchor_compact(match: torch.Tensor, count: int):
+    """match int32 [B,A] (rpn_match as sample_by_key leaves it) → (index int32 [B,count]: an image's anchors with match != 0 in
+    ascending anchor index, -1 in the slots at or past num; num int32 [B] = min(count, their number); status int32 [B], bit 0: the
+    image has more than count such anchors, of which the first count are kept). The rule is stated at mrcnn_anchor_compact in
+    include/maskrcnn_hip.h. count in 1 .. 1024, B in 1 .. 65535, B * A < 2^31. One launch, no host synchronisation."""
+    who = "anchor_compact"
+    match = checked(who, "match", match, _I32, (("B", 1), ("A", 1)))
+    b, a = match.shape
+    if b > _MAX_IMAGES or b * a >= 1 << 31:
+        refuse(who, "match", f"int32 [B,A] with B in 1 .. {_MAX_IMAGES} and B * A < 2^31", match)
+    count = _int_in(who, "count", count, 1, _MAX_CAPACITY)
+    dev = match.device
+    index = torch.empty(b, count, dtype=_I32, device=dev)
+    num = torch.empty(b, dtype=_I32, device=dev)
+    status = torch.empty(b, dtype=_I32, device=dev)
+    _launch(lib.mrcnn_anchor_compact, (match.data_ptr(), b, a, count, index.data_ptr(), num.data_ptr(), status.data_ptr(), _stream()),
+            lambda: (0, (b, a, count), 4 * b * (a + count), "anchor_compact"))
+    return index, num, status
+
+
+@_on_device
+def pyramid_patch_gather(maps, index: torch.Tensor, num: torch.Tensor, anchors_per_location: int = 3,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """The 3x3xC input patches of the sampled anchors, as GEMM rows; the rule is stated at mrcnn_pyramid_patch_gather_f32 in
+    include/maskrcnn_hip.h. maps: 1 .. 8 float32 NHWC tensors [B,H_l,W_l,C] (C % 4 == 0), index int32 [B,K] and num int32 [B] as
+    anchor_compact returned them → patches float32 [B*K,9*C]: row (b, k) holds map_l[b, py+ky-1, px+kx-1, c] at (ky*3+kx)*C + c for
+    the pixel (py, px) and level l of anchor index[b,k] — the flattening of an OHWI weight —, +0 for a tap outside the map and for
+    every tap of an empty slot (k >= num[b], or an index outside the pyramid). A copy: bit exact; every byte of out is written. One
+    launch, no host synchronisation."""
+    who = "pyramid_patch_gather"
+    if not isinstance(maps, (list, tuple)) or not 1 <= len(maps) <= _MAX_LEVELS:
+        refuse(who, "maps", f"a list of 1 .. {_MAX_LEVELS} float32 [B,H,W,C] tensors", maps if isinstance(maps, torch.Tensor) else type(maps).__name__)
+    apl = _int_in(who, "anchors_per_location", anchors_per_location, 1, _MAX_APL)
+    index, num, b, k = _index_and_num(who, index, num)
+    first = checked(who, "maps[0]", maps[0], _F32, (b, ("H", 1), ("W", 1), ("C", 4)), align16=True)
+    c = first.size(3)
+    if c % 4:
+        refuse(who, "maps[0]", "float32 [B,H,W,C] with C a multiple of 4", first)
+    maps = [first] + [checked(who, f"maps[{l}]", m, _F32, (b, ("H", 1), ("W", 1), c), align16=True) for l, m in enumerate(maps) if l]
+    sizes, _ = _pyramid_sizes(who, [(m.size(1), m.size(2)) for m in maps], apl)
+    for l, m in enumerate(maps):
+        if m.numel() > _MAX_ELEMENTS:
+            refuse(who, f"maps[{l}]", "float32 [B,H,W,C] of at most 2^30 elements", m)
+    if 9 * c * k * b > _MAX_ELEMENTS:
+        refuse(who, "index", f"int32 [B,K] with B * K * 9 * C ({b} * {k} * 9 * {c}) at most 2^30", index)
+    out = checked_out(who, "out", out, _F32, (b * k, 9 * c), first.device)
+    if out.data_ptr() % 16:
+        refuse(who, "out", "on a 16-byte boundary", out)
+    hs, ws = _level_args(sizes)
+    _launch(lib.mrcnn_pyramid_patch_gather_f32,
+            (_level_ptrs(maps), hs, ws, len(maps), b, c, apl, index.data_ptr(), num.data_ptr(), k, out.data_ptr(), _stream()),
+            lambda: (0, (b * k, 9 * c, 1), 8 * out.numel(), "pyramid_patch_gather"))
+    return out
+
+
+@_on_device
+def pyramid_patch_scatter(dpatch: torch.Tensor, index: torch.Tensor, num: torch.Tensor, map_sizes, channels: int,
+                          anchors_per_location: int = 3, needs=None, out=None):
+    """The backward of pyramid_patch_gather; the rule is stated at mrcnn_pyramid_patch_scatter_f32 in include/maskrcnn_hip.h.
+    dpatch float32 [B*K,9*C], index int32 [B,K] and num int32 [B] as the gather took them, map_sizes = [(H_l, W_l)] of the 1 .. 8
+    levels, channels = C → [grad_l float32 [B,H_l,W_l,C]]: per element the fp32 sum from +0, in ascending slot k < num[b], of
+    dpatch[b,k,y-py+1,x-px+1,c] over the entries of level l within one pixel of (y, x). needs: one flag per level (None: all); a
+    level that is not needed is None in the result and costs nothing. out: the tensors to write into (an entry of a level that is
+    not needed is ignored). Every byte of every returned map is written; no memset, no atomic; two calls give the same bits; index
+    must be ascending within num[b], as anchor_compact writes it. One launch, no host synchronisation."""
+    who = "pyramid_patch_scatter"
+    apl = _int_in(who, "anchors_per_location", anchors_per_location, 1, _MAX_APL)
+    if type(channels) is not int or channels < 4 or channels % 4:
+        refuse(who, "channels", "an int, a multiple of 4", channels)
+    index, num, b, k = _index_and_num(who, index, num)
+    sizes, _ = _pyramid_sizes(who, map_sizes, apl)
+    if 9 * channels * k * b > _MAX_ELEMENTS:
+        refuse(who, "index", f"int32 [B,K] with B * K * 9 * C ({b} * {k} * 9 * {channels}) at most 2^30", index)
+    dpatch = checked(who, "dpatch", dpatch, _F32, (b * k, 9 * channels), align16=True)
+    needs = [True] * len(sizes) if needs is None else [bool(v) for v in needs]
+    if len(needs) != len(sizes):
+        raise RuntimeError(f"{who}: needs must hold {len(sizes)} flags (one per level), got {len(needs)}")
+    if out is not None and len(out) != len(sizes):
+        raise RuntimeError(f"{who}: out must hold {len(sizes)} tensors (one per level), got {len(out)}")
+    dev, grads = dpatch.device, []
+    for l, (h, w) in enumerate(sizes):
+        if b * h * w * channels > _MAX_ELEMENTS:
+            refuse(who, "map_sizes", f"levels of at most 2^30 elements each (level {l}: {b} * {h} * {w} * {channels})", sizes)
+        g = checked_out(who, f"grad_{l}", None if out is None else out[l], _F32, (b, h, w, channels), dev) if needs[l] else None
+        if g is not None and g.data_ptr() % 16:
+            refuse(who, f"grad_{l}", "on a 16-byte boundary", g)
+        grads.append(g)
+    hs, ws = _level_args(sizes)
+    _launch(lib.mrcnn_pyramid_patch_scatter_f32,
+            (dpatch.data_ptr(), hs, ws, len(sizes), b, channels, apl, index.data_ptr(), num.data_ptr(), k, _level_ptrs(grads), _stream()),
+            lambda: (0, (b * k, 9 * channels, 1), 4 * (dpatch.numel() + sum(g.numel() for g in grads if g is not None)),
+                     "pyramid_patch_scatter"))
+    return grads
+
+
+# anchor_compact, pyramid_patch_gather and pyramid_patch_scatter have no torch.ops.maskrcnn schema and are not in ops.__all__
+# either, for the same reason. The differentiable front end is maskrcnn_amd.rpn_train (pyramid_patches, TrainableRPN).
