@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 33
+#define MRCNN_ABI_VERSION 34
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -1168,6 +1168,8 @@ int mrcnn_mask_targets_f32(const float* gt_masks, int32_t num_rows, int32_t heig
  *   slots of each image in slot order.
  * mrcnn_head_loss_backward → grad_logits, grad_bbox, grad_masks in the predictions' shapes: zeros but the slot's logits row, the
  *   class's row of pred_bbox and the class's plane of pred_masks; the mask gradient is written with 16-byte stores.
+ * The classifier alone: target_mask and pred_masks may BOTH be null (and then grad_masks must be). The mask sum and count are 0
+ *   and no mask gradient is written; the class and box columns, their launches and their bits are those of the full call.
  * ---------------------------------------------------------------------------------------------- */
 int32_t mrcnn_rpn_loss_chunks(int32_t num_anchors);
 size_t mrcnn_rpn_loss_workspace_bytes(int32_t batch, int32_t num_anchors, int32_t count);
@@ -1283,6 +1285,74 @@ int mrcnn_pyramid_patch_gather_f32(const float* const maps[8], const int32_t map
 int mrcnn_pyramid_patch_scatter_f32(const float* dpatch, const int32_t map_h[8], const int32_t map_w[8], int32_t levels,
                                     int32_t batch, int32_t channels, int32_t anchors_per_location, const int32_t* index,
                                     const int32_t* num, int32_t capacity, float* const grad_maps[8], mrcnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The mask head's class-plane branch in training (csrc/mask_train.hip). Mask.mask_loss (model.py:922-953) gathers, of the positive
+ * slots, the plane of the slot's own class, and nothing else carries a gradient into the mask head. So conv5 (the 1x1 conv to C
+ * planes) and the loss are computed for ONE plane per slot, on the first P slots of an image alone (mrcnn_detection_targets puts
+ * the positives first).
+ *
+ * Notation. S = batch * P plane slots, P = plane_slots per image, 1 <= P <= count. Plane slot (b, s) belongs to target slot (b, s)
+ * of the [batch][count] target tensors ids (target_class_ids) and target_mask, which are read in place with stride count; num is
+ * int32 [batch] (num_pos, or num_pos + num_neg: a negative's id is 0), clamped into [0, count]. Q = mask_height * mask_width.
+ * Slot (b, s) is ACTIVE when s < min(num[b], P) and 0 < ids[b][s] < C; k = ids[b][s] is its class. The data of a slot that is not
+ * active — its rows of x, y, dy, p and target_mask — is never read, whatever it holds.
+ * status int32 [batch] (the forward calls): bit 1 (value 2): a class id outside 0 .. C-1 in a slot below num[b], as
+ * mrcnn_head_loss_forward reports it (the slot is skipped); bit 2 (value 4): a slot s >= P below num[b] with ids > 0, a positive the
+ * planes have no room for (left out).
+ *
+ * mrcnn_class_plane_conv_f32: x fp32 [S][mh][mw][cin] (NHWC), w fp32 [C][cin], bias fp32 [C] or null -> y fp32 [S][mh][mw].
+ *   Active slot: z = fp32(double(bias[k]) + T) (z = fp32(T) without a bias), T the fp64 sum of the products double(x[..][c]) *
+ *   double(w[k][c]), each exact in fp64, in this order, a function of cin alone: lane l of 64 adds, from +0, the channels
+ *   4 (l + 64 i) + j for i = 0, 1, .. outer and j = 0 .. 3 inner (a lane without a channel holds +0); then the lane sums
+ *   meet in a butterfly, v[l] = v[l] + v[l xor d] for d = 32, 16, 8, 4, 2, 1, each add rounded in fp64. y = z for act 0;
+ *   y = 1.0f / (1.0f + expf(-z)) for act 2, the sigmoid epilogue of the conv forward (the library is built without fast-math, so the
+ *   same bits). A slot that is not active: its y rows are +0. EVERY byte of y is written. One launch.
+ * mrcnn_class_plane_conv_backward_f32: dy and y fp32 [S][mh][mw] (y read at act 2 only, may be null at act 0), x, w as above ->
+ *   dx fp32 [S][mh][mw][cin], dw fp32 [C][cin], dbias fp32 [C], each optional (null: not needed; x may be null when dw is).
+ *   g = dy at act 0; at act 2 t = 1 - y, u = y t, g = dy u, three separately rounded fp32 operations (mrcnn_conv_act_backward_f32's
+ *   rule). dx[s][q][c] = g[s][q] w[k][c], one fp32 product: what the dense data gradient gives, an fmaf chain whose other terms
+ *   are zero. dw[k][c] = fp32(the fp64 sum, from +0 in ascending (b, s), over the active slots of class k of D[s][c]), with D[s][c]
+ *   the fp64 sum of the exact products double(g[s][q]) double(x[s][q][c]) in this order, a function of Q alone: the pixels are cut
+ *   into chunks of 64; within a chunk v = 0 .. 3 adds the pixels 64 chunk + v + 4 j, j ascending, from +0, and the four sums are
+ *   added as ((v0 + v1) + v2) + v3; the chunk sums are added from +0 in ascending chunk. dbias[k] is the same with g alone. Rows
+ *   of a class without an active slot, dx rows of a slot that is not active: +0. EVERY byte of every requested output is written.
+ *   Store-and-sum: one pass over x writes dx and the per-(slot, chunk) sums into the workspace
+ *   (mrcnn_class_plane_conv_backward_workspace_bytes, 8-byte aligned; not needed for dx alone); a finishing launch has the owner
+ *   of (k, c) add its class's slots, found by ballots over ids. Two launches whatever batch is (one for dx alone); two calls give
+ *   the same bits.
+ * mrcnn_mask_plane_loss_forward: p fp32 [batch][P][mh][mw], target_mask fp32 [batch][count][mh][mw] -> sums fp64 [batch], counts
+ *   int32 [batch] (Q x the active slots), status. Term and derivative are the mask rule of mrcnn_head_loss_forward, word for word
+ *   and in the same code (csrc/loss_math.hpp): binary cross entropy in fp64 from the fp32 p, max(log p, -100), log1p(-p);
+ *   derivative (p - y) / max(p (1 - p), 1e-12). A slot's terms are summed as there (thread t of 256 adds elements t, t + 256, ..,
+ *   then the workgroup sum), and a second launch adds an image's slots in slot order: sums equals the mask column of
+ *   mrcnn_head_loss_forward on the dense tensor bit for bit. An empty loss is 0. workspace: mrcnn_mask_plane_loss_workspace_bytes.
+ * mrcnn_mask_plane_loss_backward -> grad_p fp32 [batch][P][mh][mw] in one launch: the derivative times grad_out / count in fp64,
+ *   narrowed last; grad_out fp32 [1] and the counts summed over the batch (per_image == 0) or grad_out fp32 [batch] and the image's
+ *   own count (per_image != 0), both read from device memory; 0 for an empty loss. Slots that are not active: +0. EVERY byte written.
+ *
+ * Limits, checked before any launch: batch in [1, 65535], count in [1, 1024], P in [1, count], C in [2, 4096], mh and mw in [1, 64],
+ * cin % 4 == 0 in [4, 4096], act 0 or 2; x, dx and w 16-byte aligned; offsets are 64-bit. No floating-point atomic, no memset, no
+ * last-block ticket; no call synchronises with the host or allocates.
+ * ---------------------------------------------------------------------------------------------- */
+int mrcnn_class_plane_conv_f32(const float* x, const float* w, const float* bias, const int32_t* ids, const int32_t* num,
+                               int32_t batch, int32_t count, int32_t plane_slots, int32_t num_classes, int32_t mask_height,
+                               int32_t mask_width, int32_t cin, int32_t act, float* y, int32_t* status, mrcnn_stream_t stream);
+size_t mrcnn_class_plane_conv_backward_workspace_bytes(int32_t batch, int32_t plane_slots, int32_t mask_height, int32_t mask_width,
+                                                       int32_t cin);
+int mrcnn_class_plane_conv_backward_f32(const float* dy, const float* y, const float* x, const float* w, const int32_t* ids,
+                                        const int32_t* num, int32_t batch, int32_t count, int32_t plane_slots, int32_t num_classes,
+                                        int32_t mask_height, int32_t mask_width, int32_t cin, int32_t act, float* dx, float* dw,
+                                        float* dbias, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+size_t mrcnn_mask_plane_loss_workspace_bytes(int32_t batch, int32_t plane_slots);
+int mrcnn_mask_plane_loss_forward(const float* p, const float* target_mask, const int32_t* ids, const int32_t* num, int32_t batch,
+                                  int32_t count, int32_t plane_slots, int32_t num_classes, int32_t mask_height, int32_t mask_width,
+                                  double* sums, int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                                  mrcnn_stream_t stream);
+int mrcnn_mask_plane_loss_backward(const float* p, const float* target_mask, const int32_t* ids, const int32_t* num,
+                                   const int32_t* counts, const float* grad_out, int32_t per_image, int32_t batch, int32_t count,
+                                   int32_t plane_slots, int32_t num_classes, int32_t mask_height, int32_t mask_width, float* grad_p,
+                                   mrcnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ from . import losses  # noqa: F401  (the training losses on the targets' padded 
 from . import layers  # noqa: F401  (the head layers' conv / transposed conv with a grad_fn)
 from . import optim  # noqa: F401  (ClippedSGD: gradient norm, clip and momentum step in three launches)
 from . import rpn_train  # noqa: F401  (TrainableRPN: a dense pass without a graph, forward and backward on the sampled anchors)
+from . import head_train  # noqa: F401  (TrainableClassifier / TrainableMask / TrainableHeads: the mask branch on the positives' class planes)
 
 
 class _RoiAlignNCHW(_torch.autograd.Function):
@@ -62,4 +63,4 @@ def roi_align(inputs, pool_size, image_shape):
     return ops.nhwc_to_nchw(pooled)
 
 
-__all__ = ["ops", "roi_align", "losses", "layers", "optim", "rpn_train"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)
+__all__ = ["ops", "roi_align", "losses", "layers", "optim", "rpn_train", "head_train"]   # reference-signature refine stages: maskrcnn_amd.refine (imports the pipeline)

@@ -57,6 +57,7 @@ SOURCES = {
     "losses.hip": ["-ffp-contract=off"],     # the five training losses: every term and derivative in fp64, operation by operation
     "optim.hip": ["-ffp-contract=off"],      # clipped SGD: g*g + acc, c*g + wd*p, momentum*b + d, p - lr*B, each rounded on its own in fp64
     "rpn_train.hip": ["-ffp-contract=off"],  # the patch scatter's running sum: plain fp32 adds in slot order
+    "mask_train.hip": ["-ffp-contract=off"],   # the class-plane conv: g = dy * (y * (1 - y)) in fp32 and the fp64 sums, operation by operation
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-fast-math",
           "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

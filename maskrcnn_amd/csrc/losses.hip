@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "loss_math.hpp"
 #include "workgroup.hpp"
 
 #pragma clang fp contract(off)
@@ -40,10 +41,7 @@ __device__ __forceinline__ float4 box_grads(float4 p, float4 t, double scale) {
                        (float)(scale * smooth_l1_grad((double)p.z - (double)t.z)), (float)(scale * smooth_l1_grad((double)p.w - (double)t.w)));
 }
 
-// log(1 - p) as torch takes it, log1p(-p): the same number wherever 1 - p is exact in fp64 (every fp32 p >= 2^-29, and 0)
-__device__ __forceinline__ double bce(double p, double y) { return -(y * fmax(log(p), -100.0) + (1.0 - y) * fmax(log1p(-p), -100.0)); }
-
-__device__ __forceinline__ double bce_grad(double p, double y) { return (p - y) / fmax((1.0 - p) * p, 1e-12); }
+using mrcnn::bce_grad;   // binary cross entropy, its derivative and a slot's sum: loss_math.hpp, shared with mask_train.hip
 
 // cross entropy over the RPN's two logits with class c: log(sum exp(x - max)) - (x[c] - max)
 __device__ __forceinline__ double ce2(float2 x, int c) {
@@ -51,23 +49,11 @@ __device__ __forceinline__ double ce2(float2 x, int c) {
     return log(exp(x0 - m) + exp(x1 - m)) - ((c ? x1 : x0) - m);
 }
 
-// gradient scale of one loss: upstream gradient / count, 0 for a loss without a contributing element
-__device__ __forceinline__ double grad_scale(float upstream, long long n) { return n > 0 ? (double)upstream / (double)n : 0.0; }
-
-// the count a gradient is divided by: the image's own (per_image) or the batch's, summed here from counts[batch][kLosses]
+// the scale of each loss's gradient for image b: loss_math.hpp's, at this file's workgroup size
 template <int kLosses>
 __device__ __forceinline__ void loss_scales(const int32_t* counts, const float* grad_out, int per_image, int batch, int b, long long* red,
                                             double* scale) {
-#pragma unroll
-    for (int k = 0; k < kLosses; ++k) {
-        if (per_image) {
-            scale[k] = grad_scale(grad_out[(int64_t)b * kLosses + k], counts[(int64_t)b * kLosses + k]);
-        } else {
-            long long n = 0;
-            for (int i = (int)threadIdx.x; i < batch; i += kBlock) n += counts[(int64_t)i * kLosses + k];
-            scale[k] = grad_scale(grad_out[k], mrcnn::block_sum<kBlock>(n, red));
-        }
-    }
+    mrcnn::loss_scales<kLosses, kBlock>(counts, grad_out, per_image, batch, b, red, scale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -313,9 +299,7 @@ __global__ __launch_bounds__(kBlock) void head_loss_slot_kernel(HeadParams p, do
                             *reinterpret_cast<const float4*>(p.target_deltas + 4 * t.index));
         const float* pm = p.pred_masks + plane * p.hw;
         const float* tm = p.target_mask + t.index * p.hw;
-        double acc = 0.0;
-        for (int i = tid; i < p.hw; i += kBlock) acc += bce((double)pm[i], (double)tm[i]);
-        mask = mrcnn::block_sum<kBlock>(acc, s_dred);
+        mask = mrcnn::bce_slot_sum<kBlock>(pm, tm, p.hw, s_dred);   // nothing is read when there is no mask tensor: hw is 0
     }
     if (tid == 0) {
         part[3 * t.index] = ce;
@@ -508,11 +492,13 @@ int head_params(const char* who, HeadParams& p, const int32_t* ids, const int32_
                 const float* logits, const float* pred_bbox, const float* pred_masks, int32_t batch, int32_t count, int32_t classes, int32_t mh,
                 int32_t mw) {
     if (int rc = check_head(who, batch, count, classes, mh, mw)) return rc;
-    MRCNN_REQUIRE(ids && num_rois && target_deltas && target_mask && logits && pred_bbox && pred_masks, "%s: null pointer", who);
+    MRCNN_REQUIRE(ids && num_rois && target_deltas && logits && pred_bbox, "%s: null pointer", who);
+    MRCNN_REQUIRE((target_mask != nullptr) == (pred_masks != nullptr), "%s: null pointer (target_mask and pred_masks are given together or both null)", who);
     MRCNN_REQUIRE(aligned(target_deltas, 16) && aligned(pred_bbox, 16), "%s: target_deltas and pred_bbox must be 16-byte aligned", who);
     p.ids = ids; p.num_rois = num_rois; p.target_deltas = target_deltas; p.target_mask = target_mask; p.logits = logits;
     p.pred_bbox = pred_bbox; p.pred_masks = pred_masks;
-    p.batch = batch; p.count = count; p.classes = classes; p.hw = mh * mw;
+    p.batch = batch; p.count = count; p.classes = classes;
+    p.hw = pred_masks ? mh * mw : 0;   // without the mask tensors: no mask term is read, the mask sum and count are 0, no gradient is written
     return MRCNN_OK;
 }
 }  // namespace
@@ -549,7 +535,8 @@ extern "C" int mrcnn_head_loss_backward(const int32_t* target_class_ids, const i
     if (int rc = head_params(who, q.in, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks, batch, count,
                              num_classes, mask_height, mask_width))
         return rc;
-    MRCNN_REQUIRE(counts && grad_out && grad_logits && grad_bbox && grad_masks, "%s: null pointer", who);
+    MRCNN_REQUIRE(counts && grad_out && grad_logits && grad_bbox, "%s: null pointer", who);
+    MRCNN_REQUIRE((grad_masks != nullptr) == (pred_masks != nullptr), "%s: null pointer (grad_masks is given with pred_masks and null without)", who);
     MRCNN_REQUIRE(aligned(grad_bbox, 16) && aligned(grad_masks, 4), "%s: grad_bbox must be 16-byte aligned", who);
     q.counts = counts; q.grad_out = grad_out; q.grad_logits = grad_logits; q.grad_bbox = grad_bbox; q.grad_masks = grad_masks;
     q.per_image = per_image != 0;

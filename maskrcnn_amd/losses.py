@@ -28,8 +28,8 @@ import torch
 
 from .targets import DetectionTargets
 
-__all__ = ["rpn_losses", "head_losses", "RpnLosses", "HeadLosses", "rpn_terms_numpy", "head_terms_numpy", "rpn_losses_numpy",
-           "head_losses_numpy", "reduce_numpy", "MAX_CLASSES"]
+__all__ = ["rpn_losses", "head_losses", "classifier_losses", "RpnLosses", "HeadLosses", "rpn_terms_numpy", "head_terms_numpy",
+           "classifier_terms_numpy", "rpn_losses_numpy", "head_losses_numpy", "reduce_numpy", "MAX_CLASSES"]
 
 MAX_CLASSES = 4096
 REDUCTIONS = ("mean", "per_image")
@@ -107,6 +107,15 @@ def head_terms_numpy(target_class_ids, num_rois, target_deltas, target_mask, log
     sums = np.array([ce.sum(), box.sum(), mask.reshape(len(pos), tm.shape[1] * tm.shape[2]).sum(axis=1).sum()])
     counts = np.array([len(use), 4 * len(pos), len(pos) * tm.shape[1] * tm.shape[2]], np.int64)
     return sums, counts, 2 * int(bad.any()), d_logits, d_bbox, d_masks
+
+
+def classifier_terms_numpy(target_class_ids, num_rois, target_deltas, logits, pred_bbox):
+    """head_terms_numpy without the mask tensors → (sums float64 [2], counts int64 [2], status, d_logits, d_bbox): its class and box
+    columns, computed by the same statements."""
+    count, classes = np.asarray(logits).shape
+    sums, counts, status, d_logits, d_bbox, _ = head_terms_numpy(target_class_ids, num_rois, target_deltas, np.zeros((count, 1, 1), np.float32),
+                                                                 logits, pred_bbox, np.full((count, classes, 1, 1), 0.5, np.float32))
+    return sums[:2], counts[:2], status, d_logits, d_bbox
 
 
 def reduce_numpy(sums, counts, reduction: str = "mean"):
@@ -316,3 +325,42 @@ def head_losses(target_class_ids, num_rois, target_deltas, target_mask, class_lo
     else:
         losses, status = _HeadLoss.apply(logits, pbox, pmask, ids, num_rois, deltas, mask, per_image)
     return HeadLosses(losses[..., 0], losses[..., 1], losses[..., 2], status)
+
+
+def classifier_losses(target_class_ids, num_rois, target_deltas=None, class_logits=None, pred_bbox=None, reduction: str = "mean",
+                      device=None):
+    """Classifier.class_loss and Classifier.boxes_loss for a batch, without a mask tensor → (class_loss, bbox_loss, status): the
+    first two losses of head_losses and its status, bit for bit, gradients included (on the device the same two launches with null
+    mask pointers, on the CPU the same numpy statements). Also classifier_losses(t, class_logits, pred_bbox, ...) with t a
+    targets.DetectionTargets. Shapes, reduction and device as for head_losses; the predictions may be flat over the slots."""
+    who = "classifier_losses"
+    if isinstance(target_class_ids, DetectionTargets):
+        if class_logits is not None or pred_bbox is not None:
+            raise ValueError(f"{who}: with a DetectionTargets pass class_logits and pred_bbox right after it")
+        t, class_logits, pred_bbox = target_class_ids, num_rois, target_deltas
+        target_class_ids, num_rois, target_deltas = t.target_class_ids, t.num_pos + t.num_neg, t.target_deltas
+    if target_deltas is None or class_logits is None or pred_bbox is None:
+        raise ValueError(f"{who}: target_deltas, class_logits and pred_bbox are required")
+    per_image = _check_reduction(who, reduction)
+    dev = _device_of(device, class_logits, pred_bbox)
+    ids, num_rois = _tensor(target_class_ids, dev), _tensor(num_rois, dev)
+    deltas, logits, pbox = (_tensor(v, dev, torch.float32) for v in (target_deltas, class_logits, pred_bbox))
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64) or ids.size(0) < 1 or not 1 <= ids.size(1) <= 1024:
+        raise ValueError(f"{who}: target_class_ids must be int32 or int64 [B,count] with count in [1, 1024], got {ids.dtype} {tuple(ids.shape)}")
+    b, count = ids.shape
+    if tuple(num_rois.shape) != (b,) or tuple(deltas.shape) != (b, count, 4):
+        raise ValueError(f"{who}: num_rois must be [{b}] and target_deltas [{b},{count},4], got {tuple(num_rois.shape)} and {tuple(deltas.shape)}")
+    if logits.dim() < 2 or logits.numel() % (b * count) or not 2 <= logits.size(-1) <= MAX_CLASSES:
+        raise ValueError(f"{who}: class_logits must be [{b},{count},C] or [{b * count},C] with C in [2, {MAX_CLASSES}], got {tuple(logits.shape)}")
+    c = logits.size(-1)
+    want = ((b, count, c), (b, count, c, 4))
+    for name, v, shape in zip(("class_logits", "pred_bbox"), (logits, pbox), want):
+        if tuple(v.shape) not in (shape, (b * count, *shape[2:])):
+            raise ValueError(f"{who}: {name} must be {list(shape)} or {[b * count, *shape[2:]]}, got {tuple(v.shape)}")
+    logits, pbox = (v.reshape(shape) for v, shape in zip((logits, pbox), want))
+    ids, num_rois = ids.to(torch.int32), num_rois.to(torch.int32)
+    if dev.type == "cpu":
+        losses, status = _NumpyLoss.apply(classifier_terms_numpy, per_image, 2, logits, pbox, ids, num_rois, deltas)
+    else:
+        losses, status = _HeadLoss.apply(logits, pbox, None, ids, num_rois, deltas, None, per_image)
+    return losses[..., 0], losses[..., 1], status

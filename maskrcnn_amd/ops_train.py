@@ -2,7 +2,8 @@
 losses, forward and backward (csrc/losses.hip), the backward of the pyramid RoIAlign (csrc/roi_align_backward.hip), the backward
 of the conv + frozen affine + activation at stride 1 or 2 (csrc/conv_backward.hip) and the backbone's two other gradients, the
 dilation of a compact stride-2 gradient and the max-pool backward (csrc/pool_backward.hip), clipped SGD (csrc/optim.hip) and the
-RPN's training branch on the sampled anchors: compaction, patch gather and patch scatter (csrc/rpn_train.hip). ops.py re-exports every name here;
+RPN's training branch on the sampled anchors: compaction, patch gather and patch scatter (csrc/rpn_train.hip), and the mask head's
+class-plane branch: the 1x1 conv to each slot's own class and the mask loss on those planes (csrc/mask_train.hip). ops.py re-exports every name here;
 argument checks and registration are _binding.py's."""
 from __future__ import annotations
 
@@ -250,16 +251,19 @@ def rpn_loss_backward(match: torch.Tensor, logits: torch.Tensor, pred_bbox: torc
 
 
 def _head_loss_inputs(who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks):
-    """The seven tensors both head loss ops read, on 16-byte boundaries, and B, count, C, mh, mw."""
+    """The seven tensors both head loss ops read, on 16-byte boundaries, and B, count, C, mh, mw. target_mask and pred_masks both
+    None: the classifier alone (the library takes null pointers for them; mh = mw = 1 stand in)."""
     ids = checked(who, "target_class_ids", target_class_ids, _I32, (("B", 1), ("count", 1)), align16=True)
     b, count = ids.shape
-    target_mask = checked(who, "target_mask", target_mask, _F32, (b, count, "mh", "mw"), align16=True)
+    no_masks = target_mask is None and pred_masks is None
+    if not no_masks:
+        target_mask = checked(who, "target_mask", target_mask, _F32, (b, count, "mh", "mw"), align16=True)
     logits = checked(who, "logits", logits, _F32, (b, count, ("C", 1)), align16=True)
-    c, mh, mw = logits.size(2), target_mask.size(2), target_mask.size(3)
+    c, mh, mw = logits.size(2), (1 if no_masks else target_mask.size(2)), (1 if no_masks else target_mask.size(3))
     return (ids, checked(who, "num_rois", num_rois, _I32, (b,), align16=True),
             checked(who, "target_deltas", target_deltas, _F32, (b, count, 4), align16=True), target_mask, logits,
             checked(who, "pred_bbox", pred_bbox, _F32, (b, count, c, 4), align16=True),
-            checked(who, "pred_masks", pred_masks, _F32, (b, count, c, mh, mw), align16=True), b, count, c, mh, mw)
+            None if no_masks else checked(who, "pred_masks", pred_masks, _F32, (b, count, c, mh, mw), align16=True), b, count, c, mh, mw)
 
 
 @_on_device
@@ -270,7 +274,8 @@ def head_loss(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_del
     num_rois int32 [B] (num_pos + num_neg: the slots past it never contribute), target_deltas float32 [B,count,4], target_mask
     float32 [B,count,mh,mw], logits float32 [B,count,C], pred_bbox float32 [B,count,C,4], pred_masks float32 [B,count,C,mh,mw] →
     (sums float64 [B,3]: class, box, mask; counts int32 [B,3]: the slots, 4 x the positive slots, mh x mw x the positive slots;
-    status int32 [B]: bit 1 = a class id outside 0 .. C-1, whose slot is skipped). Two launches, no host synchronisation."""
+    status int32 [B]: bit 1 = a class id outside 0 .. C-1, whose slot is skipped). target_mask and pred_masks both None: the classifier
+    alone — the mask sum and count are 0, the other columns and their bits unchanged. Two launches, no host synchronisation."""
     who = "head_loss"
     ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
         who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
@@ -281,8 +286,8 @@ def head_loss(target_class_ids: torch.Tensor, num_rois: torch.Tensor, target_del
     nbytes = int(lib.mrcnn_head_loss_workspace_bytes(b, count))
     ws = workspace(nbytes, dev)
     _launch(lib.mrcnn_head_loss_forward,
-            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
-             pred_masks.data_ptr(), b, count, c, mh, mw, sums.data_ptr(), counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), _ptr(mask), logits.data_ptr(), pred_bbox.data_ptr(),
+             _ptr(pred_masks), b, count, c, mh, mw, sums.data_ptr(), counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
              _stream()),
             lambda: (0, (b, count, c), 4 * b * count * (c + 2 * mh * mw + 10), "head_loss"))
     return sums, counts, status
@@ -294,17 +299,18 @@ def head_loss_backward(target_class_ids: torch.Tensor, num_rois: torch.Tensor, t
                        grad_out: torch.Tensor):
     """The gradients of head_loss's three losses → (grad_logits, grad_bbox, grad_masks) in the predictions' shapes, every element
     written: zeros but the contributing slots' logits rows, their class's box row and their class's mask plane. counts as
-    head_loss returned them; grad_out float32 [3] (batch mean) or [B,3] (per image), as for rpn_loss_backward. One launch, no host
-    synchronisation."""
+    head_loss returned them; grad_out float32 [3] (batch mean) or [B,3] (per image), as for rpn_loss_backward. Without the mask
+    tensors (both None) grad_masks is None. One launch, no host synchronisation."""
     who = "head_loss_backward"
     ids, num_rois, deltas, mask, logits, pred_bbox, pred_masks, b, count, c, mh, mw = _head_loss_inputs(
         who, target_class_ids, num_rois, target_deltas, target_mask, logits, pred_bbox, pred_masks)
     grad_out, counts, per_image = _loss_grad_out(who, grad_out, counts, 3)
-    grad_logits, grad_bbox, grad_masks = torch.empty_like(logits), torch.empty_like(pred_bbox), torch.empty_like(pred_masks)
+    grad_logits, grad_bbox = torch.empty_like(logits), torch.empty_like(pred_bbox)
+    grad_masks = None if pred_masks is None else torch.empty_like(pred_masks)
     _launch(lib.mrcnn_head_loss_backward,
-            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), mask.data_ptr(), logits.data_ptr(), pred_bbox.data_ptr(),
-             pred_masks.data_ptr(), counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, count, c, mh, mw,
-             grad_logits.data_ptr(), grad_bbox.data_ptr(), grad_masks.data_ptr(), _stream()),
+            (ids.data_ptr(), num_rois.data_ptr(), deltas.data_ptr(), _ptr(mask), logits.data_ptr(), pred_bbox.data_ptr(),
+             _ptr(pred_masks), counts.data_ptr(), grad_out.data_ptr(), int(per_image), b, count, c, mh, mw,
+             grad_logits.data_ptr(), grad_bbox.data_ptr(), _ptr(grad_masks), _stream()),
             lambda: (0, (b, count, c), 4 * b * count * c * (mh * mw + 5), "head_loss_backward"))
     return grad_logits, grad_bbox, grad_masks
 
@@ -833,3 +839,166 @@ def pyramid_patch_scatter(dpatch: torch.Tensor, index: torch.Tensor, num: torch.
 
 # anchor_compact, pyramid_patch_gather and pyramid_patch_scatter have no torch.ops.maskrcnn schema and are not in ops.__all__
 # either, for the same reason. The differentiable front end is maskrcnn_amd.rpn_train (pyramid_patches, TrainableRPN).
+
+
+# --------------------------------------------------------------------------------------------------
+# The mask head's class-plane branch in training (csrc/mask_train.hip)
+# --------------------------------------------------------------------------------------------------
+_MAX_CLASSES, _MAX_MASK_SIDE, _MAX_CIN = 4096, 64, 4096
+
+
+def _plane_targets(who, ids, num, slots, classes=None):
+    """target_class_ids int32 [B,count] and num int32 [B] of a class-plane op, with B, count and the checked P and C."""
+    ids = checked(who, "ids", ids, _I32, (("B", 1), ("count", 1)))
+    b, count = ids.shape
+    if b > _MAX_IMAGES or count > _MAX_CAPACITY:
+        refuse(who, "ids", f"int32 [B,count] with B in 1 .. {_MAX_IMAGES} and count in 1 .. {_MAX_CAPACITY}", ids)
+    num = checked(who, "num", num, _I32, (b,))
+    if type(slots) is not int or not 1 <= slots <= count:
+        refuse(who, "plane slots P", f"in 1 .. count = {count}", slots)
+    if classes is not None:
+        _int_in(who, "num_classes", classes, 2, _MAX_CLASSES)
+    return ids, num, b, count
+
+
+def _plane_act(who, act) -> int:
+    if type(act) is not int or act not in (0, 2):
+        refuse(who, "act", "0 (none) or 2 (sigmoid)", act)
+    return act
+
+
+def _plane_x(who, name, x, optional=False):
+    """x (or dx) float32 [S,mh,mw,Cin] of a class-plane op → (x, mh, mw, Cin)."""
+    x = checked(who, name, x, _F32, (("S", 1), ("mh", 1), ("mw", 1), ("Cin", 4)), align16=True, optional=optional)
+    if x is None:
+        return None, 0, 0, 0
+    _, mh, mw, cin = x.shape
+    if cin % 4 or cin > _MAX_CIN or mh > _MAX_MASK_SIDE or mw > _MAX_MASK_SIDE:
+        refuse(who, name, f"float32 [S,mh,mw,Cin] with mh, mw in 1 .. {_MAX_MASK_SIDE} and Cin a multiple of 4 in 4 .. {_MAX_CIN}", x)
+    return x, mh, mw, cin
+
+
+@_on_device
+def class_plane_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, ids: torch.Tensor, num: torch.Tensor, act: int = 0,
+                     out: torch.Tensor | None = None):
+    """The 1x1 conv to each slot's OWN class; the rule is stated at mrcnn_class_plane_conv_f32 in include/maskrcnn_hip.h. x float32
+    [B*P,mh,mw,Cin] (NHWC: the first P slots of each image), w float32 [C,Cin], bias float32 [C] or None, ids int32 [B,count]
+    (target_class_ids, read in place), num int32 [B] → (y float32 [B*P,mh,mw], status int32 [B]). Slot (b, s) is active when
+    s < min(num[b], P) and 0 < ids[b,s] < C: y = act(bias[k] + x . w[k]) with the dot product in fp64, act 0 none / 2 sigmoid. A slot
+    that is not active: +0, and its x rows are never read. status bit 1: a class id outside 0 .. C-1 below num[b]; bit 2: a positive at
+    or past P. Every byte of y is written. One launch, no host synchronisation."""
+    who = "class_plane_conv"
+    act = _plane_act(who, act)
+    x, mh, mw, cin = _plane_x(who, "x", x)
+    w = checked(who, "w", w, _F32, (("C", 2), cin), align16=True)
+    c = w.size(0)
+    bias = checked(who, "bias", bias, _F32, (c,), optional=True)
+    s = x.size(0)
+    b = ids.size(0) if isinstance(ids, torch.Tensor) and ids.dim() == 2 and ids.size(0) else 1
+    ids, num, b, count = _plane_targets(who, ids, num, s // b if s % b == 0 else 0, c)
+    out = checked_out(who, "out", out, _F32, (s, mh, mw), x.device)
+    status = torch.empty(b, dtype=_I32, device=x.device)
+    _launch(lib.mrcnn_class_plane_conv_f32,
+            (x.data_ptr(), w.data_ptr(), _ptr(bias), ids.data_ptr(), num.data_ptr(), b, count, s // b, c, mh, mw, cin, act,
+             out.data_ptr(), status.data_ptr(), _stream()),
+            lambda: (2.0 * s * mh * mw * cin, (s * mh * mw, 1, cin), 4 * (x.numel() + out.numel()), "class_plane_conv"))
+    return out, status
+
+
+@_on_device
+def class_plane_conv_backward(dy: torch.Tensor, y: torch.Tensor | None, x: torch.Tensor, w: torch.Tensor, ids: torch.Tensor,
+                              num: torch.Tensor, act: int = 0, needs=(True, True, True), out=None):
+    """The gradients of class_plane_conv; the rule is stated at mrcnn_class_plane_conv_backward_f32 in include/maskrcnn_hip.h. dy and
+    y float32 [B*P,mh,mw] (y is read at act 2 only and may be None at act 0), x, w, ids, num and act as the forward took them;
+    needs = (dx, dw, dbias) → (dx float32 [B*P,mh,mw,Cin], dw float32 [C,Cin], dbias float32 [C]), None where not needed. dx is one
+    fp32 product g * w[k]; dw and dbias are fp64 sums in a fixed order (the pixels of a slot, then the slots of a class in ascending
+    (b, s)), narrowed last. Every byte of every returned tensor is written, +0 for a slot that is not active and for a class without
+    one; two calls give the same bits. out: the three tensors to write into (an entry that is not needed is ignored). Two launches (one
+    for dx alone), no floating-point atomic, no host synchronisation."""
+    who = "class_plane_conv_backward"
+    act = _plane_act(who, act)
+    if len(needs) != 3:
+        raise RuntimeError(f"{who}: needs must hold 3 flags (dx, dw, dbias), got {len(needs)}")
+    if out is not None and len(out) != 3:
+        raise RuntimeError(f"{who}: out must hold 3 tensors (dx, dw, dbias), got {len(out)}")
+    need_dx, need_dw, need_db = [bool(v) for v in needs]
+    x, mh, mw, cin = _plane_x(who, "x", x)
+    s, dev = x.size(0), x.device
+    w = checked(who, "w", w, _F32, (("C", 2), cin), align16=True)
+    c = w.size(0)
+    dy = checked(who, "dy", dy, _F32, (s, mh, mw))
+    y = checked(who, "y", y, _F32, (s, mh, mw), optional=act == 0)
+    b = ids.size(0) if isinstance(ids, torch.Tensor) and ids.dim() == 2 and ids.size(0) else 1
+    ids, num, b, count = _plane_targets(who, ids, num, s // b if s % b == 0 else 0, c)
+    given = out or (None, None, None)
+    dx = checked_out(who, "dx", given[0], _F32, (s, mh, mw, cin), dev) if need_dx else None
+    dw = checked_out(who, "dw", given[1], _F32, (c, cin), dev) if need_dw else None
+    db = checked_out(who, "dbias", given[2], _F32, (c,), dev) if need_db else None
+    if dx is not None and dx.data_ptr() % 16:
+        refuse(who, "dx", "on a 16-byte boundary", dx)
+    nbytes = int(lib.mrcnn_class_plane_conv_backward_workspace_bytes(b, s // b, mh, mw, cin)) if need_dw or need_db else 0
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_class_plane_conv_backward_f32,
+            (dy.data_ptr(), _ptr(y), x.data_ptr(), w.data_ptr(), ids.data_ptr(), num.data_ptr(), b, count, s // b, c, mh, mw, cin, act,
+             _ptr(dx), _ptr(dw), _ptr(db), ws.data_ptr(), nbytes, _stream()),
+            lambda: (2.0 * s * mh * mw * cin * (need_dx + need_dw), (s * mh * mw, 1, cin),
+                     4 * x.numel() * (need_dx + need_dw) + 2 * nbytes, "class_plane_conv_backward"))
+    return dx, dw, db
+
+
+def _plane_loss_inputs(who, p, target_mask, ids, num):
+    p = checked(who, "p", p, _F32, (("B", 1), ("P", 1), ("mh", 1), ("mw", 1)))
+    b, slots, mh, mw = p.shape
+    if mh > _MAX_MASK_SIDE or mw > _MAX_MASK_SIDE:
+        refuse(who, "p", f"float32 [B,P,mh,mw] with mh, mw in 1 .. {_MAX_MASK_SIDE}", p)
+    ids = checked(who, "ids", ids, _I32, (b, ("count", 1)))
+    ids, num, b, count = _plane_targets(who, ids, num, slots)
+    return p, checked(who, "target_mask", target_mask, _F32, (b, count, mh, mw)), ids, num, b, count, slots, mh, mw
+
+
+@_on_device
+def mask_plane_loss(p: torch.Tensor, target_mask: torch.Tensor, ids: torch.Tensor, num: torch.Tensor, num_classes: int):
+    """Mask.mask_loss (model.py:922-953) on class planes; the rule is stated at mrcnn_mask_plane_loss_forward in
+    include/maskrcnn_hip.h. p float32 [B,P,mh,mw] (class_plane_conv's sigmoid output), target_mask float32 [B,count,mh,mw], ids int32
+    [B,count] and num int32 [B] read in place, num_classes = C → (sums float64 [B], counts int32 [B] = mh * mw x the active slots,
+    status int32 [B] as class_plane_conv's). The per-element term and the order of a slot's sum are ops.head_loss's: the sums equal its
+    mask column on the dense tensor bit for bit. Two launches, no host synchronisation."""
+    who = "mask_plane_loss"
+    p, target_mask, ids, num, b, count, slots, mh, mw = _plane_loss_inputs(who, p, target_mask, ids, num)
+    c = _int_in(who, "num_classes", num_classes, 2, _MAX_CLASSES)
+    dev = p.device
+    sums = torch.empty(b, dtype=torch.float64, device=dev)
+    counts = torch.empty(b, dtype=_I32, device=dev)
+    status = torch.empty(b, dtype=_I32, device=dev)
+    nbytes = int(lib.mrcnn_mask_plane_loss_workspace_bytes(b, slots))
+    ws = workspace(nbytes, dev)
+    _launch(lib.mrcnn_mask_plane_loss_forward,
+            (p.data_ptr(), target_mask.data_ptr(), ids.data_ptr(), num.data_ptr(), b, count, slots, c, mh, mw, sums.data_ptr(),
+             counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            lambda: (0, (b, slots, mh * mw), 8 * p.numel(), "mask_plane_loss"))
+    return sums, counts, status
+
+
+@_on_device
+def mask_plane_loss_backward(p: torch.Tensor, target_mask: torch.Tensor, ids: torch.Tensor, num: torch.Tensor, num_classes: int,
+                             counts: torch.Tensor, grad_out: torch.Tensor, per_image: bool = False,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+    """The gradient of mask_plane_loss's loss → grad_p float32 [B,P,mh,mw], every byte written, +0 for a slot that is not active.
+    counts as mask_plane_loss returned them; grad_out float32 [1] (the upstream gradient of the batch's sum / the batch's count) or,
+    with per_image, [B] (of each image's own sum / count), both read on the device. One launch, no host synchronisation."""
+    who = "mask_plane_loss_backward"
+    p, target_mask, ids, num, b, count, slots, mh, mw = _plane_loss_inputs(who, p, target_mask, ids, num)
+    c = _int_in(who, "num_classes", num_classes, 2, _MAX_CLASSES)
+    counts = checked(who, "counts", counts, _I32, (b,), hint=" as the forward returned them")
+    per_image = bool(per_image)
+    grad_out = checked(who, "grad_out", grad_out, _F32, (b,) if per_image else (1,))
+    out = checked_out(who, "out", out, _F32, (b, slots, mh, mw), p.device)
+    _launch(lib.mrcnn_mask_plane_loss_backward,
+            (p.data_ptr(), target_mask.data_ptr(), ids.data_ptr(), num.data_ptr(), counts.data_ptr(), grad_out.data_ptr(), int(per_image),
+             b, count, slots, c, mh, mw, out.data_ptr(), _stream()),
+            lambda: (0, (b, slots, mh * mw), 12 * p.numel(), "mask_plane_loss_backward"))
+    return out
+
+
+# class_plane_conv, class_plane_conv_backward, mask_plane_loss and mask_plane_loss_backward have no torch.ops.maskrcnn schema and are
+# not in ops.__all__ either, for the same reason. The differentiable front end is maskrcnn_amd.head_train.
