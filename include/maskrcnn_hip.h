@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 34
+#define MRCNN_ABI_VERSION 35
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -477,14 +477,16 @@ int32_t mrcnn_conv_route(int32_t batch, int32_t height, int32_t width, int32_t c
 int mrcnn_nhwc_to_kblocked_f32(const float* x, int64_t pixels, int32_t channels, float* y, mrcnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Backward of the stride-1 fp32 NHWC convolution with a FROZEN affine and an activation — the layers train_model(layers="heads")
- * trains (model.py:1010-1016, :1218: fpn.P*, rpn.*, classifier.*, mask.*, BatchNorm in eval mode): gradients for the input, the
- * weight, the shift and the residual. No gradient of `scale` is produced: BatchNorm is frozen in that stage, and its statistics
- * are not this library's business. The reference has no kernel for any of this (autograd of nn.Conv2d / BatchNorm2d / ReLU).
+ * Backward of the fp32 NHWC convolution with a FROZEN affine and an activation, at stride 1 — the layers train_model(layers="heads")
+ * trains (model.py:1010-1016, :1218: fpn.P*, rpn.*, classifier.*, mask.*, BatchNorm in eval mode) — or 2 (the backbone's strided
+ * convs, next block): gradients for the input, the weight, the shift and the residual. No gradient of `scale` is produced: BatchNorm
+ * is frozen in every schedule, and its statistics are not this library's business. The reference has no kernel for any of this (autograd of nn.Conv2d / BatchNorm2d / ReLU).
  *
- * The forward is  pre = scale[co] * conv(x, w) + shift[co] (+ residual),  y = act(pre),  stride 1, pads (pt, pl, pb, pr),
+ * The forward is  pre = scale[co] * conv(x, w) + shift[co] (+ residual),  y = act(pre),  stride s, pads (pt, pl, pb, pr),
  * x [B][H][W][Cin], w [Cout][KH][KW][Cin], y [B][OH][OW][Cout]  (mrcnn_conv_bn_act_nhwc_f32). Given dy of y's shape:
  *
+ *   stride  s = 1 or 2; OH = (H + pt + pb - KH) / s + 1, OW likewise, a remainder is legal (a 1 x 1 kernel on odd H uses the last
+ *           row). mrcnn_conv_act_backward_f32 has no stride: it works on the output map.
  *   g       the gradient of pre; every operation a separately rounded fp32 operation:
  *             activation 0   g = dy          1 (ReLU)   g = y > 0 ? dy : 0          2 (sigmoid)   t = 1 - y; u = y * t; g = dy * u
  *           g is the residual's gradient at res_div = 1; at res_div = 2 (the FPN's nearest-upsample add) the residual's gradient
@@ -495,21 +497,26 @@ int mrcnn_nhwc_to_kblocked_f32(const float* x, int64_t pixels, int32_t channels,
  *   dshift  [co] = the sum of g over the contributing output pixels, accumulated in fp64 in a fixed order that depends on the
  *           shape only (a thread's pixels in ascending order, then the threads' partials in index order, in a second launch),
  *           narrowed to fp32 last. No atomic, no last-block protocol.
- *   dx      [b,iy,ix,ci] = sum over (ky,kx,co) of z[b, iy+pt-ky, ix+pl-kx, co] * w[co,ky,kx,ci]. It IS the forward:
+ *   dx      at stride 1 [b,iy,ix,ci] = sum over (ky,kx,co) of z[b, iy+pt-ky, ix+pl-kx, co] * w[co,ky,kx,ci]. It IS the forward:
  *           mrcnn_conv_bn_act_nhwc_f32 on z as the input [B][OH][OW][Cout4] with the weight
  *           w'[ci][ky'][kx'][co] = w[co][KH-1-ky'][KW-1-kx'][ci] (co >= Cout: zero), pads (KH-1-pt, KW-1-pl, KH-1-pb, KW-1-pr), no
  *           affine, no residual, activation 0; a transform kernel writes w' into the workspace on every call (the weights change
  *           every step). dx equals that forward call on those operands bit for bit: it has the forward's routes and limits, and
  *           image i does not depend on the rest of the batch. A pad larger than K - 1 is refused.
- *   dw      [co,ky,kx,ci] = sum over (b,oy,ox) of z[b,oy,ox,co] * x[b, oy+ky-pt, ox+kx-pl, ci], taps outside the image contributing
- *           nothing. The pixel axis M = B*OH*OW is cut into chunks of L = mrcnn_conv_backward_weights_chunk(...) pixels — a function
- *           of the shape only, chosen as for a 256-CU part, so the bits do not depend on the device. Inside a chunk an element is
- *           an fp32 fmaf chain over the chunk's pixels in ascending order (v_mfma_f32_32x32x2_f32); a second launch adds the
- *           ceil(M / L) chunks' sums in ascending chunk order in fp64 and narrows last. Two calls give the same bits.
+ *           At stride 2 for the 1 x 1 kernel without padding only (every strided conv of the model whose input needs a gradient):
+ *           dx is then the COMPACT gradient dxc [B][OH][OW][Cin], dxc[b,i,j,ci] = sum over co of z[b,i,j,co] * w[co,0,0,ci] — the
+ *           same forward call, with w'[ci][co] = w[co][ci] a plain GEMM, bit for bit; mrcnn_dilate2_sum_f32 (below) writes the full
+ *           gradient from it.
+ *   dw      [co,ky,kx,ci] = sum over (b,oy,ox) of z[b,oy,ox,co] * x[b, oy*s+ky-pt, ox*s+kx-pl, ci], taps outside the image
+ *           contributing nothing; any kernel size at either stride. The pixel axis M = B*OH*OW is cut into chunks of
+ *           L = mrcnn_conv_backward_weights_chunk(...) pixels — a function of the shape only, chosen as for a 256-CU part, so the
+ *           bits do not depend on the device; it depends on the stride through M = B*OH*OW. Inside a chunk an element is an fp32
+ *           fmaf chain over the chunk's pixels in ascending order (v_mfma_f32_32x32x2_f32); a second launch adds the ceil(M / L)
+ *           chunks' sums in ascending chunk order in fp64 and narrows last. Two calls give the same bits.
  *   rows    row_counts / rows_per_group as in mrcnn_conv_bn_act_rows_f32: an output row at or past its group's count contributes
  *           nothing to dw and dshift, its z and g rows are written as zero, and its rows of dy and y — and the x values of its taps
  *           in dw — are never read into the arithmetic (the forward leaves such rows unwritten: they may hold NaN). dx is then
- *           zero wherever only such rows land. Not with a residual or the scatter.
+ *           zero wherever only such rows land. Not with a residual or the scatter, and at stride 1 only.
  *   scatter (mrcnn_deconv2x2_bias_act_nhwc_f32): dy and y are [B][2*out_h][2*out_w][cout / 4]; GEMM column (dy*2+dx)*C + co of
  *           row (b,i,j) is pixel (2i+dy, 2j+dx). mrcnn_conv_act_backward_f32 gathers; after it z [M][cout] is an ordinary 1 x 1
  *           case and dshift is [cout] = [4*C] (the caller adds the four taps for the bias). Activation 0 or 1.
@@ -518,12 +525,12 @@ int mrcnn_nhwc_to_kblocked_f32(const float* x, int64_t pixels, int32_t channels,
  *   (not wanted). out_h, out_w, cout: the GEMM's row map and column count (with scatter: the deconv's input map and 4 * C).
  *   g fp32 [B][out_h][out_w][cout] (dense pitch, no scatter), dresidual2 fp32 [B][out_h/2][out_w/2][cout] (res_div = 2 only; out_h
  *   and out_w even). Two launches with dshift, one without, none when every output is NULL.
- * mrcnn_conv_backward_data_f32: z [B][OH][OW][Cout4] -> dx [B][H][W][Cin]. Two launches.
+ * mrcnn_conv_backward_data_f32: z [B][OH][OW][Cout4] -> dx [B][H][W][Cin] (stride 2: [B][OH][OW][Cin]). Two launches.
  * mrcnn_conv_backward_weights_f32: x, z -> dw [Cout][KH][KW][Cin]. Two launches.
  * workspace: >= mrcnn_conv_backward_workspace_bytes(...) bytes of device memory, 16-byte aligned, shared by the three calls of a
  *   layer on one stream (the larger of: the dshift partials, w', ceil(M / L) * Cout * KH*KW*Cin floats of chunk sums, which are
  *   addressed with 64-bit offsets). The library allocates nothing and never synchronises; the launch counts do not depend on B.
- * Limits: stride 1, fp32, NHWC, Cin % 4 == 0, Cout >= 1, activation 0 / 1 / 2 in the forward's combinations, every tensor — z
+ * Limits: stride 1 or 2, fp32, NHWC, Cin % 4 == 0, Cout >= 1, activation 0 / 1 / 2 in the forward's combinations, every tensor — z
  *   included — within the forward's 32-bit byte offsets (<= 0xFFFFFFF0 bytes). Outside them: an error before any launch.
  *   mrcnn_conv_backward_weights_chunk and _workspace_bytes return 0 for arguments the entry points refuse.
  * ---------------------------------------------------------------------------------------------- */
@@ -532,35 +539,26 @@ int mrcnn_conv_act_backward_f32(const float* dy, const float* y, int32_t batch, 
                                 const int32_t* row_counts, int32_t rows_per_group, float* z, float* g, float* dresidual2,
                                 float* dshift, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
 int mrcnn_conv_backward_data_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* w,
-                                 int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                 int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+                                 int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                 int32_t pad_bottom, int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes,
+                                 mrcnn_stream_t stream);
 int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* z,
-                                    int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                    int32_t pad_right, const int32_t* row_counts, int32_t rows_per_group, float* dw,
-                                    void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+                                    int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                    int32_t pad_bottom, int32_t pad_right, const int32_t* row_counts, int32_t rows_per_group,
+                                    float* dw, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
 size_t mrcnn_conv_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
-                                           int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
+                                           int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                           int32_t pad_right);
 int32_t mrcnn_conv_backward_weights_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
-                                          int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right);
+                                          int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
+                                          int32_t pad_right);
 
 /* ------------------------------------------------------------------------------------------------
- * The backbone's backward: the conv backward above with a stride, and the two gradients that are not convolutions. With them every
+ * The backbone's backward: the conv backward above at stride 2, and the two gradients that are not convolutions. With them every
  * layer of the model has a backward (model.py:174-270: conv1 and downsample.0 of the first block of C3, C4 and C5 are 1 x 1 stride
  * 2; the stem is 7 x 7 stride 2 pad 3 on the image, then SamePad2d(3,2) + MaxPool2d(3,2); P6 = MaxPool2d(1,2) of P5). BatchNorm
- * stays frozen in every schedule, so there is still no gradient of `scale`. The four mrcnn_conv_*_f32 entry points above keep their
- * signatures and their stride-1 launches and bits; mrcnn_conv_act_backward_f32 has no stride (it works on the output map).
+ * stays frozen in every schedule, so there is still no gradient of `scale`.
  *
- *   stride  s = 1 or 2; OH = (H + pt + pb - KH) / s + 1, OW likewise, a remainder is legal (a 1 x 1 kernel on odd H uses the last
- *           row). z is [B][OH][OW][Cout4] as above.
- *   dw      [co,ky,kx,ci] = sum over (b,oy,ox) of z[b,oy,ox,co] * x[b, oy*s+ky-pt, ox*s+kx-pl, ci], taps outside the image
- *           contributing nothing; any kernel size the stride-1 path takes. The rule above carries over word for word: an element
- *           is an fp32 fmaf chain over a chunk's output pixels in ascending order, the chunks' sums are added in fp64 in ascending
- *           order and narrowed last, two calls give the same bits. The chunk length L = mrcnn_conv_backward_weights_strided_chunk(...)
- *           is a function of the shape only; it depends on the stride through M = B*OH*OW. No row counts at stride 2.
- *   dx      at stride 2 for the 1 x 1 kernel without padding only (every strided conv of the model whose input needs a gradient).
- *           mrcnn_conv_backward_data_strided_f32 writes the COMPACT gradient dxc [B][OH][OW][Cin], dxc[b,i,j,ci] = sum over co of
- *           z[b,i,j,co] * w[co,0,0,ci]: the forward mrcnn_conv_bn_act_nhwc_f32 on z with w'[ci][co] = w[co][ci], a plain GEMM, bit
- *           for bit. At stride 1 it is mrcnn_conv_backward_data_f32.
  *   dilate  mrcnn_dilate2_sum_f32 writes the full gradient from the compact one: dx[b,2i,2j,:] = a[b,i,j,:], or a + b2 as ONE fp32
  *           add where a second compact tensor is given (conv1 and downsample.0 of a strided block read the same x: the sum of
  *           their two full-size gradients is a + b2 at the even positions and 0 + 0 elsewhere, bit for bit), and +0 at every other
@@ -582,24 +580,9 @@ int32_t mrcnn_conv_backward_weights_chunk(int32_t batch, int32_t height, int32_t
  *             NaN      a NaN tap takes over whatever the maximum was (torch's `|| isnan(val)`), so the LAST NaN of a window in walk
  *                      order receives its gradient. A padding tap is never NaN. (A window of -inf alone keeps its first tap.)
  *           kernel 1 .. 3, stride 1 .. 2, every pad in 0 .. kernel - 1, C % 4 == 0, fp32 NHWC. One launch.
- * workspace: >= mrcnn_conv_backward_strided_workspace_bytes(...) bytes, 16-byte aligned, shared with mrcnn_conv_act_backward_f32 as
- *   above. The chunk and workspace queries return 0 for arguments the entry points refuse. Every tensor <= 0xFFFFFFF0 bytes and on
- *   a 16-byte boundary. Outside these limits: an error before any launch. Nothing here synchronises with the host.
+ * Limits: every tensor <= 0xFFFFFFF0 bytes and on a 16-byte boundary. Outside them: an error before any launch. Nothing here
+ *   synchronises with the host.
  * ---------------------------------------------------------------------------------------------- */
-int mrcnn_conv_backward_weights_strided_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* z,
-                                            int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
-                                            int32_t pad_bottom, int32_t pad_right, float* dw, void* workspace, size_t workspace_bytes,
-                                            mrcnn_stream_t stream);
-int mrcnn_conv_backward_data_strided_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* w,
-                                         int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
-                                         int32_t pad_bottom, int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes,
-                                         mrcnn_stream_t stream);
-size_t mrcnn_conv_backward_strided_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
-                                                   int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                                   int32_t pad_right);
-int32_t mrcnn_conv_backward_weights_strided_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t kh,
-                                                  int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                                  int32_t pad_right);
 int mrcnn_dilate2_sum_f32(const float* a, const float* b2, int32_t batch, int32_t height, int32_t width, int32_t channels, float* dx,
                           mrcnn_stream_t stream);
 int mrcnn_maxpool_backward_f32(const float* dy, const float* x, int32_t batch, int32_t height, int32_t width, int32_t channels,

@@ -1,7 +1,7 @@
 // Backward of the fp32 NHWC convolution with a frozen affine and an activation (the layers train_model trains, model.py:1010-1016;
 // stride 1 for the heads, stride 2 for the stem and the first block of C3 / C4 / C5): gradients for the input, the weight, the
-// shift and the residual. The rule is stated at mrcnn_conv_act_backward_f32 and, for a stride, at mrcnn_conv_backward_weights_strided_f32
-// in include/maskrcnn_hip.h. Built with -ffp-contract=off: g and z are separately rounded operations.
+// shift and the residual. The rule is stated at mrcnn_conv_act_backward_f32 in include/maskrcnn_hip.h, for both strides. Built
+// with -ffp-contract=off: g and z are separately rounded operations.
 //   conv_act_backward   elementwise: dy, y -> z (= g * scale, pitch Cout4), g, the 2 x 2 residual sums, and per (workgroup, thread
 //                       row) fp64 partials of dshift — a thread owns channel quads and walks its pixels in ascending order.
 //   conv_weight_flip    w [Cout][KH][KW][Cin] -> w' [Cin][KH][KW][Cout4], taps mirrored: the data gradient is then the FORWARD
@@ -382,9 +382,9 @@ struct BackwardShape {
     long long M, N;
 };
 
-// The limits of the three entry points, checked before any launch.
-int fill_shape(BackwardShape& s, const char* who, int batch, int height, int width, int cin, int cout, int kh, int kw, int pad_top,
-               int pad_left, int pad_bottom, int pad_right, int stride = 1) {
+// The limits of the data and weight gradients and the two queries, checked before any launch.
+int fill_shape(BackwardShape& s, const char* who, int batch, int height, int width, int cin, int cout, int kh, int kw, int stride,
+               int pad_top, int pad_left, int pad_bottom, int pad_right) {
     if (!(stride == 1 || stride == 2)) return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: stride must be 1 or 2, got %d", who, stride);
     if (!(batch >= 1 && height >= 1 && width >= 1 && cin >= 4 && cin % 4 == 0 && cout >= 1))
         return mrcnn::fail(MRCNN_ERR_INVALID_ARGUMENT, "%s: bad shape B=%d H=%d W=%d Cin=%d (Cin %% 4 == 0 required) Cout=%d", who,
@@ -432,19 +432,21 @@ int launch_wgrad(WgradParams& p, int chunks, hipStream_t stream) {
 }  // namespace
 
 extern "C" size_t mrcnn_conv_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
-                                                      int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                                      int32_t pad_right) {
+                                                      int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                                      int32_t pad_bottom, int32_t pad_right) {
     BackwardShape s;
-    if (fill_shape(s, "conv_backward_workspace_bytes", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right))
+    if (fill_shape(s, "conv_backward_workspace_bytes", batch, height, width, cin, cout, kh, kw, stride, pad_top, pad_left, pad_bottom,
+                   pad_right))
         return 0;
     return backward_workspace_bytes(s);
 }
 
 extern "C" int32_t mrcnn_conv_backward_weights_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
-                                                     int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left, int32_t pad_bottom,
-                                                     int32_t pad_right) {
+                                                     int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                                     int32_t pad_bottom, int32_t pad_right) {
     BackwardShape s;
-    if (fill_shape(s, "conv_backward_weights_chunk", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right))
+    if (fill_shape(s, "conv_backward_weights_chunk", batch, height, width, cin, cout, kh, kw, stride, pad_top, pad_left, pad_bottom,
+                   pad_right))
         return 0;
     return wgrad_chunk(s.M, s.Cout, s.N);
 }
@@ -495,12 +497,15 @@ extern "C" int mrcnn_conv_act_backward_f32(const float* dy, const float* y, int3
 }
 
 extern "C" int mrcnn_conv_backward_data_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin, const float* w,
-                                            int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left,
+                                            int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
                                             int32_t pad_bottom, int32_t pad_right, float* dx, void* workspace, size_t workspace_bytes,
                                             mrcnn_stream_t stream) {
     const char* who = "conv_backward_data";
     BackwardShape s;
-    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right)) return rc;
+    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, stride, pad_top, pad_left, pad_bottom, pad_right)) return rc;
+    MRCNN_REQUIRE(stride == 1 || (kh == 1 && kw == 1 && pad_top == 0 && pad_left == 0 && pad_bottom == 0 && pad_right == 0),
+                  "%s: the stride-2 data gradient covers the 1 x 1 kernel without padding, got %d x %d with pads (%d, %d, %d, %d)", who,
+                  kh, kw, pad_top, pad_left, pad_bottom, pad_right);
     MRCNN_REQUIRE(z && w && dx, "%s: null pointer", who);
     const size_t need = sizeof(float) * static_cast<size_t>(s.N) * s.Cout4;
     MRCNN_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
@@ -511,18 +516,20 @@ extern "C" int mrcnn_conv_backward_data_f32(const float* z, int32_t batch, int32
     hipLaunchKernelGGL(conv_weight_flip, dim3(static_cast<unsigned>((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, w, cout,
                        s.Cout4, kh, kw, cin, wt);
     if (int rc = mrcnn::check_launch("conv_weight_flip")) return rc;
+    // the forward at stride 1 on the output map: at stride 2 (1 x 1, pads 0) a plain GEMM that writes the compact [B][OH][OW][Cin]
     return mrcnn_conv_bn_act_nhwc_f32(z, batch, s.OH, s.OW, s.Cout4, wt, cin, kh, kw, 1, kh - 1 - pad_top, kw - 1 - pad_left,
                                       kh - 1 - pad_bottom, kw - 1 - pad_right, nullptr, nullptr, nullptr, 1, 0, dx, stream);
 }
 
-namespace {
-
-// Both weight-gradient entry points: the stride only moves the pixel table's (iy0, ix0) and, through M, the chunk length.
-int backward_weights(const char* who, const float* x, int batch, int height, int width, int cin, const float* z, int cout, int kh,
-                     int kw, int stride, int pad_top, int pad_left, int pad_bottom, int pad_right, const int32_t* row_counts,
-                     int rows_per_group, float* dw, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
+// The stride only moves the pixel table's (iy0, ix0) and, through M, the chunk length.
+extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
+                                               const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top,
+                                               int32_t pad_left, int32_t pad_bottom, int32_t pad_right, const int32_t* row_counts,
+                                               int32_t rows_per_group, float* dw, void* workspace, size_t workspace_bytes,
+                                               mrcnn_stream_t stream) {
+    const char* who = "conv_backward_weights";
     BackwardShape s;
-    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, stride)) return rc;
+    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, stride, pad_top, pad_left, pad_bottom, pad_right)) return rc;
     MRCNN_REQUIRE(!(row_counts && stride != 1), "%s: row counts need stride 1", who);
     MRCNN_REQUIRE(x && z && dw, "%s: null pointer", who);
     if (row_counts)
@@ -547,72 +554,4 @@ int backward_weights(const char* who, const float* x, int batch, int height, int
                             : launch_wgrad<128, 2, 2>(p, chunks, st))
         return rc;
     return launch_reduce(p.part, 1LL * cout * s.N, chunks, 1LL * cout * s.N, dw, st);
-}
-
-}  // namespace
-
-extern "C" int mrcnn_conv_backward_weights_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
-                                               const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t pad_top, int32_t pad_left,
-                                               int32_t pad_bottom, int32_t pad_right, const int32_t* row_counts,
-                                               int32_t rows_per_group, float* dw, void* workspace, size_t workspace_bytes,
-                                               mrcnn_stream_t stream) {
-    return backward_weights("conv_backward_weights", x, batch, height, width, cin, z, cout, kh, kw, 1, pad_top, pad_left, pad_bottom,
-                            pad_right, row_counts, rows_per_group, dw, workspace, workspace_bytes, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ the entry points with a stride
-extern "C" size_t mrcnn_conv_backward_strided_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
-                                                              int32_t kh, int32_t kw, int32_t stride, int32_t pad_top,
-                                                              int32_t pad_left, int32_t pad_bottom, int32_t pad_right) {
-    BackwardShape s;
-    if (fill_shape(s, "conv_backward_strided_workspace_bytes", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom,
-                   pad_right, stride))
-        return 0;
-    return backward_workspace_bytes(s);
-}
-
-extern "C" int32_t mrcnn_conv_backward_weights_strided_chunk(int32_t batch, int32_t height, int32_t width, int32_t cin, int32_t cout,
-                                                             int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
-                                                             int32_t pad_bottom, int32_t pad_right) {
-    BackwardShape s;
-    if (fill_shape(s, "conv_backward_weights_strided_chunk", batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom,
-                   pad_right, stride))
-        return 0;
-    return wgrad_chunk(s.M, s.Cout, s.N);
-}
-
-extern "C" int mrcnn_conv_backward_weights_strided_f32(const float* x, int32_t batch, int32_t height, int32_t width, int32_t cin,
-                                                       const float* z, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
-                                                       int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right,
-                                                       float* dw, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
-    return backward_weights("conv_backward_weights_strided", x, batch, height, width, cin, z, cout, kh, kw, stride, pad_top, pad_left,
-                            pad_bottom, pad_right, nullptr, 0, dw, workspace, workspace_bytes, stream);
-}
-
-extern "C" int mrcnn_conv_backward_data_strided_f32(const float* z, int32_t batch, int32_t height, int32_t width, int32_t cin,
-                                                    const float* w, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
-                                                    int32_t pad_top, int32_t pad_left, int32_t pad_bottom, int32_t pad_right,
-                                                    float* dx, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
-    const char* who = "conv_backward_data_strided";
-    if (stride == 1)
-        return mrcnn_conv_backward_data_f32(z, batch, height, width, cin, w, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, dx,
-                                            workspace, workspace_bytes, stream);
-    BackwardShape s;
-    if (int rc = fill_shape(s, who, batch, height, width, cin, cout, kh, kw, pad_top, pad_left, pad_bottom, pad_right, stride)) return rc;
-    MRCNN_REQUIRE(kh == 1 && kw == 1 && pad_top == 0 && pad_left == 0 && pad_bottom == 0 && pad_right == 0,
-                  "%s: the stride-2 data gradient covers the 1 x 1 kernel without padding, got %d x %d with pads (%d, %d, %d, %d)", who,
-                  kh, kw, pad_top, pad_left, pad_bottom, pad_right);
-    MRCNN_REQUIRE(z && w && dx, "%s: null pointer", who);
-    const size_t need = sizeof(float) * static_cast<size_t>(s.N) * s.Cout4;
-    MRCNN_REQUIRE(workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
-                  "%s: workspace of %zu bytes, 16-byte aligned, needed (got %zu)", who, need, workspace_bytes);
-    float* wt = static_cast<float*>(workspace);
-    hipStream_t st = mrcnn::as_stream(stream);
-    const long long total = s.N * s.Cout4;
-    hipLaunchKernelGGL(conv_weight_flip, dim3(static_cast<unsigned>((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, w, cout,
-                       s.Cout4, 1, 1, cin, wt);
-    if (int rc = mrcnn::check_launch("conv_weight_flip")) return rc;
-    // the compact gradient [B][OH][OW][Cin]: a plain GEMM of z with w' over the output pixels
-    return mrcnn_conv_bn_act_nhwc_f32(z, batch, s.OH, s.OW, s.Cout4, wt, cin, 1, 1, 1, 0, 0, 0, 0, nullptr, nullptr, nullptr, 1, 0, dx,
-                                      stream);
 }

@@ -401,15 +401,12 @@ def _backward_stride(who, stride) -> int:
 
 
 def conv_backward_chunk(b: int, h: int, w: int, cin: int, cout: int, kh: int, kw: int, pad=(0, 0, 0, 0), stride: int = 1) -> int:
-    """The chunk length L of the weight gradient of this layer (mrcnn_conv_backward_weights_chunk, or _strided_chunk with a stride of
-    2): its pixel axis M = B*OH*OW is summed in ceil(M / L) fp32 chains that a second launch adds in fp64. A function of the shape
-    only (the stride enters through OH and OW); host arithmetic."""
+    """The chunk length L of the weight gradient of this layer (mrcnn_conv_backward_weights_chunk): its pixel axis M = B*OH*OW is
+    summed in ceil(M / L) fp32 chains that a second launch adds in fp64. A function of the shape only (the stride enters through OH
+    and OW); host arithmetic."""
     pt, pl, pb, pr = [int(v) for v in pad]
-    shape = (int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw))
-    if _backward_stride("conv_backward_chunk", stride) == 1:
-        got = int(lib.mrcnn_conv_backward_weights_chunk(*shape, pt, pl, pb, pr))
-    else:
-        got = int(lib.mrcnn_conv_backward_weights_strided_chunk(*shape, stride, pt, pl, pb, pr))
+    stride = _backward_stride("conv_backward_chunk", stride)
+    got = int(lib.mrcnn_conv_backward_weights_chunk(int(b), int(h), int(w), int(cin), int(cout), int(kh), int(kw), stride, pt, pl, pb, pr))
     if got < 1:
         raise RuntimeError(f"conv_backward_chunk: the conv backward refuses these arguments ({lib.mrcnn_last_error().decode()})")
     return got
@@ -429,7 +426,7 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
     entries not asked for are None (z: when neither dx nor dw is). No gradient of scale: BatchNorm is frozen. dx is the forward
     kernel on z bit for bit; dw is summed in chunks of conv_backward_chunk(...) pixels, then in fp64; dshift in fp64. Two calls give
     the same bits. Two launches per gradient, no floating-point atomic, no host synchronisation.
-    stride 1 or 2 as the forward took it (the rule with a stride is stated at mrcnn_conv_backward_weights_strided_f32). At stride 2
+    stride 1 or 2 as the forward took it (the same entry points and the same rule, which the header states for both). At stride 2
     OH = (H + top + bottom - KH) // 2 + 1; dw and dshift are as above for any kernel size; dx is returned only for a 1x1 kernel
     without padding and is then the COMPACT gradient [B,OH,OW,Cin] — the values at the even positions of the full one, which
     ops.dilate2_sum writes out (adding a second compact gradient on the way). No row_counts and no scatter at stride 2."""
@@ -480,10 +477,8 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
         row_counts = checked(who, "row_counts", row_counts, _I32, (m // rpg,))
     if res_div == 2 and (oh % 2 or ow % 2):
         refuse(who, "res_div", f"1 for an odd output size ({oh} x {ow})", res_div)
-    shape_args = (b, h, wd, cin, cout, kh, kw, pt, pl, pb, pr)
-    strided_args = (b, h, wd, cin, cout, kh, kw, stride, pt, pl, pb, pr)
-    nbytes = int(lib.mrcnn_conv_backward_workspace_bytes(*shape_args) if stride == 1 else
-                 lib.mrcnn_conv_backward_strided_workspace_bytes(*strided_args))
+    shape_args = (b, h, wd, cin, cout, kh, kw, stride, pt, pl, pb, pr)
+    nbytes = int(lib.mrcnn_conv_backward_workspace_bytes(*shape_args))
     if nbytes < 1:
         raise RuntimeError(f"{who}: {lib.mrcnn_last_error().decode()}")
     dev, cout4, n = x.device, -(-cout // 4) * 4, kh * kw * cin
@@ -508,33 +503,18 @@ def conv_bn_act_backward(grad_out: torch.Tensor, x: torch.Tensor, w: torch.Tenso
                  _stream()),
                 lambda: (0, (m, cout, 1), 4 * m * (2 * cout + cout4), "conv_act_backward"))
     dx = dw = None
-    if need_dx and stride == 2:
-        dx = torch.empty(b, oh, ow, cin, dtype=_F32, device=dev)
-        _launch(lib.mrcnn_conv_backward_data_strided_f32,
-                (z.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, stride, pt, pl, pb, pr, dx.data_ptr(), ws.data_ptr(), nbytes,
-                 _stream()),
-                lambda: (2.0 * m * n * cout, (m, cin, cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()), "conv_backward_data_strided"))
-    elif need_dx:
-        dx = torch.empty(b, h, wd, cin, dtype=_F32, device=dev)
+    if need_dx:
+        dx = torch.empty((b, oh, ow, cin) if stride == 2 else (b, h, wd, cin), dtype=_F32, device=dev)   # stride 2: the compact one
         _launch(lib.mrcnn_conv_backward_data_f32,
-                (z.data_ptr(), b, h, wd, cin, w.data_ptr(), cout, kh, kw, pt, pl, pb, pr, dx.data_ptr(), ws.data_ptr(), nbytes,
-                 _stream()),
-                lambda: (2.0 * m * n * cout, (b * h * wd, cin, kh * kw * cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()),
+                (z.data_ptr(), *shape_args[:4], w.data_ptr(), *shape_args[4:], dx.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+                lambda: (2.0 * m * n * cout, (dx.numel() // cin, cin, kh * kw * cout4), 4 * (m * cout4 + 2 * n * cout4 + dx.numel()),
                          "conv_backward_data"))
-    if need_dw and stride == 2:
-        dw = torch.empty(cout, kh, kw, cin, dtype=_F32, device=dev)
-        chunks2 = -(-m // int(lib.mrcnn_conv_backward_weights_strided_chunk(*strided_args)))
-        _launch(lib.mrcnn_conv_backward_weights_strided_f32,
-                (x.data_ptr(), b, h, wd, cin, z.data_ptr(), cout, kh, kw, stride, pt, pl, pb, pr, dw.data_ptr(), ws.data_ptr(), nbytes,
-                 _stream()),
-                lambda: (2.0 * m * n * cout, (cout, n, m), 4 * (x.numel() + m * cout4 + (2 * chunks2 + 1) * n * cout),
-                         "conv_backward_weights_strided"))
-    elif need_dw:
+    if need_dw:
         dw = torch.empty(cout, kh, kw, cin, dtype=_F32, device=dev)
         chunks = -(-m // int(lib.mrcnn_conv_backward_weights_chunk(*shape_args)))
         _launch(lib.mrcnn_conv_backward_weights_f32,
-                (x.data_ptr(), b, h, wd, cin, z.data_ptr(), cout, kh, kw, pt, pl, pb, pr, _ptr(row_counts), rpg, dw.data_ptr(),
-                 ws.data_ptr(), nbytes, _stream()),
+                (x.data_ptr(), *shape_args[:4], z.data_ptr(), *shape_args[4:], _ptr(row_counts), rpg, dw.data_ptr(), ws.data_ptr(),
+                 nbytes, _stream()),
                 lambda: (2.0 * m * n * cout, (cout, n, m), 4 * (x.numel() + m * cout4 + (2 * chunks + 1) * n * cout),
                          "conv_backward_weights"))
     return ConvBackward(dx, dw, dshift, dres2 if res_div == 2 else g, z)

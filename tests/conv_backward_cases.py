@@ -51,7 +51,7 @@ class Case:
 
     @property
     def shape_args(self):
-        return (self.b, self.h, self.w, self.cin, self.cout, *self.k, *self.pad)
+        return (self.b, self.h, self.w, self.cin, self.cout, *self.k, 1, *self.pad)
 
 
 def chunk_of(case) -> int:

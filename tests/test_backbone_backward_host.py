@@ -13,9 +13,8 @@ import backbone_backward_cases as bb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "maskrcnn_hip.h")
-ENTRY_POINTS = ("mrcnn_conv_backward_weights_strided_f32", "mrcnn_conv_backward_data_strided_f32",
-                "mrcnn_conv_backward_strided_workspace_bytes", "mrcnn_conv_backward_weights_strided_chunk", "mrcnn_dilate2_sum_f32",
-                "mrcnn_maxpool_backward_f32")
+ENTRY_POINTS = ("mrcnn_conv_backward_weights_f32", "mrcnn_conv_backward_data_f32", "mrcnn_conv_backward_workspace_bytes",
+                "mrcnn_conv_backward_weights_chunk", "mrcnn_dilate2_sum_f32", "mrcnn_maxpool_backward_f32")
 
 
 # ------------------------------------------------------------------------------------------------------ exactness conditions
@@ -110,17 +109,17 @@ def test_nan_and_ties_follow_torchs_walk():
 
 
 # ------------------------------------------------------------------------------------------------------------------- chunking
-def test_the_strided_chunk_function_through_the_librarys_query():
+def test_the_chunk_function_with_a_stride_through_the_librarys_query():
     from maskrcnn_amd import ops
     for c in bb.CONVS:
         L = bb.chunk_of(c)
         assert L >= 128 and L % 32 == 0, (c.id, L)
     c = bb.conv_case(bb.MULTI_CHUNK)
     assert c.m == 512 and bb.chunk_of(c) == 128 and -(-c.m // bb.chunk_of(c)) == 4
-    # the stride enters through M = B*OH*OW alone: stride 1 is the existing query, and a stride-2 1x1 layer has the chunk of the
-    # stride-1 layer on its output map
+    # the stride enters through M = B*OH*OW alone: stride 1 is the default (8 tiles of 128 x 128: 64 chunks of the 8192 pixels),
+    # and a stride-2 1x1 layer has the chunk of the stride-1 layer on its output map
     args = (2, 64, 64, 256, 512, 1, 1)
-    assert ops.conv_backward_chunk(*args, stride=1) == ops.conv_backward_chunk(*args)
+    assert ops.conv_backward_chunk(*args, stride=1) == ops.conv_backward_chunk(*args) == 128
     assert ops.conv_backward_chunk(*args, stride=2) == ops.conv_backward_chunk(2, 32, 32, 256, 512, 1, 1)
     assert ops.conv_backward_chunk(2, 63, 63, 256, 512, 1, 1, stride=2) == ops.conv_backward_chunk(2, 32, 32, 256, 512, 1, 1)
     assert ops.conv_backward_chunk(2, 1024, 1024, 4, 64, 7, 7, (3, 3, 3, 3), stride=2) % 32 == 0       # the stem
@@ -138,27 +137,32 @@ def test_header_declares_and_the_library_exports_the_entry_points():
     for name in ENTRY_POINTS:
         assert name in declared and name in protos and hasattr(_lib.lib, name), name
         assert getattr(_lib.lib, name).argtypes == protos[name][1]
-    assert _lib.header_abi_version() >= 32 and int(_lib.lib.mrcnn_abi_version()) == _lib.header_abi_version()
+    # one set of entry points, the stride an argument of the four above: no conv name that carries the stride is declared, spoken of
+    # or exported (the library's symbol table and its message strings)
+    with_stride = re.compile(r"conv_\w*strided")
+    assert not with_stride.search(text) and not [n for n in declared if with_stride.search(n)]
+    assert not re.search(with_stride.pattern.encode(), open(_lib.LIB_PATH, "rb").read())
+    assert _lib.header_abi_version() >= 35 and int(_lib.lib.mrcnn_abi_version()) == _lib.header_abi_version()
     for phrase in ("the first of equal maxima wins", "a padding tap loses the gradient", "the LAST NaN of a window",
                    "Every byte of dx is\n *           written exactly once", "a + b2 as ONE fp32\n *           add",
                    "in ascending (oy, ox) order", "it depends on the stride through M = B*OH*OW"):
         assert phrase in text, phrase
     i32, vp, sz = _lib.c_i32, _lib.c_vp, ctypes.c_size_t
-    assert protos["mrcnn_conv_backward_weights_strided_chunk"] == (i32, [i32] * 12)
-    assert protos["mrcnn_conv_backward_strided_workspace_bytes"] == (sz, [i32] * 12)
-    assert protos["mrcnn_conv_backward_weights_strided_f32"] == (ctypes.c_int, [vp] + [i32] * 4 + [vp] + [i32] * 8 + [vp, vp, sz, vp])
-    assert protos["mrcnn_conv_backward_data_strided_f32"] == (ctypes.c_int, [vp] + [i32] * 4 + [vp] + [i32] * 8 + [vp, vp, sz, vp])
+    # the stride comes directly after kw, where the forward has it; the weight gradient alone takes row counts
+    assert protos["mrcnn_conv_backward_weights_chunk"] == (i32, [i32] * 12)
+    assert protos["mrcnn_conv_backward_workspace_bytes"] == (sz, [i32] * 12)
+    assert protos["mrcnn_conv_backward_weights_f32"] == (ctypes.c_int, [vp] + [i32] * 4 + [vp] + [i32] * 8 + [vp, i32, vp, vp, sz, vp])
+    assert protos["mrcnn_conv_backward_data_f32"] == (ctypes.c_int, [vp] + [i32] * 4 + [vp] + [i32] * 8 + [vp, vp, sz, vp])
     assert protos["mrcnn_dilate2_sum_f32"] == (ctypes.c_int, [vp, vp, i32, i32, i32, i32, vp, vp])
     assert protos["mrcnn_maxpool_backward_f32"] == (ctypes.c_int, [vp, vp] + [i32] * 10 + [vp, vp])
-    # the existing signatures are as they were
-    assert protos["mrcnn_conv_backward_weights_chunk"] == (i32, [i32] * 11)
-    assert protos["mrcnn_conv_backward_data_f32"] == (ctypes.c_int, [vp] + [i32] * 4 + [vp] + [i32] * 7 + [vp, vp, sz, vp])
-    # queries: stride 1 is the existing answer; a refused stride answers 0
+    # queries: at stride 1 the workspace holds the ceil(M / L) chunk sums of Cout * KH*KW*Cin floats; a refused stride answers 0
+    from maskrcnn_amd import ops
     lib = _lib.lib
-    assert int(lib.mrcnn_conv_backward_strided_workspace_bytes(2, 16, 16, 64, 64, 3, 3, 1, 1, 1, 1, 1)) == \
-        int(lib.mrcnn_conv_backward_workspace_bytes(2, 16, 16, 64, 64, 3, 3, 1, 1, 1, 1))
-    assert int(lib.mrcnn_conv_backward_strided_workspace_bytes(2, 16, 16, 64, 64, 3, 3, 3, 1, 1, 1, 1)) == 0
-    assert int(lib.mrcnn_conv_backward_weights_strided_chunk(2, 16, 16, 64, 64, 3, 3, 0, 1, 1, 1, 1)) == 0
+    chunks = -(-2 * 16 * 16 // ops.conv_backward_chunk(2, 16, 16, 64, 64, 3, 3, (1, 1, 1, 1)))
+    assert chunks == 4
+    assert int(lib.mrcnn_conv_backward_workspace_bytes(2, 16, 16, 64, 64, 3, 3, 1, 1, 1, 1, 1)) == chunks * 64 * 9 * 64 * 4
+    assert int(lib.mrcnn_conv_backward_workspace_bytes(2, 16, 16, 64, 64, 3, 3, 3, 1, 1, 1, 1)) == 0
+    assert int(lib.mrcnn_conv_backward_weights_chunk(2, 16, 16, 64, 64, 3, 3, 0, 1, 1, 1, 1)) == 0
     assert b"stride must be 1 or 2" in lib.mrcnn_last_error()
 
 
@@ -166,14 +170,17 @@ def test_the_library_refuses_bad_arguments_before_any_launch():
     """No GPU here: a call that got as far as a launch would fail with another message (or crash on the null pointers)."""
     from maskrcnn_amd._lib import lib
     err = lambda: lib.mrcnn_last_error().decode()
-    assert lib.mrcnn_conv_backward_data_strided_f32(None, 1, 8, 8, 8, None, 8, 3, 3, 2, 1, 1, 1, 1, None, None, 0, None) != 0
+    assert lib.mrcnn_conv_backward_data_f32(None, 1, 8, 8, 8, None, 8, 3, 3, 2, 1, 1, 1, 1, None, None, 0, None) != 0
     assert "the stride-2 data gradient covers the 1 x 1 kernel without padding, got 3 x 3 with pads (1, 1, 1, 1)" in err()
-    assert lib.mrcnn_conv_backward_data_strided_f32(None, 1, 8, 8, 8, None, 8, 1, 1, 4, 0, 0, 0, 0, None, None, 0, None) != 0
+    assert lib.mrcnn_conv_backward_data_f32(None, 1, 8, 8, 8, None, 8, 1, 1, 4, 0, 0, 0, 0, None, None, 0, None) != 0
     assert "stride must be 1 or 2, got 4" in err()
-    assert lib.mrcnn_conv_backward_weights_strided_f32(None, 1, 8, 8, 6, None, 8, 1, 1, 2, 0, 0, 0, 0, None, None, 0, None) != 0
+    assert lib.mrcnn_conv_backward_weights_f32(None, 1, 8, 8, 6, None, 8, 1, 1, 2, 0, 0, 0, 0, None, 0, None, None, 0, None) != 0
     assert "Cin % 4 == 0 required" in err()
-    assert lib.mrcnn_conv_backward_weights_strided_f32(None, 1, 8, 8, 8, None, 8, 1, 1, 2, 0, 0, 0, 0, None, None, 0, None) != 0
+    assert lib.mrcnn_conv_backward_weights_f32(None, 1, 8, 8, 8, None, 8, 1, 1, 2, 0, 0, 0, 0, None, 0, None, None, 0, None) != 0
     assert "null pointer" in err()
+    # row counts at stride 2 (a dummy non-null pointer: never dereferenced on the host, and no launch is reached)
+    assert lib.mrcnn_conv_backward_weights_f32(None, 1, 8, 8, 8, None, 8, 1, 1, 2, 0, 0, 0, 0, 16, 4, None, None, 0, None) != 0
+    assert "row counts need stride 1" in err()
     assert lib.mrcnn_dilate2_sum_f32(None, None, 1, 5, 5, 6, None, None) != 0 and "C % 4 == 0 required" in err()
     assert lib.mrcnn_dilate2_sum_f32(None, None, 1, 5, 5, 8, None, None) != 0 and "null pointer" in err()
     assert lib.mrcnn_dilate2_sum_f32(None, None, 1 << 14, 1 << 10, 1 << 10, 8, None, None) != 0 and "tensor too large" in err()

@@ -71,14 +71,14 @@ def test_header_declares_and_the_library_exports_the_entry_points():
                    "are never read into the arithmetic", "(g00 + g01) + (g10 + g11)"):
         assert phrase in text, phrase
     i32, vp = _lib.c_i32, _lib.c_vp
-    assert protos["mrcnn_conv_backward_weights_chunk"] == (i32, [i32] * 11)
-    assert protos["mrcnn_conv_backward_workspace_bytes"] == (ctypes.c_size_t, [i32] * 11)
-    assert protos["mrcnn_conv_backward_weights_f32"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp,
-                                                                      i32, vp, vp, ctypes.c_size_t, vp])
+    assert protos["mrcnn_conv_backward_weights_chunk"] == (i32, [i32] * 12)
+    assert protos["mrcnn_conv_backward_workspace_bytes"] == (ctypes.c_size_t, [i32] * 12)
+    assert protos["mrcnn_conv_backward_weights_f32"] == (ctypes.c_int, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32,
+                                                                      vp, i32, vp, vp, ctypes.c_size_t, vp])
     # the workspace holds the chunk sums: ceil(M / L) * Cout * KH*KW*Cin floats where that is the largest of the three uses
     c = cb.case("3x3_pow2")
     assert int(_lib.lib.mrcnn_conv_backward_workspace_bytes(*c.shape_args)) == 4 * cb.chunks_of(c) * c.cout * 9 * c.cin
-    assert int(_lib.lib.mrcnn_conv_backward_workspace_bytes(0, 1, 1, 4, 4, 1, 1, 0, 0, 0, 0)) == 0
+    assert int(_lib.lib.mrcnn_conv_backward_workspace_bytes(0, 1, 1, 4, 4, 1, 1, 1, 0, 0, 0, 0)) == 0
 
 
 def test_the_kernel_file_is_built_without_contraction_and_has_no_atomic_or_assembly():

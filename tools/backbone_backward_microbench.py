@@ -17,7 +17,7 @@ HIP events go around --inner back-to-back calls after a warm-up, the time of one
 windows is reported with the minimum and the maximum; the measurements alternate inside a repetition. Per block:
   backward            the whole block's backward through autograd (dx, four dw, four dshift), the graph retained
   <entry point>       its pieces apart, from the events ops.CONV_PROFILE puts around each launch group, summed over the block's
-                      convs (conv_act_backward, conv_backward_data[_strided], conv_backward_weights[_strided], dilate2_sum)
+                      convs at either stride (conv_act_backward, conv_backward_data, conv_backward_weights, dilate2_sum)
   forward             the same block's forward through layers.bottleneck
   aten_convolution_backward   torch.ops.aten.convolution_backward (input, weight and bias gradients) of the block's three or four
                       convs back to back on the same shapes, NCHW, in the same process; a failure is recorded as its reason
