@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 35
+#define MRCNN_ABI_VERSION 36
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -98,6 +98,15 @@ int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t depth, int
                            int32_t width, const float* boxes, const int32_t* box_index,
                            int32_t num_boxes, float extrapolation_value, int32_t crop_height,
                            int32_t crop_width, float* crops, mrcnn_stream_t stream);
+/* What mrcnn_crop_forward_f32 launches for these arguments — the launcher's own answer (it launches from the same function),
+ * host arithmetic only, no device needed. image / crops are looked at for their 16-byte alignment only; num_boxes >= 1.
+ *   plan_out[0] route: 1 the LDS-staged kernel (crop_forward_nchw_staged), 0 the gather kernel (crop_forward_nchw)
+ *   plan_out[1] channels per wave (staged) / per workgroup (gather)      plan_out[2] channel slabs = ceil(depth / [1])
+ *   plan_out[3] workgroup numbering of the staged kernel: 0 grid (box, slab), 1 / 2 the XCD-local 1-D grids (csrc/crop.hip)
+ *   plan_out[4] 16-byte slots of a wave's LDS-DMA ring (0 on the gather route)      plan_out[5] dynamic LDS bytes
+ * The process's tuning switches (MRCNN_CROP_STAGED / _CPW / _MAP / _RING, read once) are part of the answer. */
+int mrcnn_crop_forward_plan(const float* image, const float* crops, int32_t depth, int32_t height, int32_t width,
+                            int32_t num_boxes, int32_t crop_height, int32_t crop_width, int32_t plan_out[6]);
 
 /* crop_and_resize backward — replaces
  *   void crop_backward(grads, boxes, box_index, grads_image)

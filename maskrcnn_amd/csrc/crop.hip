@@ -149,7 +149,8 @@ typedef float cs_f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) unsigned char cs_lds_u8;
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n: the largest immediate of a fixed set that does not exceed n (waiting for
-// more than asked is always safe)
+// more than asked is always safe). With the default 512-slot ring the largest budget is 15: the arms above 14 are reached only
+// with a larger MRCNN_CROP_RING.
 __device__ __forceinline__ void cs_wait_vmcnt_at_most(int n) {
     if (n >= 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
     else if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
@@ -536,22 +537,17 @@ const CropTuning& crop_tuning() {
 }
 bool crop_staged_enabled() { return crop_tuning().staged; }
 
-}  // namespace
-
-extern "C" int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t depth,
-                                      int32_t height, int32_t width, const float* boxes,
-                                      const int32_t* box_index, int32_t num_boxes,
-                                      float extrapolation_value, int32_t crop_height,
-                                      int32_t crop_width, float* crops, mrcnn_stream_t stream) {
-    MRCNN_REQUIRE(batch >= 1 && depth >= 1 && height >= 1 && width >= 1,
-                  "crop_forward: bad image shape [%d,%d,%d,%d]", batch, depth, height, width);
-    MRCNN_REQUIRE(crop_height >= 1 && crop_width >= 1 && crop_height + crop_width <= 4096,
-                  "crop_forward: bad crop size %dx%d", crop_height, crop_width);
-    MRCNN_REQUIRE(num_boxes >= 0, "crop_forward: num_boxes=%d", num_boxes);
-    if (num_boxes == 0) return MRCNN_OK;
-    MRCNN_REQUIRE(image && boxes && box_index && crops, "crop_forward: null pointer");
+// What the forward launches, decided HERE and nowhere else: mrcnn_crop_forward_f32 launches from it, mrcnn_crop_forward_plan
+// reports it. route 1: the staged kernel, `cpw` channels per wave, grid numbering `mode` (wgs workgroups when mode != 0);
+// route 0: the gather kernel, `cpw` channels per workgroup, grid (num_boxes, slabs).
+struct CropPlan {
+    int route, cpw, slabs, mode, ring_slots;
+    int64_t wgs;
+    size_t lds;
+};
+CropPlan crop_plan(const void* image, const void* crops, int depth, int height, int width, int num_boxes, int crop_height,
+                   int crop_width) {
     const int plane = crop_height * crop_width;
-    hipStream_t s = mrcnn::as_stream(stream);
     // the staged kernel: 4 positions per lane, 16-byte segments and stores, 32-bit byte offsets inside one image
     const bool staged = plane % 4 == 0 && plane <= 256 && crop_height + crop_width <= 64 && width % 4 == 0 &&
                         (reinterpret_cast<uintptr_t>(image) & 15) == 0 && (reinterpret_cast<uintptr_t>(crops) & 15) == 0 &&
@@ -571,7 +567,6 @@ extern "C" int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t
                     : mode == 2 ? 8ll * ((num_boxes + 8 / slabs - 1) / (8 / slabs)) : 0;
         if (mode != 0 && wgs > 0x7FFFFFFF) mode = 0;
         if (mode != 0 || slabs <= 65535) {
-            const dim3 grid = mode == 0 ? dim3(num_boxes, slabs) : dim3(static_cast<unsigned>(wgs));
             int ring_slots = CS_RING_SLOTS;
             if (crop_tuning().ring_slots) ring_slots = crop_tuning().ring_slots;
             // + the dword a (lo, lo+1) pair may read past the last slot; and never less than the in-launch gather fallback
@@ -579,10 +574,7 @@ extern "C" int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t
             // (16 x 16 crops: 512 + 8192 B, more than the default ring)
             const size_t lds = std::max(static_cast<size_t>(ring_slots) * 16 + 16,
                                         sizeof(Sample) * (crop_height + crop_width) + sizeof(Tap) * plane);
-            hipLaunchKernelGGL(crop_forward_nchw_staged, grid, dim3(64), lds, s, image, batch, depth,
-                               height, width, boxes, box_index, num_boxes, extrapolation_value, crop_height, crop_width, cpw,
-                               slabs, mode, ring_slots, crops);
-            return mrcnn::check_launch("crop_forward_nchw_staged");
+            return CropPlan{1, cpw, slabs, mode, ring_slots, mode == 0 ? 0 : wgs, lds};
         }
     }
     // a channel slab gives each workgroup ~2k outputs (measured best of 1k/2k/4k/8k: thousands of workgroups keep every CU gathering); grid.y <= 65535
@@ -592,10 +584,54 @@ extern "C" int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t
     int gy = (depth + slab - 1) / slab;
     if (gy > 65535) { gy = 65535; slab = (depth + gy - 1) / gy; gy = (depth + slab - 1) / slab; }
     const size_t lds = sizeof(Sample) * (crop_height + crop_width) + (plane <= 1024 ? sizeof(Tap) * plane : 0);
-    hipLaunchKernelGGL(crop_forward_nchw, dim3(num_boxes, gy), dim3(256), lds,
+    return CropPlan{0, slab, gy, 0, 0, 0, lds};
+}
+
+}  // namespace
+
+extern "C" int mrcnn_crop_forward_f32(const float* image, int32_t batch, int32_t depth,
+                                      int32_t height, int32_t width, const float* boxes,
+                                      const int32_t* box_index, int32_t num_boxes,
+                                      float extrapolation_value, int32_t crop_height,
+                                      int32_t crop_width, float* crops, mrcnn_stream_t stream) {
+    MRCNN_REQUIRE(batch >= 1 && depth >= 1 && height >= 1 && width >= 1,
+                  "crop_forward: bad image shape [%d,%d,%d,%d]", batch, depth, height, width);
+    MRCNN_REQUIRE(crop_height >= 1 && crop_width >= 1 && crop_height + crop_width <= 4096,
+                  "crop_forward: bad crop size %dx%d", crop_height, crop_width);
+    MRCNN_REQUIRE(num_boxes >= 0, "crop_forward: num_boxes=%d", num_boxes);
+    if (num_boxes == 0) return MRCNN_OK;
+    MRCNN_REQUIRE(image && boxes && box_index && crops, "crop_forward: null pointer");
+    hipStream_t s = mrcnn::as_stream(stream);
+    const CropPlan p = crop_plan(image, crops, depth, height, width, num_boxes, crop_height, crop_width);
+    if (p.route == 1) {
+        const dim3 grid = p.mode == 0 ? dim3(num_boxes, p.slabs) : dim3(static_cast<unsigned>(p.wgs));
+        hipLaunchKernelGGL(crop_forward_nchw_staged, grid, dim3(64), p.lds, s, image, batch, depth,
+                           height, width, boxes, box_index, num_boxes, extrapolation_value, crop_height, crop_width, p.cpw,
+                           p.slabs, p.mode, p.ring_slots, crops);
+        return mrcnn::check_launch("crop_forward_nchw_staged");
+    }
+    hipLaunchKernelGGL(crop_forward_nchw, dim3(num_boxes, p.slabs), dim3(256), p.lds,
                        s, image, batch, depth, height, width, boxes,
-                       box_index, extrapolation_value, crop_height, crop_width, slab, crops);
+                       box_index, extrapolation_value, crop_height, crop_width, p.cpw, crops);
     return mrcnn::check_launch("crop_forward_nchw");
+}
+
+// What mrcnn_crop_forward_f32 launches for these arguments (see the header): crop_plan's answer, host arithmetic only.
+extern "C" int mrcnn_crop_forward_plan(const float* image, const float* crops, int32_t depth, int32_t height, int32_t width,
+                                       int32_t num_boxes, int32_t crop_height, int32_t crop_width, int32_t plan_out[6]) {
+    MRCNN_REQUIRE(depth >= 1 && height >= 1 && width >= 1, "crop_forward_plan: bad image shape [%d,%d,%d]", depth, height, width);
+    MRCNN_REQUIRE(crop_height >= 1 && crop_width >= 1 && crop_height + crop_width <= 4096,
+                  "crop_forward_plan: bad crop size %dx%d", crop_height, crop_width);
+    MRCNN_REQUIRE(num_boxes >= 1, "crop_forward_plan: num_boxes=%d (an empty call launches nothing)", num_boxes);
+    MRCNN_REQUIRE(plan_out, "crop_forward_plan: null plan_out");
+    const CropPlan p = crop_plan(image, crops, depth, height, width, num_boxes, crop_height, crop_width);
+    plan_out[0] = p.route;
+    plan_out[1] = p.cpw;
+    plan_out[2] = p.slabs;
+    plan_out[3] = p.mode;
+    plan_out[4] = p.ring_slots;
+    plan_out[5] = static_cast<int32_t>(p.lds);
+    return MRCNN_OK;
 }
 
 extern "C" int mrcnn_crop_backward_f32(const float* grads, const float* boxes,

@@ -165,6 +165,23 @@ def _crop_launch(image, boxes, box_index, extrapolation_value, crop_height, crop
                                      int(crop_height), int(crop_width), crops.data_ptr(), _stream()))
 
 
+CropPlan = collections.namedtuple("CropPlan", "route cpw slabs map_mode ring_slots lds_bytes")
+CROP_ROUTES = ("gather", "staged")
+
+
+def crop_plan(depth: int, height: int, width: int, num_boxes: int, crop_height: int, crop_width: int, image=0,
+              crops=0) -> CropPlan:
+    """What crop / crop_forward launch for these arguments: the launcher's own answer (mrcnn_crop_forward_plan), route as a
+    name. `image` / `crops`: the tensors (or their addresses) — only their 16-byte alignment counts; the default is aligned.
+    cpw: channels per wave ("staged") or per workgroup ("gather"); slabs = ceil(depth / cpw). The process's MRCNN_CROP_*
+    switches, read when the library first needs them, are part of the answer. Host arithmetic only — no GPU is needed."""
+    ptrs = [int(t.data_ptr()) if isinstance(t, torch.Tensor) else int(t) for t in (image, crops)]
+    out = (c_i32 * 6)()
+    check(lib.mrcnn_crop_forward_plan(ptrs[0], ptrs[1], int(depth), int(height), int(width), int(num_boxes), int(crop_height),
+                                      int(crop_width), out))
+    return CropPlan(CROP_ROUTES[out[0]], *[int(v) for v in out[1:]])
+
+
 @_on_device
 def _crop_forward(image, boxes, box_index, extrapolation_value, crop_height, crop_width, crops):
     """Out-param form of crop.h:14-22: `crops` is resized to [N,C,h,w] and overwritten

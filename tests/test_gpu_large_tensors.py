@@ -15,9 +15,14 @@ Inputs are generated on the device; only the patches the sampled rows read are c
 tensors before the next and stays under ~16 GB of device memory.
 """
 import math
+import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from crop_staged_cases import _crop_footprint_slots  # noqa: E402  the staged crop kernel's footprint, restated
 
 pytestmark = pytest.mark.gpu
 
@@ -663,31 +668,6 @@ def test_conv_f16_pipelined_at_the_top_of_the_range(dev):
     torch.cuda.synchronize()
     assert bool((buf == 7.0).all())
     del x2, buf, y
-
-
-def _crop_footprint_slots(box, size_h, size_w, ch, cw):
-    """Host restatement of crop_forward_nchw_staged's footprint (csrc/crop.hip: make_sample in fp32, then S = rows x 16-byte
-    column segments of the samples inside the map): None when no sample is inside, else S. S <= 256 takes the LDS-DMA path."""
-    import numpy as np
-    f = np.float32
-
-    def samples(c1, c2, size, crop):
-        c1, c2 = f(c1), f(c2)
-        scale = f(f(f(c2 - c1) * f(size - 1)) / f(crop - 1))
-        a = f(c1 * f(size - 1))
-        out = []
-        for t in range(crop):
-            v = f(a + f(f(t) * scale))
-            if not (v < 0 or v > f(size - 1)):
-                out.append((int(np.floor(v)), int(np.ceil(v))))
-        return out
-
-    ys, xs = samples(box[0], box[2], size_h, ch), samples(box[1], box[3], size_w, cw)
-    if not ys or not xs:
-        return None
-    ymin, ymax = min(lo for lo, _ in ys), max(hi for _, hi in ys)
-    xmin, xmax = min(lo for lo, _ in xs), max(hi for _, hi in xs)
-    return (ymax - ymin + 1) * (((xmax - (xmin & ~3)) >> 2) + 1)
 
 
 def test_crop_staged_past_2_to_the_31_bytes_per_image(dev, oracle):

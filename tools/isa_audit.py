@@ -15,12 +15,19 @@ number somebody counted by hand. This tool re-derives those counts from the gene
   D  accumulators    inside the innermost loop that holds asm MFMAs (the k loop) the compiler touches no accumulator register
                      (no v_accvgpr_*, no copy) and places no spill code;
   E  M0              at least one instruction between a write of M0 and the LDS-DMA that reads it;
-  F  metadata        vgpr_spill_count == 0 and no scratch in every kernel under contract.
+  F  metadata        vgpr_spill_count == 0 and no scratch in every kernel under contract;
+  G  vmcnt ladder    a run-time wait budget mapped onto asm s_waitcnt vmcnt(N) by a chain of compares (csrc/crop.hip's
+                     cs_wait_vmcnt_at_most): in the order the compares test them the immediates strictly decrease to 0, and each is
+                     at most the constant its arm is guarded by (waiting for fewer operations than the budget allows is safe,
+                     for more is not).
+
+Every source is compiled with the per-source flags maskrcnn_amd/build.py gives it (-ffp-contract=off for crop.hip).
 
 Usage: tools/isa_audit.py [--mutations]    (tests/test_isa_contract.py runs both)
 """
 from __future__ import annotations
 
+import importlib.util
 import os
 import re
 import subprocess
@@ -33,15 +40,28 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-fno-fast-math"
          "-I" + CSRC, "-S", "--cuda-device-only"]
 
 
+BUILD_PY = os.path.join(ROOT, "maskrcnn_amd", "build.py")
+
+
+def build_flags(source: str) -> list:
+    """The per-source flags of the product build (maskrcnn_amd/build.py's SOURCES; loaded by path: importing the package needs
+    the built library)."""
+    spec = importlib.util.spec_from_file_location("_mrcnn_build_flags", BUILD_PY)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return list(mod.SOURCES[source])
+
+
 def compile_asm(source: str, extra=()) -> str:
-    """hipcc -S of maskrcnn_amd/csrc/<source>, cached by mtime of the source and the headers."""
+    """hipcc -S of maskrcnn_amd/csrc/<source> with the flags the product build gives it, cached by mtime of the source, the headers
+    and build.py."""
     os.makedirs(OUT, exist_ok=True)
     src = os.path.join(CSRC, source)
     dst = os.path.join(OUT, source.replace(".hip", "") + ("_" + "_".join(e.lstrip("-D") for e in extra) if extra else "") + ".s")
-    deps = [src] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "maskrcnn_hip.h")]
+    deps = [src, BUILD_PY] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "maskrcnn_hip.h")]
     if not os.path.exists(dst) or os.path.getmtime(dst) < max(os.path.getmtime(d) for d in deps):
         hipcc = os.environ.get("HIPCC") or "/opt/rocm/bin/hipcc"
-        r = subprocess.run([hipcc, *FLAGS, *extra, src, "-o", dst], capture_output=True, text=True)
+        r = subprocess.run([hipcc, *FLAGS, *build_flags(source), *extra, src, "-o", dst], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(r.stderr)
     return open(dst).read()
@@ -265,6 +285,77 @@ def audit(insts, require_no_dma_behind_asm_vmcnt=True) -> list:
     return uniq
 
 
+# how a compare + branch pair guards an arm: (compare, branch) -> the arm is taken for n >= constant + this (an equality test
+# stands for >=: the arms above it have been ruled out)
+GUARDS = {("lt_i32", "scc0"): 0, ("ge_i32", "scc1"): 0, ("lg_u32", "scc0"): 0, ("lg_i32", "scc0"): 0, ("eq_u32", "scc1"): 0,
+          ("eq_i32", "scc1"): 0, ("gt_i32", "scc1"): 1, ("le_i32", "scc0"): 1}
+
+
+def vmcnt_ladders(insts) -> list:
+    """The compare ladders that end in asm s_waitcnt vmcnt(N): [[(guard constant, immediate, line), ...]] in the order the
+    compares test the arms, the arm nothing guards (every compare failed) last with guard 0. An arm whose compare, branch or wait
+    is not understood has None in the place of what is missing."""
+    at = {ins.label: k for k, ins in enumerate(insts) if ins.label}
+
+    def wait_behind(k):
+        """The asm vmcnt wait within four instructions of index k, before any other label."""
+        for j in range(k, min(k + 4, len(insts))):
+            if j > k and insts[j].label:
+                return None
+            if insts[j].asm and insts[j].op.startswith("s_waitcnt") and vm_n(insts[j]) is not None:
+                return insts[j]
+        return None
+
+    def pair(k):
+        """(register, guard constant or None, branch target, instructions taken) when a scalar compare with a constant stands at
+        insts[k] and a branch on SCC behind it (a scalar move, which leaves SCC alone, may stand between the two)."""
+        if k + 1 >= len(insts):
+            return None
+        c = insts[k]
+        n = 3 if insts[k + 1].op.startswith("s_mov_b") and k + 2 < len(insts) else 2
+        b = insts[k + n - 1]
+        m = re.fullmatch(r"s_cmpk?_(\w+)", c.op)
+        if not m or len(c.ops) != 2 or not re.fullmatch(r"-?(0x[0-9a-f]+|\d+)", c.ops[1]) or not b.op.startswith("s_cbranch_scc") or not b.ops:
+            return None
+        add = GUARDS.get((m.group(1), b.op[len("s_cbranch_"):]))
+        return c.ops[0], None if add is None else int(c.ops[1], 0) + add, b.ops[0], n
+
+    out, k = [], 0
+    while k < len(insts):
+        run, end = [], k
+        while (p := pair(end)) and (not run or p[0] == run[0][0]):
+            run.append(p + (insts[end].line,))
+            end += p[3]
+        if len(run) < 3:
+            k += 1
+            continue
+        arms = []
+        for _, guard, target, _, line in run:
+            w = wait_behind(at[target]) if target in at else None
+            arms.append((guard, vm_n(w) if w else None, w.line if w else line))
+        w = wait_behind(end)
+        arms.append((0, vm_n(w) if w else None, w.line if w else insts[end - 1].line))
+        if sum(a[1] is not None for a in arms) >= 3:      # a chain of compares that selects among asm waits
+            out.append(arms)
+        k = end
+    return out
+
+
+def audit_ladders(insts) -> list:
+    """Check G on every ladder of the kernel."""
+    viol = []
+    for arms in vmcnt_ladders(insts):
+        for n, (guard, imm, line) in enumerate(arms):
+            if guard is None or imm is None:
+                viol.append(("G", line, f"arm {n} of the vmcnt ladder is not understood (guard {guard}, immediate {imm})"))
+            elif imm > guard:
+                viol.append(("G", line, f"arm {n} of the vmcnt ladder waits with vmcnt({imm}) where the budget is only known to be >= {guard}"))
+        imms = [imm for _, imm, _ in arms if imm is not None]
+        if any(a <= b for a, b in zip(imms, imms[1:])) or imms[-1:] != [0]:
+            viol.append(("G", arms[0][2], f"the vmcnt ladder's immediates {imms} do not strictly decrease to 0"))
+    return viol
+
+
 def has_asm_contract(insts) -> bool:
     return any(i.asm and (i.is_lds or i.op in MFMA_PASSES or (i.op.startswith("s_waitcnt") and vm_n(i) is not None)) for i in insts)
 
@@ -279,6 +370,11 @@ SOURCES = {
     # conv_f16p: asm ds_read_b128 behind lgkmcnt(0), counted vmcnt(N) that deliberately leaves later tiles' DMAs in flight
     "conv_f16p.hip": {"dma_free_behind_asm_vmcnt": False,
                       "spills": lambda name, meta: meta["vgpr_spill_count"] == 0 and meta["private_segment_fixed_size"] == 0},
+    # crop_forward_nchw_staged: asm ds_read2_b32 retired by a counted lgkmcnt(8) / lgkmcnt(0), and a run-time vmcnt budget on a
+    # 16-arm ladder that deliberately leaves the groups ahead (LDS-DMA) and the stores in flight
+    "crop.hip": {"dma_free_behind_asm_vmcnt": False,
+                 "spills": lambda name, meta: meta["vgpr_spill_count"] == 0 and meta["private_segment_fixed_size"] == 0,
+                 "ladder_arms": 16},
 }
 
 
@@ -289,14 +385,18 @@ def audit_source(source: str, text: str | None = None) -> dict:
     for name, k in ks.items():
         if not has_asm_contract(k["insts"]):
             continue
-        v = audit(k["insts"], spec["dma_free_behind_asm_vmcnt"])
+        v = audit(k["insts"], spec["dma_free_behind_asm_vmcnt"]) + audit_ladders(k["insts"])
         if not spec["spills"](name, k["meta"]):
             v.append(("F", 0, f"spills: {k['meta']}"))
+        ladders = vmcnt_ladders(k["insts"])
+        if "ladder_arms" in spec and [len(a) for a in ladders] != [spec["ladder_arms"]]:
+            v.append(("G", 0, f"expected one vmcnt ladder of {spec['ladder_arms']} arms, found {[len(a) for a in ladders]}"))
         report[name] = {"violations": v, "meta": k["meta"], "instructions": len(k["insts"]),
                         "asm_mfma": sum(1 for i in k["insts"] if i.asm and i.op in MFMA_PASSES),
                         "asm_lds_reads": sum(1 for i in k["insts"] if i.asm and i.is_lds),
                         "lds_dma": sum(1 for i in k["insts"] if i.is_dma),
-                        "asm_vmcnt_waits": sum(1 for i in k["insts"] if i.asm and i.op.startswith("s_waitcnt") and vm_n(i) is not None)}
+                        "asm_vmcnt_waits": sum(1 for i in k["insts"] if i.asm and i.op.startswith("s_waitcnt") and vm_n(i) is not None),
+                        "ladders": [[(g, n) for g, n, _ in a] for a in ladders]}
     return report
 
 
@@ -322,6 +422,26 @@ def mutations(text: str) -> dict:
     return out
 
 
+def crop_mutations(text: str) -> dict:
+    """Edits of crop.hip's generated code that break one contract each; every one must be reported."""
+    out = {}
+    # the counted LDS wait one too loose: the first channel's last read is still outstanding when its result is used
+    out["lgkmcnt(8) -> lgkmcnt(9) between the two channels in flight"] = ("A", text.replace("s_waitcnt lgkmcnt(8)", "s_waitcnt lgkmcnt(9)"))
+    # one arm of the ladder waits for less than its guard promises: equal to the arm above it ...
+    out["ladder arm 7 waits with vmcnt(8)"] = ("G", text.replace(";;#ASMSTART\n\ts_waitcnt vmcnt(7)\n", ";;#ASMSTART\n\ts_waitcnt vmcnt(8)\n"))
+    # ... or still in order, but above its own guard
+    out["ladder arm 14 waits with vmcnt(15)"] = ("G", text.replace(";;#ASMSTART\n\ts_waitcnt vmcnt(14)\n", ";;#ASMSTART\n\ts_waitcnt vmcnt(15)\n"))
+    # the arm nothing guards must drain everything
+    out["the ladder's last arm waits with vmcnt(1)"] = ("G", text.replace(";;#ASMSTART\n\ts_waitcnt vmcnt(0)\n", ";;#ASMSTART\n\ts_waitcnt vmcnt(1)\n"))
+    # a spill of an asm read's destination between the read and its wait
+    m = re.search(r"(;;#ASMSTART\n\tds_read2_b32 (v\[(\d+):\d+\]), [^\n]*\n\t;;#ASMEND\n)", text)
+    out["spill of an asm LDS read's destination before its wait"] = ("A", text.replace(m.group(1), m.group(1) + f"\tscratch_store_dword off, v{m.group(3)}, off offset:60\n", 1))
+    return out
+
+
+MUTATIONS = {"conv_wino4.hip": mutations, "crop.hip": crop_mutations}
+
+
 if __name__ == "__main__":
     bad = 0
     for source in SOURCES:
@@ -333,11 +453,12 @@ if __name__ == "__main__":
                 print("    ", v)
             bad += len(r["violations"])
     if "--mutations" in sys.argv:
-        text = compile_asm("conv_wino4.hip")
-        for what, (check, mutated) in mutations(text).items():
-            assert mutated != text, what
-            rep = audit_source("conv_wino4.hip", mutated)
-            found = sorted({v[0] for r in rep.values() for v in r["violations"]})
-            print(f"mutation '{what}': checks that fire {found} (expected {check})")
-            bad += check not in found
+        for source, mutate in MUTATIONS.items():
+            text = compile_asm(source)
+            for what, (check, mutated) in mutate(text).items():
+                assert mutated != text, what
+                rep = audit_source(source, mutated)
+                found = sorted({v[0] for r in rep.values() for v in r["violations"]})
+                print(f"{source}: mutation '{what}': checks that fire {found} (expected {check})")
+                bad += check not in found
     sys.exit(1 if bad else 0)
