@@ -15,10 +15,11 @@ On such data every one of these kernels is exactly computable:
 The references are F.conv2d / F.conv_transpose2d / F.max_pool2d in float64. Every reference takes `mut`, ONE thing done wrong
 (MUTANTS): the host test asserts that each mutant changes `want`, i.e. that the data would notice that error in a kernel.
 
-F(4x4) (csrc/conv_wino4.hip) is NOT here: with the interpolation points 0, +-3/4, +-3/2 its G has the entries 64/81, 32/81 and
-8/27, U = G g G^T is not dyadic for integer g, so no data make its fp32 sums independent of their order. Those kernels stay
-with the tolerance tests of tests/test_gpu_conv.py, where their fused forms are already tied bit for bit to
-conv3x3_winograd4 + conv_bn_act."""
+F(4x4) (csrc/conv_wino4.hip) is not here but in tests/wino4_exact_cases.py: with the interpolation points 0, +-3/4, +-3/2 its
+G has the entries 64/81, 32/81 and 8/27, U = G g G^T is not dyadic for integer g, so no CONVOLUTION is exact there. But those
+kernels take U as an operand, and B^T and A^T are dyadic: on a synthetic integer U the bilinear form they evaluate is exact, and
+that sweep holds them to it bit for bit (the tolerance tests of tests/test_gpu_conv.py keep showing that the form is a
+convolution)."""
 import dataclasses
 import functools
 import types

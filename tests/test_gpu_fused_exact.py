@@ -8,10 +8,10 @@ bits; image (RoI) i of a batch equals image i alone. The last test runs the file
 there a hand-placed barrier that orders too little contradicts a bit pattern.
 
 What this proves is indexing, padding, tails, layouts, the place of every rounding and of the residual. It does not measure
-accumulation accuracy on real-valued data: that stays with the tolerance tests of tests/test_gpu_conv.py — and so do the F(4x4)
-kernels (csrc/conv_wino4.hip) altogether: their G holds 64/81, 32/81 and 8/27, U = G g G^T is not dyadic for integer g, and no
-data make their fp32 sums independent of the order (their fused forms are tied bit for bit to conv3x3_winograd4 + conv_bn_act
-there)."""
+accumulation accuracy on real-valued data: that stays with the tolerance tests of tests/test_gpu_conv.py. The F(4x4) kernels
+(csrc/conv_wino4.hip) have a sweep of their own, tests/test_gpu_wino4_exact.py: their G holds 64/81, 32/81 and 8/27, so U = G g G^T
+is not dyadic for integer g and no convolution is exact; but they take U as an operand, and on a synthetic integer U the bilinear
+form A^T [sum U .* (B^T d B)] A is."""
 import dataclasses
 import os
 import subprocess
