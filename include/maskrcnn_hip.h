@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 36
+#define MRCNN_ABI_VERSION 37
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -48,7 +48,8 @@ const char* mrcnn_arch(void);
  * S independent segments are processed by one launch (one workgroup per segment).
  *   dets        [S][n_max] rows (y1,x1,y2,x2,score); element (s,i,c) at
  *               dets[s*seg_stride + i*row_stride + c*col_stride]   (strides in elements)
- *   seg_counts  int32[S] boxes in each segment (<= n_max), device memory; NULL = all n_max
+ *   seg_counts  int32[S] boxes in each segment, device memory; NULL = all n_max. An entry outside [0, n_max] is clamped
+ *               into it (a negative count is 0 boxes, a count above n_max is n_max); rows at and past the count are never read
  *   class_ids   int32, element (s,i) at class_ids[s*n_max + i]; NULL = single class. When given,
  *               a box only suppresses boxes of the same class: the one-pass form of the per-class
  *               loop in MaskRCNN.mrn_refine (model.py:1454-1475).
@@ -67,6 +68,13 @@ int mrcnn_nms_batched_f32(const float* dets, int32_t num_segments, int64_t n_max
                           const int32_t* class_ids, float threshold, int64_t* keep_out,
                           int32_t* counts_out, void* workspace, size_t workspace_bytes,
                           mrcnn_stream_t stream);
+/* What mrcnn_nms_batched_f32 launches for this n_max — the launcher's own answer (it launches from the same function), host
+ * arithmetic only, no device needed. has_workspace: whether a workspace pointer is passed. n_max as limited above.
+ *   plan_out[0] path: 0 the single LDS-resident launch (nms_kernel), 1 sort → pair mask → scan on the workspace
+ *   plan_out[1] boxes the LDS kernel (path 0) / the sort kernel (path 1) is instantiated for: 256, 1024, 2048, 4096 (8192, 16384)
+ *   plan_out[2] threads of that kernel's workgroup (256 or 1024)
+ *   plan_out[3] path 1: 1 when the scan holds the segment's column words in LDS, 0 when it reads them from L2; path 0: 0 */
+int mrcnn_nms_plan(int64_t n_max, int32_t has_workspace, int32_t plan_out[4]);
 
 /* The rest of the reference's nms surface: ANY number of boxes, and float64 boxes (cpu/nms_cpu.cpp:73-79 dispatches over the
  * floating types; nms.h:15 takes a float threshold either way). One segment; arithmetic in the boxes' own type; the same

@@ -457,9 +457,49 @@ size_t ws_layout(int32_t S, int64_t n_max, void* base, NmsWs* ws) {
 constexpr int64_t NMS_MAX_WS = 16384, NMS_MAX_LDS = 4096;
 extern "C" int64_t mrcnn_nms_max_boxes(void) { return NMS_MAX_WS; }
 
+namespace {
+
+// What mrcnn_nms_batched_f32 launches, decided HERE and nowhere else: the launcher launches from it, mrcnn_nms_plan reports it.
+// path 1: sort (nms_sort_kernel<cap, 1024>) → pair mask → scan, the scan's column words in LDS when scan_lds (else read from
+// L2), scan_bytes of dynamic LDS; path 0: nms_kernel<cap, threads>. n_max is in range for the path (the callers check).
+struct NmsPlan {
+    int path, cap, threads, scan_lds;
+    size_t scan_bytes;
+};
+NmsPlan nms_plan(int64_t n_max, bool has_workspace) {
+    if (has_workspace && n_max > 128) {
+        const int cap = n_max <= 1024 ? 1024 : n_max <= 2048 ? 2048 : n_max <= 4096 ? 4096 : n_max <= 8192 ? 8192 : 16384;
+        const size_t np = static_cast<size_t>((n_max + 63) / 64 * 64), nb = np / 64;   // ws_layout's
+        const size_t tail = (np + 7) / 8 * 8 + sizeof(u64) * (nb + 2);
+        const size_t lds_full = sizeof(u64) * np * nb + tail;
+        const bool in_lds = lds_full <= 150 * 1024;
+        return NmsPlan{1, cap, 1024, in_lds ? 1 : 0, in_lds ? lds_full : tail};
+    }
+    if (n_max <= 256) return NmsPlan{0, 256, 256, 0, 0};
+    const int cap = n_max <= 1024 ? 1024 : n_max <= 2048 ? 2048 : 4096;
+    return NmsPlan{0, cap, 1024, 0, 0};
+}
+int64_t nms_limit(bool has_workspace, int64_t n_max) { return (has_workspace && n_max > 128) ? NMS_MAX_WS : NMS_MAX_LDS; }
+
+}  // namespace
+
 extern "C" size_t mrcnn_nms_workspace_bytes(int32_t num_segments, int64_t n_max) {
     if (num_segments < 1 || n_max < 1 || n_max > NMS_MAX_WS) return 0;
     return ws_layout(num_segments, n_max, nullptr, nullptr);
+}
+
+// What mrcnn_nms_batched_f32 launches for this n_max (see the header): nms_plan's answer, host arithmetic only.
+extern "C" int mrcnn_nms_plan(int64_t n_max, int32_t has_workspace, int32_t plan_out[4]) {
+    MRCNN_REQUIRE(plan_out, "nms_plan: null plan_out");
+    MRCNN_REQUIRE(n_max >= 1 && n_max <= nms_limit(has_workspace != 0, n_max),
+                  "nms_plan: n_max=%lld outside [1, %lld] (%lld with a workspace)", (long long)n_max, (long long)NMS_MAX_LDS,
+                  (long long)NMS_MAX_WS);
+    const NmsPlan p = nms_plan(n_max, has_workspace != 0);
+    plan_out[0] = p.path;
+    plan_out[1] = p.cap;
+    plan_out[2] = p.threads;
+    plan_out[3] = p.scan_lds;
+    return MRCNN_OK;
 }
 
 extern "C" int mrcnn_nms_batched_f32(const float* dets, int32_t num_segments, int64_t n_max,
@@ -469,11 +509,12 @@ extern "C" int mrcnn_nms_batched_f32(const float* dets, int32_t num_segments, in
                                      void* workspace, size_t workspace_bytes, mrcnn_stream_t stream) {
     MRCNN_REQUIRE(dets && keep_out && counts_out, "nms: null pointer");
     MRCNN_REQUIRE(num_segments >= 1, "nms: num_segments=%d must be >= 1", num_segments);
-    MRCNN_REQUIRE(n_max >= 1 && n_max <= ((workspace && n_max > 128) ? NMS_MAX_WS : NMS_MAX_LDS),
+    MRCNN_REQUIRE(n_max >= 1 && n_max <= nms_limit(workspace != nullptr, n_max),
                   "nms: n_max=%lld outside [1, %lld] (%lld with a workspace)", (long long)n_max, (long long)NMS_MAX_LDS,
                   (long long)NMS_MAX_WS);
     hipStream_t s = mrcnn::as_stream(stream);
-    if (workspace && n_max > 128) {
+    const NmsPlan p = nms_plan(n_max, workspace != nullptr);
+    if (p.path == 1) {
         // ---- path 2: sort → pair mask over the whole chip → serial scan ------------------------------
         MRCNN_REQUIRE(workspace_bytes >= mrcnn_nms_workspace_bytes(num_segments, n_max),
                       "nms: workspace too small (%zu < %zu bytes)", workspace_bytes,
@@ -482,16 +523,16 @@ extern "C" int mrcnn_nms_batched_f32(const float* dets, int32_t num_segments, in
         NmsWs ws;
         ws_layout(num_segments, n_max, workspace, &ws);
         int rc;
-        if (n_max <= 1024)
+        if (p.cap == 1024)
             rc = launch_sort<1024, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                          seg_counts, class_ids, ws, s);
-        else if (n_max <= 2048)
+        else if (p.cap == 2048)
             rc = launch_sort<2048, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                          seg_counts, class_ids, ws, s);
-        else if (n_max <= 4096)
+        else if (p.cap == 4096)
             rc = launch_sort<4096, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                          seg_counts, class_ids, ws, s);
-        else if (n_max <= 8192)
+        else if (p.cap == 8192)
             rc = launch_sort<8192, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                          seg_counts, class_ids, ws, s);
         else
@@ -501,27 +542,25 @@ extern "C" int mrcnn_nms_batched_f32(const float* dets, int32_t num_segments, in
         hipLaunchKernelGGL(nms_mask_kernel, dim3(ws.nb * (ws.nb + 1) / 2, num_segments), dim3(64), 0, s, ws,
                            threshold);
         if ((rc = mrcnn::check_launch("nms_mask_kernel"))) return rc;
-        const size_t tail = (ws.np + 7) / 8 * 8 + sizeof(u64) * (ws.nb + 2);
-        const size_t lds_full = sizeof(u64) * ws.np * ws.nb + tail;
-        if (lds_full <= 150 * 1024) {
+        if (p.scan_lds) {
             auto k = nms_scan_kernel<true>;
-            if ((rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds_full, "nms"))) return rc;
-            hipLaunchKernelGGL(k, dim3(num_segments), dim3(256), lds_full, s, ws, n_max, seg_counts, keep_out,
+            if ((rc = mrcnn::ensure_dynamic_lds(reinterpret_cast<const void*>(k), p.scan_bytes, "nms"))) return rc;
+            hipLaunchKernelGGL(k, dim3(num_segments), dim3(256), p.scan_bytes, s, ws, n_max, seg_counts, keep_out,
                                counts_out);
         } else {
-            hipLaunchKernelGGL(nms_scan_kernel<false>, dim3(num_segments), dim3(256), tail, s, ws, n_max,
+            hipLaunchKernelGGL(nms_scan_kernel<false>, dim3(num_segments), dim3(256), p.scan_bytes, s, ws, n_max,
                                seg_counts, keep_out, counts_out);
         }
         return mrcnn::check_launch("nms_scan_kernel");
     }
     // ---- path 1: one LDS-resident workgroup per segment, no workspace --------------------------------
-    if (n_max <= 256)
+    if (p.cap == 256)
         return launch<256, 256>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                 seg_counts, class_ids, threshold, keep_out, counts_out, s);
-    if (n_max <= 1024)
+    if (p.cap == 1024)
         return launch<1024, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                   seg_counts, class_ids, threshold, keep_out, counts_out, s);
-    if (n_max <= 2048)
+    if (p.cap == 2048)
         return launch<2048, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,
                                   seg_counts, class_ids, threshold, keep_out, counts_out, s);
     return launch<4096, 1024>(dets, num_segments, n_max, seg_stride, row_stride, col_stride,

@@ -84,6 +84,19 @@ def nms_batched(dets: torch.Tensor, threshold: float, seg_counts: torch.Tensor |
 NMS_MAX_BOXES = int(lib.mrcnn_nms_max_boxes())   # per segment on the fp32 LDS / pair-mask paths (csrc/nms.hip)
 
 
+NmsPlan = collections.namedtuple("NmsPlan", "path cap threads scan_in_lds")
+NMS_PATHS = ("lds", "workspace")
+
+
+def nms_plan(n_max: int, has_workspace: bool = True) -> NmsPlan:
+    """What nms_batched launches for n_max boxes per segment: the launcher's own answer (mrcnn_nms_plan), path as a name.
+    cap / threads: the instantiation of the LDS kernel ("lds") or of the sort kernel ("workspace"); scan_in_lds: whether the
+    scan of the "workspace" path holds its column words in LDS. Host arithmetic only — no GPU is needed."""
+    out = (c_i32 * 4)()
+    check(lib.mrcnn_nms_plan(int(n_max), 1 if has_workspace else 0, out))
+    return NmsPlan(NMS_PATHS[out[0]], int(out[1]), int(out[2]), bool(out[3]))
+
+
 @_on_device
 def nms_general(dets: torch.Tensor, threshold: float):
     """dets [N, >=5] float32 or float64, any strides, any N → (keep int64 [N] ascending input indices padded with -1, count

@@ -42,6 +42,7 @@ def test_header_parser_yields_the_hand_written_signatures():
         "mrcnn_last_error": (ctypes.c_char_p, []),
         "mrcnn_nms_max_boxes": (c_i64, []),
         "mrcnn_nms_workspace_bytes": (c_size, [c_i32, c_i64]),
+        "mrcnn_nms_plan": (c_int, [c_i64, c_i32, P(c_i32)]),
         "mrcnn_nms_batched_f32": (c_int, [c_vp, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                           c_f32, c_vp, c_vp, c_vp, c_size, c_vp]),
         "mrcnn_roi_align_pyramid_counted_f32": (c_int, [P(c_vp), P(c_i32), P(c_i32),
