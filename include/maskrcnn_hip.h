@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MRCNN_ABI_VERSION 37
+#define MRCNN_ABI_VERSION 38 /* 38: mrcnn_resize_u8_route, mrcnn_paste_masks_store_width */
 
 #define MRCNN_OK 0
 #define MRCNN_ERR_INVALID_ARGUMENT (-1) /* bad shape / null pointer / unsupported size          */
@@ -685,12 +685,23 @@ int mrcnn_nhwc_to_nchw_f32(const float* x, int32_t batch, int32_t channels, int3
  * mrcnn_resize_bilinear_u8: n images of one size, src[i] [in_h][in_w][channels] interleaved uint8 at
  *   src + i*src_image_stride with src_row_stride bytes between rows (so a crop of a larger image — transform.CenterCrop
  *   before Resize in decode_masks, data.py:272-277 — needs no copy) -> dst n x [out_h][out_w][channels] contiguous,
- *   each == numpy.array(Image.fromarray(src[i]).resize((out_w, out_h), Image.BILINEAR)). channels 1..4, sizes <= 16384. */
+ *   channels 1..4, sizes <= 16384. Every channel is resampled on its own, PER CHANNEL: each image equals a per-band Pillow
+ *   resize always, and numpy.array(Image.fromarray(src[i]).resize((out_w, out_h), Image.BILINEAR)) for 1 and 3 channels
+ *   (L, RGB); for 2 and 4 channels Pillow reads LA / RGBA and premultiplies by alpha around the resample, so that call
+ *   gives the same bytes only where alpha is 255. */
 size_t mrcnn_resize_u8_workspace_bytes(int32_t n, int32_t in_h, int32_t in_w, int32_t channels, int32_t out_h,
                                        int32_t out_w);
 int mrcnn_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t in_h, int32_t in_w, int32_t channels,
                              int64_t src_image_stride, int64_t src_row_stride, uint8_t* dst, int32_t out_h,
                              int32_t out_w, void* workspace, size_t workspace_bytes, mrcnn_stream_t stream);
+/* Which launch sequence mrcnn_resize_bilinear_u8 takes for these arguments — the launcher's own answer (it chooses through the
+ * same function), host arithmetic only, no device needed. dst_alignment / workspace_alignment: the two pointers' addresses
+ * modulo 16 (0: 16-byte aligned). Returns -1 for shapes the entry point refuses (n 1..65536), else
+ *   0 fused: both passes in one launch, the 8-bit intermediate in LDS (1 channel, not shrinking, out_w % 16 == 0, aligned dst)
+ *   1 h-fast + v-fast      2 h-fast + v-generic      3 h-generic + v-fast      4 h-generic + v-generic
+ * h-fast: 1 channel, not shrinking in width, out_w % 4 == 0.  v-fast: out_w * channels % 16 == 0, dst and workspace aligned. */
+int mrcnn_resize_u8_route(int32_t n, int32_t in_h, int32_t in_w, int32_t channels, int32_t out_h, int32_t out_w,
+                          int32_t dst_alignment, int32_t workspace_alignment);
 /* Replaces utils.resize_image's resize + pad (utils.py:72-88), mold_image (model.py:1750-1754) and the HWC -> CHW
  * float conversion of detect() (model.py:1108-1110) for one RGB image: src uint8 [in_h][in_w][3] is resized to
  * new_h x new_w (no resample when that equals the input size), placed at (top, left) of a zero canvas out_h x out_w,
@@ -712,13 +723,17 @@ int mrcnn_mold_images_u8(const uint8_t* src, int32_t n, int64_t src_image_stride
  * (clamp, truncate: Image.fromarray(F).convert('L')), resized to the box's int(y2-y1) x int(x2-x1) and pasted at
  * (int(y1), int(x1)) of a zero height x width canvas; out[i][y][x] = on_value where the 8-bit value > 127, else 0
  * (on_value 1: the boolean mask of data.py:308; 255: the same mask as the 'L' image decode_masks starts from).
- * Boxes the reference cannot paste (empty, or not inside the canvas: PIL raises) give an all-zero mask, as do
- * class ids outside [0, num_classes) — so padded detection slots (class 0, zero box) cost nothing and stay empty.
+ * Boxes the reference cannot paste (empty, or not inside the canvas: PIL raises; a NaN or infinite coordinate) give an
+ * all-zero mask, as do class ids outside [0, num_classes) — so padded detection slots (class 0, zero box) cost nothing and stay empty.
+ * A NaN mask value is grey level 0 (defined here; the reference leaves it to the platform's conversion, 0 on x86).
  * mask_h, mask_w <= 64; width % 4 == 0. */
 int mrcnn_paste_masks_u8(const float* masks, int64_t stride_n, int64_t stride_y, int64_t stride_x, int64_t stride_c,
                          int32_t n, int32_t mask_h, int32_t mask_w, int32_t num_classes, const int64_t* class_ids,
                          const float* boxes, int32_t height, int32_t width, int32_t on_value, uint8_t* out,
                          mrcnn_stream_t stream);
+/* Bytes per store of mrcnn_paste_masks_u8 for a canvas of this width at an `out` whose address modulo 16 is out_alignment:
+ * 16 (width % 16 == 0 and an aligned out) or 4. The launcher's own answer; host arithmetic only. */
+int mrcnn_paste_masks_store_width(int32_t width, int32_t out_alignment);
 /* COCO run-length encoding of n single-channel 8-bit masks — replaces maskUtils.encode(np.asfortranarray(mask)) per
  * detection in build_coco_results (coco.py:40-60): rleEncode, rleToString, rleArea and rleToBbox of
  * cocoapi/common/maskApi.c applied to the mask binarised as byte > threshold (0: the 0/1 and 0/255 masks of

@@ -288,6 +288,24 @@ unsigned blocks_for(int64_t n) {
     return static_cast<unsigned>(b < 1 ? 1 : b > 256 * 32 ? 256 * 32 : b);
 }
 
+// Which kernels a resize launches, decided HERE for the launchers and for the mrcnn_resize_u8_route query alike.
+bool h_pass_fast(int c, const ResizePlan& p, int out_w) { return c == 1 && p.ah.ksize == 3 && out_w % 4 == 0; }
+
+enum ResizeRoute { ROUTE_FUSED = 0, ROUTE_HFAST_VFAST = 1, ROUTE_HFAST_VGENERIC = 2, ROUTE_HGENERIC_VFAST = 3, ROUTE_GENERIC = 4 };
+
+// dst_misalign / ws_misalign: the pointers' addresses modulo 16
+int resize_route(int n, int in_h, int in_w, int c, int out_h, int out_w, const ResizePlan& p, unsigned dst_misalign,
+                 unsigned ws_misalign) {
+    // single-channel enlargement with aligned rows (decode_masks): both passes in one launch, the intermediate stays in LDS
+    const int64_t fv_tiles = static_cast<int64_t>(n) * ((out_h + FV_ROWS - 1) / FV_ROWS) * ((out_w + FV_COLS - 1) / FV_COLS);
+    if (c == 1 && p.ah.ksize == 3 && p.av.ksize == 3 && out_w % 16 == 0 && out_h >= in_h && out_w >= in_w &&
+        dst_misalign == 0 && fv_tiles <= 0x7FFFFFFF)
+        return ROUTE_FUSED;
+    const bool hf = h_pass_fast(c, p, out_w);
+    const bool vf = (static_cast<int64_t>(out_w) * c) % 16 == 0 && dst_misalign == 0 && ws_misalign == 0;
+    return hf ? (vf ? ROUTE_HFAST_VFAST : ROUTE_HFAST_VGENERIC) : (vf ? ROUTE_HGENERIC_VFAST : ROUTE_GENERIC);
+}
+
 // coefficient tables + horizontal pass; leaves the intermediate at workspace[0..)
 int run_horizontal(const uint8_t* src, int n, int in_h, int in_w, int c, int64_t image_stride, int64_t row_stride,
                    int out_h, int out_w, const ResizePlan& p, unsigned char* ws, hipStream_t s) {
@@ -298,7 +316,7 @@ int run_horizontal(const uint8_t* src, int n, int in_h, int in_w, int c, int64_t
     int* kv = reinterpret_cast<int*>(ws + p.off_kv);
     hipLaunchKernelGGL(coeffs_kernel, dim3((out_w + 255) / 256), dim3(256), 0, s, p.ah, bh, kh);
     hipLaunchKernelGGL(coeffs_kernel, dim3((out_h + 255) / 256), dim3(256), 0, s, p.av, bv, kv);
-    if (c == 1 && p.ah.ksize == 3 && out_w % 4 == 0) {
+    if (h_pass_fast(c, p, out_w)) {
         const dim3 grid(static_cast<unsigned>((static_cast<int64_t>(n) * in_h + RH_ROWS - 1) / RH_ROWS),
                         static_cast<unsigned>((out_w / 4 + 255) / 256));
         hipLaunchKernelGGL(resample_h1_u8_fast, grid, dim3(256), 0, s, src, n * in_h, in_h, in_w, image_stride, row_stride, out_w,
@@ -346,12 +364,16 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(const PasteParams p) {
     const int tid = threadIdx.x;
     const float* b = p.boxes + 4 * static_cast<int64_t>(det);
     const double y1 = b[0], x1 = b[1], y2 = b[2], x2 = b[3];
-    const int bh = static_cast<int>(y2 - y1), bw = static_cast<int>(x2 - x1);  // data.py:295 int(box.height()), ...
-    const int top = static_cast<int>(y1), left = static_cast<int>(x1);         // :298,300
+    const double dh = y2 - y1, dw = x2 - x1;
     const int64_t cls = p.class_ids[det];
-    // boxes the reference cannot paste (empty, or not inside the canvas: PIL raises) give an all-zero mask
-    const bool valid = bh > 0 && bw > 0 && top >= 0 && left >= 0 && top + bh <= p.H && left + bw <= p.W &&
-                       cls >= 0 && cls < p.C;
+    // boxes the reference cannot paste (empty, or not inside the canvas: PIL raises) give an all-zero mask. Decided on the
+    // doubles, before any narrowing: a NaN, an infinity or 3e9 has no defined int. int(height) >= 1; int(y1) >= 0, which
+    // -0.5 satisfies (int(-0.5) == 0) and -1 does not; int(y1) + int(height) <= H — and then all four fit an int.
+    const bool valid = isfinite(y1) && isfinite(x1) && isfinite(y2) && isfinite(x2) && dh >= 1.0 && dw >= 1.0 &&
+                       y1 > -1.0 && x1 > -1.0 && trunc(y1) + trunc(dh) <= static_cast<double>(p.H) &&
+                       trunc(x1) + trunc(dw) <= static_cast<double>(p.W) && cls >= 0 && cls < p.C;
+    const int bh = valid ? static_cast<int>(dh) : 0, bw = valid ? static_cast<int>(dw) : 0;  // data.py:295 int(box.height()), ...
+    const int top = valid ? static_cast<int>(y1) : 0, left = valid ? static_cast<int>(x1) : 0;  // :298,300
     uint8_t* out = p.out + static_cast<int64_t>(det) * p.H * p.W;
     if (!valid || row0 >= top + bh || row1 <= top) return;  // the canvas is already zero
     uint8_t* m8 = lds;
@@ -360,12 +382,14 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(const PasteParams p) {
     int* vb = reinterpret_cast<int*>(lds + p.off_vb);
     int* vk = reinterpret_cast<int*>(lds + p.off_vk);
 
-    // mask channel * 255.0 (fp32, data.py:291) -> 'L' (Pillow f2l: clamp, truncate)
+    // mask channel * 255.0 (fp32, data.py:291) -> 'L' (Pillow f2l: clamp, truncate). A NaN is 0 BY DEFINITION here: f2l
+    // leaves it to the float -> integer conversion, whose result for NaN is the platform's (0 on x86, where Pillow and the
+    // oracle were observed); !(v > 0) says so without converting it.
     const float* msrc = p.masks + det * p.sn + cls * p.sc;
     for (int i = tid; i < p.mh * p.mw; i += 256) {
         const int my = i / p.mw, mx = i - my * p.mw;
         const float v = msrc[my * p.sy + mx * p.sx] * 255.0f;
-        m8[i] = v <= 0.0f ? 0 : v >= 255.0f ? 255 : static_cast<uint8_t>(v);
+        m8[i] = !(v > 0.0f) ? 0 : v >= 255.0f ? 255 : static_cast<uint8_t>(v);
     }
     auto axis = [](int in_size, int out_size) {
         Axis a;
@@ -464,6 +488,13 @@ extern "C" size_t mrcnn_resize_u8_workspace_bytes(int32_t n, int32_t in_h, int32
     return plan_resize(n, in_h, in_w, channels, out_h, out_w).total;
 }
 
+extern "C" int mrcnn_resize_u8_route(int32_t n, int32_t in_h, int32_t in_w, int32_t channels, int32_t out_h, int32_t out_w,
+                                     int32_t dst_alignment, int32_t workspace_alignment) {
+    if (n < 1 || n > 65536 || !resize_args_ok(in_h, in_w, channels, out_h, out_w)) return -1;
+    return resize_route(n, in_h, in_w, channels, out_h, out_w, plan_resize(n, in_h, in_w, channels, out_h, out_w),
+                        static_cast<unsigned>(dst_alignment) & 15u, static_cast<unsigned>(workspace_alignment) & 15u);
+}
+
 extern "C" int mrcnn_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t in_h, int32_t in_w, int32_t channels,
                                         int64_t src_image_stride, int64_t src_row_stride, uint8_t* dst,
                                         int32_t out_h, int32_t out_w, void* workspace, size_t workspace_bytes,
@@ -479,10 +510,10 @@ extern "C" int mrcnn_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t i
     MRCNN_REQUIRE(workspace_bytes >= p.total, "resize_u8: workspace too small (%zu < %zu)", workspace_bytes, p.total);
     hipStream_t s = mrcnn::as_stream(stream);
     unsigned char* ws = static_cast<unsigned char*>(workspace);
-    // single-channel enlargement with aligned rows (decode_masks): both passes in one launch, the intermediate stays in LDS
-    const int64_t fv_tiles = static_cast<int64_t>(n) * ((out_h + FV_ROWS - 1) / FV_ROWS) * ((out_w + FV_COLS - 1) / FV_COLS);
-    if (channels == 1 && p.ah.ksize == 3 && p.av.ksize == 3 && out_w % 16 == 0 && out_h >= in_h && out_w >= in_w &&
-        (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && fv_tiles <= 0x7FFFFFFF) {
+    const int route = resize_route(n, in_h, in_w, channels, out_h, out_w, p, static_cast<unsigned>(reinterpret_cast<uintptr_t>(dst) & 15),
+                                   static_cast<unsigned>(reinterpret_cast<uintptr_t>(ws) & 15));
+    if (route == ROUTE_FUSED) {
+        const int64_t fv_tiles = static_cast<int64_t>(n) * ((out_h + FV_ROWS - 1) / FV_ROWS) * ((out_w + FV_COLS - 1) / FV_COLS);
         int* bh = reinterpret_cast<int*>(ws + p.off_bh);
         int* kh = reinterpret_cast<int*>(ws + p.off_kh);
         int* bv = reinterpret_cast<int*>(ws + p.off_bv);
@@ -496,7 +527,7 @@ extern "C" int mrcnn_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t i
     if (int rc = run_horizontal(src, n, in_h, in_w, channels, src_image_stride, src_row_stride, out_h, out_w, p, ws, s))
         return rc;
     const int64_t row = static_cast<int64_t>(out_w) * channels;
-    if (row % 16 == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0) {
+    if (route == ROUTE_HFAST_VFAST || route == ROUTE_HGENERIC_VFAST) {
         const int G = static_cast<int>(row / 16 < 256 ? row / 16 : 256), rpb = 256 / G;
         const int64_t total_rows = static_cast<int64_t>(n) * out_h;
         const dim3 grid(static_cast<unsigned>((total_rows + rpb - 1) / rpb), static_cast<unsigned>((row / 16 + 255) / 256));
@@ -549,6 +580,10 @@ extern "C" int mrcnn_mold_image_u8(const uint8_t* src, int32_t in_h, int32_t in_
                                 mean_pixel, dst, workspace, workspace_bytes, stream);
 }
 
+extern "C" int mrcnn_paste_masks_store_width(int32_t width, int32_t out_alignment) {
+    return width % 16 == 0 && (static_cast<unsigned>(out_alignment) & 15u) == 0 ? 16 : 4;
+}
+
 extern "C" int mrcnn_paste_masks_u8(const float* masks, int64_t stride_n, int64_t stride_y, int64_t stride_x,
                                     int64_t stride_c, int32_t n, int32_t mask_h, int32_t mask_w,
                                     int32_t num_classes, const int64_t* class_ids, const float* boxes, int32_t height,
@@ -580,7 +615,7 @@ extern "C" int mrcnn_paste_masks_u8(const float* masks, int64_t stride_n, int64_
     hipError_t e = hipMemsetAsync(out, 0, static_cast<size_t>(n) * height * width, s);
     if (e != hipSuccess) return mrcnn::fail(MRCNN_ERR_LAUNCH, "paste_masks: hipMemsetAsync: %s", hipGetErrorString(e));
     const dim3 grid(static_cast<unsigned>((height + TILE_ROWS - 1) / TILE_ROWS) * n);
-    if (width % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0)
+    if (mrcnn_paste_masks_store_width(width, static_cast<int32_t>(reinterpret_cast<uintptr_t>(out) & 15)) == 16)
         hipLaunchKernelGGL(paste_masks_kernel<16>, grid, dim3(256), o, s, p);
     else
         hipLaunchKernelGGL(paste_masks_kernel<4>, grid, dim3(256), o, s, p);

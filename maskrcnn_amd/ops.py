@@ -1127,8 +1127,11 @@ def deconv2x2(x: torch.Tensor, w, bias4: torch.Tensor, activation: int = 0, prod
 @_on_device
 def resize_bilinear_u8(image: torch.Tensor, out_h: int, out_w: int) -> torch.Tensor:
     """uint8 [H,W], [H,W,C] (C <= 4) or a batch [N,H,W] of single-channel images (rows contiguous; image and row
-    strides free, so a cropped view needs no copy) → uint8 of the same rank at out_h x out_w; every image
-    == Image.fromarray(a).resize((out_w, out_h), Image.BILINEAR)."""
+    strides free, so a cropped view needs no copy) → uint8 of the same rank at out_h x out_w. Pillow's 8-bit BILINEAR
+    resample per channel: the channels are resampled independently. That is Image.fromarray(a).resize((out_w, out_h),
+    Image.BILINEAR) for L and RGB, and for LA / RGBA (C = 2, 4) only where alpha is 255 — Pillow premultiplies those by
+    alpha around the resample —; it equals a per-band Pillow resize always. A [N,H,W] tensor with W <= 4 and contiguous
+    rows reads as [H,W,C]."""
     _need_gpu(image)
     if image.dtype != torch.uint8 or image.dim() not in (2, 3):
         raise RuntimeError(f"resize_bilinear_u8: expected a uint8 2-d or 3-d tensor, got {image.dtype} {tuple(image.shape)}")
@@ -1159,6 +1162,27 @@ def resize_bilinear_u8(image: torch.Tensor, out_h: int, out_w: int) -> torch.Ten
     check(lib.mrcnn_resize_bilinear_u8(a.data_ptr(), n, h, w, c, image_stride, row_stride, out.data_ptr(), out_h,
                                        out_w, ws.data_ptr(), nbytes, _stream()))
     return out
+
+
+RESIZE_ROUTES = ("fused", "hfast_vfast", "hfast_vgeneric", "hgeneric_vfast", "generic")
+
+
+def resize_route(n: int, in_h: int, in_w: int, channels: int, out_h: int, out_w: int, dst_alignment: int = 0,
+                 workspace_alignment: int = 0) -> str:
+    """The launch sequence mrcnn_resize_bilinear_u8 takes for n images [in_h,in_w,channels] → out_h x out_w: the launcher's
+    own answer (mrcnn_resize_u8_route), as a name. dst_alignment / workspace_alignment: the pointers' addresses modulo 16.
+    Host arithmetic only — no GPU is needed."""
+    code = int(lib.mrcnn_resize_u8_route(int(n), int(in_h), int(in_w), int(channels), int(out_h), int(out_w),
+                                         int(dst_alignment) & 15, int(workspace_alignment) & 15))
+    if code < 0:
+        raise RuntimeError(f"resize_route: mrcnn_resize_bilinear_u8 refuses {n} x {in_h}x{in_w}x{channels} -> {out_h}x{out_w}")
+    return RESIZE_ROUTES[code]
+
+
+def paste_store_width(width: int, out_alignment: int = 0) -> int:
+    """Bytes per store of paste_masks on a canvas of this width at an `out` whose address modulo 16 is out_alignment: 16 or 4
+    (mrcnn_paste_masks_store_width, the launcher's own answer). Host arithmetic only."""
+    return int(lib.mrcnn_paste_masks_store_width(int(width), int(out_alignment) & 15))
 
 
 @_on_device

@@ -119,10 +119,11 @@ int oracle_resize_bilinear_u8(const uint8_t* src, int in_h, int in_w, int c, uin
     return 0;
 }
 
-/* Convert.c f2l: float -> 8-bit, clamp then truncate */
+/* Convert.c f2l: float -> 8-bit, clamp then truncate. f2l hands a NaN to the float -> integer conversion, whose result is
+ * the platform's (0 on x86, observed through Pillow); here NaN is 0 by definition: !(v > 0) never converts it. */
 void oracle_f32_to_l8(const float* src, int64_t n, uint8_t* dst) {
     for (int64_t i = 0; i < n; i++) {
         float v = src[i];
-        dst[i] = v <= 0.0f ? 0 : v >= 255.0f ? 255 : (uint8_t)v;
+        dst[i] = !(v > 0.0f) ? 0 : v >= 255.0f ? 255 : (uint8_t)v;
     }
 }

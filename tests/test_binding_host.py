@@ -175,7 +175,8 @@ def test_registered_schemas_and_public_names_are_the_parents():
     assert set(ops.__all__) == set(PUBLIC) and len(ops.__all__) == len(PUBLIC)
     for name in PUBLIC + ["RLE_BAD_BYTE", "RLE_LONG_TOKEN", "RLE_OPEN_TOKEN", "RLE_BAD_SIZE", "RLE_BAD_OFFSETS", "RLE_EMPTY_RUN",
                           "RLE_PIXEL_SUM", "POLY_MAX_DIM", "POLY_MAX_PART_POINTS", "poly_host_bounds", "rle_string_tokens", "rle_table",
-                          "CONV_PROFILE", "BOTTLENECK_OP_FUSED", "NMS_MAX_BOXES", "nms_plan", "NmsPlan", "crop_plan", "CropPlan"]:
+                          "CONV_PROFILE", "BOTTLENECK_OP_FUSED", "NMS_MAX_BOXES", "nms_plan", "NmsPlan", "crop_plan", "CropPlan",
+                          "resize_route", "paste_store_width"]:
         assert hasattr(ops, name), name
 
 
